@@ -11,9 +11,13 @@ own pairs against its own index replica).
 The reference FASTA the metric names (GRCh37) is not available offline; the workload uses a seeded
 synthetic reference of GRCh37's size and contig-length proportions (order-6 Markov model of the
 bundled chr20 slice + planted repeat families; stated in config.workload).  The FM-index
-is built on the GPU (`bwa index` kernels, k_index.h) before the timed region.  After the timed region
-a sample of the same batch is aligned by the CPU oracle and compared record by record with the GPU's
-output (parity gate: a mismatch voids `value`); the same oracle run is the reported cpu_baseline.
+is built on the GPU (`bwa index` kernels, k_index.h) before the timed region.
+
+A plain run does only that: set up, warm up, time --steps steps, write --dump-outputs if asked, print the line.
+With --full, after the timed region a sample of the same batch is aligned by the CPU oracle and compared record
+by record with the GPU's output (parity gate: a mismatch voids `value`); the same oracle run is the reported
+cpu_baseline.  --full also adds the per-kernel times and the roofline, the 2x250 leg, the plugin-path and
+script legs and the N > 1 rehearsal.
 """
 import argparse
 import ctypes as C
@@ -346,13 +350,13 @@ def e2e_leg(a, td, prefix, reads, reads2, rl, ns, orc_exe, b=None, reads_long=No
 
 def script_leg(td, tag, ref_prefix, fq, n_pairs, threads, bwa, samblaster, sambamba, sort_mem_gb=40, config_extra="", env_extra=None, limit_s=300, ranks=0):
     """SURVEY.md 8d's own definition of the metric: the reference's `speedseq align` (the script itself, unmodified -- the fixture copy
-    tests/golden/speedseq_ref_script.sh, or /root/reference/bin/speedseq where that exists) on the executables speedseq.config names,
+    tests/golden/speedseq_ref_script.sh, a byte-for-byte copy of the reference's bin/speedseq) on the executables speedseq.config names,
     wall clock from FASTQ open to the three coordinate-sorted, indexed BAMs closed.  The index files are already next to `ref_prefix`.
     config_extra: further lines of speedseq.config (the script `source`s it: `export SSG_FUSED=1` switches the product's stages to
     the binary hand-off of speedseq_amd/host/fused.h)."""
     import shutil
     import subprocess
-    script = "/root/reference/bin/speedseq" if os.path.exists("/root/reference/bin/speedseq") else os.path.join(ROOT, "tests", "golden", "speedseq_ref_script.sh")
+    script = os.path.join(ROOT, "tests", "golden", "speedseq_ref_script.sh")
     awk = shutil.which("gawk") or shutil.which("mawk") or shutil.which("awk")
     if not os.path.exists(script) or awk is None:
         return {"skipped": "reference script fixture or awk not available"}
@@ -517,6 +521,61 @@ def literal_legs(a, td, prefix, rl, ns, b, orc_exe):
     return res
 
 
+DUMP_PAIRS = 16384          # pairs whose records --dump-outputs writes (a fixed, seeded sample when the batch is larger)
+DUMP_LINES = 1 << 19        # SAM lines whose samblaster decisions it writes (likewise)
+DUMP_SEED = 20150810
+
+
+def dump_outputs(d, lib, summary, last, n_pairs, multi, rank=None):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as .npy files in d (float64 where an integer may
+    exceed 2^24, float32 otherwise; about 25 MB at 1 M pairs, never more than 64 MB):
+      summary        the step's 16 counts (include/ssgpu.h, ssg_hotpath_dev_ex)
+      pairs          the sampled pair indices (all pairs up to DUMP_PAIRS, else a fixed seeded sample)
+      records        one row per record of the sampled pairs' reads, in record order: read index, then the request fields (read, reg, kind,
+                     owner, flag, mapq) and the alignment fields (pos, rid, flag, mapq, NM, score, sub, n_cigar, is_rev, l_md, reg_idx, xa_cnt),
+                     then the CRC-32 of the MD string
+      cigar          the records' CIGAR words (len << 4 | op), zero past n_cigar
+      lines          the sampled SAM line indices (all lines up to DUMP_LINES, else a fixed seeded sample)
+      line_bits      samblaster's per-line SSG_SBL_* bits (duplicate / discordant / splitter) of those lines
+      mate_line      the line whose CIGAR / MAPQ fill their MC / MQ tags
+    N > 1 (per rank, file names end in _rank<r>): summary and the globally decided duplicate flag of every pair of the rank."""
+    import zlib
+    from speedseq_amd import capi
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank is None else "_rank%d" % rank
+    files = {"summary": np.asarray(summary, dtype=np.float64)}
+    if multi:
+        files["dup"] = last.cpu().numpy().astype(np.float32)
+    else:
+        try:
+            res, bits, mate = capi.dev_records_download(lib, last, n_pairs)
+        finally:
+            capi.dev_records_free(lib, last)
+        req_off, req, alns = res.req_off, res.req, res.alns
+        res.close()
+        rng = np.random.default_rng(DUMP_SEED)
+        pairs = np.arange(n_pairs) if n_pairs <= DUMP_PAIRS else np.sort(rng.choice(n_pairs, DUMP_PAIRS, replace=False))
+        reads = np.stack([2 * pairs, 2 * pairs + 1], 1).reshape(-1)
+        cnt = req_off[reads + 1] - req_off[reads]
+        start = np.repeat(req_off[reads] - np.concatenate([[0], np.cumsum(cnt)[:-1]]), cnt)
+        rec = start + np.arange(int(cnt.sum()))
+        q, al = req[rec], alns[rec]
+        md = [zlib.crc32(bytes(m[:max(0, int(l))])) for m, l in zip(al["md"], al["l_md"])]
+        cols = [np.repeat(reads, cnt)] + [q[f] for f in ("read", "reg", "kind", "owner", "flag", "mapq")] + \
+               [al[f] for f in ("pos", "rid", "flag", "mapq", "NM", "score", "sub", "n_cigar", "is_rev", "l_md", "reg_idx", "xa_cnt")] + [np.asarray(md, dtype=np.int64)]
+        cig = al["cigar"].astype(np.float32)
+        cig[np.arange(cig.shape[1])[None, :] >= al["n_cigar"][:, None]] = 0
+        nl = bits.shape[0]
+        lines = np.arange(nl) if nl <= DUMP_LINES else np.sort(rng.choice(nl, DUMP_LINES, replace=False))
+        files.update({"pairs": pairs.astype(np.float64), "records": np.stack(cols, 1).astype(np.float64), "cigar": cig,
+                      "lines": lines.astype(np.float64), "line_bits": bits[lines].astype(np.float32), "mate_line": mate[lines].astype(np.float64)})
+    total = sum(v.nbytes for v in files.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes is more than the 64 MB allowed" % total)
+    for k, v in files.items():
+        np.save(os.path.join(d, k + sfx + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -543,10 +602,19 @@ def main():
     ap.add_argument("--emu-selftest", action="store_true", help="TEST INFRASTRUCTURE, never a measurement: walk this script's whole flow on the CPU with the host-emulation build "
                     "(tests/emu) and the bundled chr20 slice as the reference, at toy sizes -- catches a broken leg before it costs GPU minutes")
     ap.add_argument("--partial", default=os.path.join(ROOT, "gpurun_out", "bench_partial.json"), help="the line so far is also written here after every leg (a run that is cut short leaves its numbers)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else this script measures or checks: per-kernel times and the roofline (a pass of "
+                    "their own), the parity gate against the CPU oracle and the CPU baselines, the 2x250 leg, the plugin-path and script legs, the N > 1 rehearsal. "
+                    "Without it a run sets up, warms up, times the steps and prints the line; the options above that configure those legs apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                    "summary counts, a fixed seeded sample of the pairs' records, samblaster's per-line decisions)")
     if "--emu-selftest" in sys.argv:                         # toy sizes unless given: the emulation runs the kernels lane by lane on the CPU
         ap.set_defaults(pairs=600, steps=1, warmup=0, bwa_threads=1, e2e_pairs=1200, script_pairs=1200, script_threads=2, cpu_script_pairs=200, config5_pairs=300, wide_pairs=300,
                         no_profile=True, partial="/tmp/bench_emu_partial.json")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:                                           # a plain run: the headline only
+        a.cpu_sample, a.e2e, a.config5_pairs, a.dist_rehearsal, a.no_profile = 0, False, 0, False, True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -630,9 +698,9 @@ def main():
     n_dup_global, merge_bytes = [0], [0]
     rec_bytes = capi.dev_record_bytes(lib)
 
-    def step(want_dup=False):
+    def step(want_dup=False, keep=False):
         if not multi:
-            return capi.hotpath_dev_ex(lib, idx, opt, a.pairs, rl, d_seq.data_ptr(), d_off.data_ptr(), d_pb.data_ptr(), n_batches, 0)
+            return capi.hotpath_dev_ex(lib, idx, opt, a.pairs, rl, d_seq.data_ptr(), d_off.data_ptr(), d_pb.data_ptr(), n_batches, 0, keep=keep)
         # N > 1: every rank aligns its shard; duplicates are decided over the whole input (first-seen-wins on the global pair
         # ordinal): signatures routed to an owner rank by hash with one all-to-all, verdicts routed back (speedseq_amd/dist.py);
         # the side-stream classification (discordant / splitter, --excludeDups) then runs on the records still resident in HBM
@@ -660,13 +728,10 @@ def main():
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
-    prof = not a.no_profile
-    if prof:
-        lib.l.ssg_prof_reset()
-        lib.l.ssg_prof_enable(C.c_int(1))
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        summary, _ = step()
+    for i in range(a.steps):
+        # --dump-outputs: the last step keeps its records in HBM (instead of freeing them on return) so that they can be written after the clock stops
+        summary, last = step(keep=bool(a.dump_outputs) and i == a.steps - 1)
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
@@ -675,10 +740,22 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
-    kern = capi.prof_get(lib) if prof else {}
     log('timed steps done: %.1f ms/step' % (1e3 * dt / a.steps))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, lib, summary, last, a.pairs, multi, rank if world > 1 else None)
+        log('outputs of the last timed step written to %s' % a.dump_outputs)
+    # --full: per-kernel device time (HIP events around every launch: the roofline below) from a pass of as many steps of its own
+    prof = a.full and not a.no_profile
+    if prof:
+        lib.l.ssg_prof_reset()
+        lib.l.ssg_prof_enable(C.c_int(1))
+        for _ in range(a.steps):
+            step()
+        torch.cuda.synchronize()
+    kern = capi.prof_get(lib) if prof else {}
     if prof:
         lib.l.ssg_prof_enable(C.c_int(0))
+        log('per-kernel pass done')
 
     workload = ("%d synthetic 2x%d bp PE pairs per GPU vs a seeded synthetic GRCh37-shaped reference of %.0f Mbp (25 contigs, order-6 Markov "
                 "model of the bundled chr20 slice + %d planted repeat families of 10..10^4 copies at 0-10%% divergence = 5%% of the bases; "
@@ -696,6 +773,8 @@ def main():
                    "sorted_merge": ("coordinate range exchange of %d-byte records by samtools' key inside the step; %.1f MB sent by rank 0 per step" % (rec_bytes, merge_bytes[0] / 1e6)) if multi else "single GPU: bin/sambamba sort (device radix sort of the keys)"},
     }
     def save_partial():
+        if not a.full:
+            return
         try:
             os.makedirs(os.path.dirname(a.partial), exist_ok=True)
             with open(a.partial, "w") as f:

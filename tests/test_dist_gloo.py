@@ -139,7 +139,7 @@ def test_bench_two_rank_flow_on_the_emulation(emu_lib, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29583",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--emu-selftest", "--cpu-sample", "0", "--partial", str(tmp_path / "p.json")],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--emu-selftest", "--cpu-sample", "0", "--partial", str(tmp_path / "p.json")],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]

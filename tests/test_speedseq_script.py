@@ -5,8 +5,8 @@ speedseq.config that names this repo's executables (the reference's plugin mecha
   * the product executables on the MI355X        (-m gpu),
 the product runs with this repo's native sambamba (SAM->BAM, device coordinate sort, BGZF, BAI), the oracle run with the reference's
 samtools behind sambamba's command line (tools/sambamba_samtools_shim.sh) as the comparator; bin/parallel throughout.  The three BAMs of the product runs must decode (samtools view) to the
-same records as the oracle run's.  The script comes from /root/reference when present, else from the fixture copy
-tests/golden/speedseq_ref_script.sh (tests/golden/make_golden.sh)."""
+same records as the oracle run's.  The script is the fixture copy tests/golden/speedseq_ref_script.sh (tests/golden/make_golden.sh);
+samtools and wgsim are the ones build() compiles into oracle/_ref/ (oracle/build_ref_tools.sh)."""
 import os
 import shutil
 import subprocess
@@ -16,7 +16,7 @@ import pytest
 import simreads
 from common import EXAMPLE_FA, ROOT
 
-REF_SCRIPT = "/root/reference/bin/speedseq" if os.path.exists("/root/reference/bin/speedseq") else os.path.join(ROOT, "tests", "golden", "speedseq_ref_script.sh")
+REF_SCRIPT = os.path.join(ROOT, "tests", "golden", "speedseq_ref_script.sh")
 SAMTOOLS = os.path.join(ROOT, "oracle", "_ref", "samtools")
 ORC = os.path.join(ROOT, "oracle", "orc_bwa")
 EMU = os.path.join(ROOT, "tests", "emu")
@@ -24,8 +24,6 @@ SHIM = os.path.join(ROOT, "tools", "sambamba_samtools_shim.sh")   # comparator: 
 
 
 def _need_tools():
-    if not os.path.exists(SAMTOOLS) and os.path.exists("/root/reference"):
-        subprocess.check_call(["sh", os.path.join(ROOT, "oracle", "build_ref_tools.sh")])
     if not os.path.exists(SAMTOOLS) or shutil.which("mawk") is None:
         pytest.skip("samtools (oracle/_ref) or mawk unavailable")
     if not os.path.exists(ORC):
@@ -147,8 +145,6 @@ def _wgsim_fastq(tmp_path, n_pairs, seed=11):
     """example/run_speedseq.sh:4-10 aligns data/NA12878.20slice.30X.fastq.gz, which the reference tree lists as a missing blob; SURVEY.md 8d prescribes its
     stand-in: 30x of the example FASTA from the reference's wgsim (src/samtools-1.3.1/misc/wgsim.c:438-463), interleaved and gzipped"""
     import gzip
-    if not os.path.exists(WGSIM) and os.path.exists("/root/reference"):
-        subprocess.check_call(["sh", os.path.join(ROOT, "oracle", "build_ref_tools.sh")])
     if not os.path.exists(WGSIM):
         pytest.skip("the reference's wgsim (oracle/_ref) is not built")
     r1, r2 = str(tmp_path / "w1.fq"), str(tmp_path / "w2.fq")

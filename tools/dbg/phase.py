@@ -4,7 +4,7 @@ import sys, os, ctypes as C
 import runpy, json, io, contextlib
 os.environ["SSG_DEBUG"] = "2"
 os.environ["SSGPU_LIB"] = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "speedseq_amd", "libssgpu_tune.so")  # make tune
-sys.argv = ["bench.py", "--steps", "2", "--warmup", "1", "--no-e2e", "--cpu-sample", "0"]   # the timed step only
+sys.argv = ["bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-e2e", "--cpu-sample", "0"]   # the timed step and its per-kernel pass
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     runpy.run_path("bench.py", run_name="__main__")

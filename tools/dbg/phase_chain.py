@@ -1,7 +1,7 @@
 # tuning aid: chain_wave phase counters (cycles of lane 0, summed over reads of the 2048 / 4096 classes) on the bench workload; needs `make tune`
 import sys, os, ctypes as C, runpy, json, io, contextlib
 os.environ["SSGPU_LIB"] = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "speedseq_amd", "libssgpu_tune.so")
-sys.argv = ["bench.py", "--steps", "1", "--warmup", "0", "--no-e2e", "--cpu-sample", "0"]
+sys.argv = ["bench.py", "--full", "--steps", "1", "--warmup", "0", "--no-e2e", "--cpu-sample", "0"]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     runpy.run_path("bench.py", run_name="__main__")

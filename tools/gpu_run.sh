@@ -3,7 +3,7 @@
 #   gpurun --timeout S -- 'bash tools/gpu_run.sh TAG STEP [STEP...]'
 # Every step writes gpurun_out/TAG_<what> and prints a few summary lines; a step that fails does not stop the later ones.
 #   suite[:K_EXPR]            pytest -m gpu (optionally -k K_EXPR)
-#   bench[:ARGS]              bench.py --steps 5 --warmup 2 ARGS  (ARGS with '+' for spaces, e.g. bench:--cpu-script-pairs+0)
+#   bench[:ARGS]              bench.py --full --steps 5 --warmup 2 ARGS  (ARGS with '+' for spaces, e.g. bench:--cpu-script-pairs+0)
 #   ab:KERNELS:CFG[;CFG...]   tools/smem_ab.py --kernels KERNELS CFG...   (A/B of variants inside the device step)
 #   ab250:KERNELS:CFG[;...]   the same at 2x250, 200 k pairs
 #   profile                   tools/profile_round.sh TAG (kernel stats + PMC passes + probes) and tools/pmc_summarize.py
@@ -24,7 +24,7 @@ for step in "$@"; do
     else timeout 1500 python -m pytest tests -m gpu -x -q > $out/${tag}_pytest_gpu.log 2>&1; fi
     tail -4 $out/${tag}_pytest_gpu.log | cut -c1-300 ;;
   bench)
-    timeout 1200 python bench.py --steps 5 --warmup 2 ${arg//+/ } > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -2 $out/${tag}_bench.err | cut -c1-300
+    timeout 1200 python bench.py --full --steps 5 --warmup 2 ${arg//+/ } > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -2 $out/${tag}_bench.err | cut -c1-300
     python - $out/${tag}_bench.json <<'PY'
 import json, sys
 try: d = json.load(open(sys.argv[1]))
