@@ -15,8 +15,8 @@
  *   - test_and_merge reads the chain's first/last seed summary from LDS;
  *   - chain weights: one lane per chain; the weight sort replays upstream's introsort (ties are the
  *     norm for repeats, and the unstable tie order selects what is kept) on packed keys in LDS;
- *   - the filter tests chain i against 64 kept chains at a time: ballot of the `break' condition,
- *     side effects applied only to the kept chains up to the first break, exactly as the scalar loop.
+ *   - the filter tests 64 chains of the sorted list at a time, a lane each, against the kept chains in
+ *     order, with the side effects of the scalar loop (wv_chain_read).
  * LDS footprint: 31.1 bytes per seed (27 per chain + 4.1 per seed, chains <= seeds); 256 / 1024 / 2048 / 5120 seeds run 20 / 5 / 2 / 1
  * reads per CU.
  */
@@ -25,10 +25,10 @@
 #include "k_chain.h"
 
 template <int CAPC, int CAPS = CAPC> struct ssg_chw_lds_t {   /* CAPC chains, CAPS seeds: the kernels use CAPS = CAPC, so a read that fits can always fall back to the shifting form */
-	int64_t a8[CAPC];   /* insertion: rbeg of the chain's last seed [chain id] | weights [chain id] | filter: kept w<<32 | kept sorted idx<<16 | first shadowed */
+	int64_t a8[CAPC];   /* insertion: rbeg of the chain's last seed [chain id] | weights [chain id] | filter: kept chain's query begin | end << 9 | w << 18 in the high half, first shadowed in the low 16 bits */
 	int64_t b8[CAPC];   /* insertion: chain position [chain id] (shifting form: positions, sorted [slot]) | sort/filter: w<<32 | chain id, sorted by w */
 	int16_t rid[CAPC];  /* insertion: contig of the chain [chain id] (< 32768 contigs: host-checked) | filter: kept state [sorted idx] */
-	uint16_t ls[CAPC];  /* last seed [chain id]                                | filter: query end of kept chain */
+	uint16_t ls[CAPC];  /* last seed [chain id] */
 	uint16_t n[CAPC], fs[CAPC];            /* [chain id]: #seeds (13 bits; bits 13 / 14 / 15 = bit 8 of fq / lq / ll), first seed */
 	SSG_DEVMEM int get_fq(int c) const { return fq[c] | (n[c] >> 13 & 1) << 8; }
 	SSG_DEVMEM int get_lq(int c) const { return lq[c] | (n[c] >> 14 & 1) << 8; }
@@ -37,7 +37,7 @@ template <int CAPC, int CAPS = CAPC> struct ssg_chw_lds_t {   /* CAPC chains, CA
 	SSG_DEVMEM void new_chain(int c, int qbeg, int len) { fq[c] = lq[c] = (uint8_t)qbeg; ll[c] = (uint8_t)len; n[c] = (uint16_t)(1 | (qbeg >> 8 & 1) << 13 | (qbeg >> 8 & 1) << 14 | (len >> 8 & 1) << 15); }
 	SSG_DEVMEM void add_seed(int c, int qbeg, int len) { lq[c] = (uint8_t)qbeg; ll[c] = (uint8_t)len; n[c] = (uint16_t)((((n[c] & 0x1fff) + 1) & 0x1fff) | (n[c] & 0x2000) | (qbeg >> 8 & 1) << 14 | (len >> 8 & 1) << 15); }
 	uint8_t fq[CAPC], lq[CAPC], ll[CAPC];  /* [chain id]: qbeg of first seed, qbeg/len of last seed: the low 8 bits (the ninth of each, for reads of 256..511 bases, rides in n[]) */
-	uint16_t ids[CAPS]; /* shifting form of the insertion: chain id of sorted slot (the ranked form needs none: a chain is named after the rank of its first seed) | filter: query begin of kept chain */
+	uint16_t ids[CAPS]; /* shifting form of the insertion: chain id of sorted slot (the ranked form needs none: a chain is named after the rank of its first seed) */
 	uint16_t nx[CAPS];  /* [seed]: next seed of the same chain */
 	uint64_t bm[CAPS / 64];                  /* ranks that hold a chain */
 	uint64_t bms[(CAPS / 64 + 63) / 64];     /* words of bm[] that are not empty */
@@ -155,7 +155,7 @@ SSG_DEVFN void wv_introsort_whi(ssg_chw_lds_t<CAPC, CAPS> &L, const int n)
 template <int CAPC, int CAPS>
 SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt, const long r, const int64_t *read_off, const ssg_intv_t *intv,
                              const int32_t *n_intv, int cap, const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *seed_rid,
-                             ssg_chain_t *chains, int32_t *order, int32_t *chain_seeds, int32_t *n_chain, ssg_chw_lds_t<CAPC, CAPS> &L, const uint16_t *rank, int capc_lim, int wave_sort, int32_t *kbflag)
+                             ssg_chain_t *chains, int32_t *order, int32_t *chain_seeds, int32_t *n_chain, ssg_chw_lds_t<CAPC, CAPS> &L, const uint16_t *rank, int capc_lim, int32_t *kbflag)
 {
 	const int lane = wv_lane();
 	const int len_read = (int)(read_off[r+1] - read_off[r]);
@@ -187,9 +187,7 @@ SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt
 		for (i = lane; i < (ns + 63) / 64; i += 64) L.bm[i] = 0;
 		for (i = lane; i < ((ns + 63) / 64 + 63) / 64; i += 64) L.bms[i] = 0;
 		ssg_wave_ldssync();
-	}
-	if (rank && (wave_sort & 2)) {
-		/* 64 seeds at a time, every lane its own: the one-seed-at-a-time loop below is one wave alone on its SIMD running ~200 dependent instructions
+		/* 64 seeds at a time, every lane its own: a loop one seed at a time is one wave alone on its SIMD running ~200 dependent instructions
 		 * per seed with 63 lanes idle (1 460 cycles per seed, profiles/r05n_chain_ab.json).  Here every lane looks up ITS seed's floor chain and decides
 		 * (contained / appended / new chain) against the state as it is when the round starts.  A lane's decision is what the sequential loop would
 		 * reach unless an EARLIER seed of the round changes what it read: a new chain whose rank falls between its floor and its own rank, or a seed
@@ -262,72 +260,6 @@ SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt
 				ssg_wave_ldssync();
 				nc += __popcll(cre);
 				done = p;
-			}
-		}
-	} else if (rank) {
-		for (int i0 = 0; i0 < ns && !fail; i0 += 64) {
-			const int me = i0 + lane;
-			int64_t my_rbeg = 0; int my_q = 0, my_len = 0, my_rid = -1, my_rk = 0;
-			if (me < ns) { const ssg_seed_t sdd = sd[me]; my_rbeg = sdd.rbeg; my_q = sdd.qbeg; my_len = sdd.len; my_rid = srid[me]; my_rk = rank[me]; }
-			const int cn = ns - i0 < 64 ? ns - i0 : 64;
-			int pf_t = -1, pf_w = 0; uint64_t pf_m = 0;
-			for (int t = 0; t < cn; ++t) {
-				const int prid = wv_get(my_rid, t);
-				if (prid < 0) continue;
-				const int sid = i0 + t, rk = wv_get(my_rk, t);
-				const int64_t rbeg = wv_get64(my_rbeg, t);
-				const int qbeg = wv_get(my_q, t), len = wv_get(my_len, t);
-				/* A chain's id is the rank of its first seed: the floor lookup lands on the chain's state directly.  Two dependent LDS round trips
-				 * per seed: the bitmap word of the seed's rank (also the word a new chain sets its bit in), then the floor chain's state in one batch --
-				 * and the first of the two is read one seed ahead (a bit this seed sets in that word is patched into the copy). */
-				const int bw = rk >> 6, bit = rk & 63;
-				const uint64_t mw = pf_t == t ? pf_m : L.bm[bw];
-				if (t + 1 < cn) { pf_w = wv_get(my_rk, t + 1) >> 6; pf_m = L.bm[pf_w]; pf_t = t + 1; }   /* the next seed's word travels with this seed's state reads */
-				const uint64_t mlow = mw & (bit == 63 ? ~0ull : (1ull << (bit + 1)) - 1);
-				int fl = mlow ? (bw << 6) + 63 - __clzll(mlow) : chw_prev_set(L, (bw << 6) - 1), two_equal = 0, res = 0, eqp2 = 0;
-				if (fl >= 0) { /* upstream test_and_merge against the floor chain */
-					int64_t f_rbeg = L.b8[fl], l_rbeg = L.a8[fl];
-					unsigned n16 = L.n[fl], ls = L.ls[fl]; int f_q = L.fq[fl], l_q = L.lq[fl], l_len = L.ll[fl], crid = L.rid[fl];
-					if (f_rbeg == rbeg) {   /* a chain at this very position: upstream tests the FIRST of them */
-						eqp2 = 1;
-						const int f2 = chw_prev_set(L, fl - 1);
-						if (f2 >= 0 && L.b8[f2] == rbeg) {
-							fl = f2; two_equal = 1;
-							f_rbeg = L.b8[fl]; l_rbeg = L.a8[fl]; n16 = L.n[fl]; ls = L.ls[fl]; f_q = L.fq[fl]; l_q = L.lq[fl]; l_len = L.ll[fl]; crid = L.rid[fl];
-						}
-					}
-					f_q |= (int)(n16 >> 13 & 1) << 8; l_q |= (int)(n16 >> 14 & 1) << 8; l_len |= (int)(n16 >> 15 & 1) << 8;
-					if (prid != crid) res = 0;
-					else if (qbeg >= f_q && qbeg + len <= l_q + l_len && rbeg >= f_rbeg && rbeg + len <= l_rbeg + l_len) res = 1;
-					else if ((l_rbeg < l_pac || f_rbeg < l_pac) && rbeg >= l_pac) res = 0;
-					else {
-						const int64_t x = qbeg - l_q, y = rbeg - l_rbeg;
-						if (y >= 0 && x - y <= opt.w && y - x <= opt.w && x - l_len < opt.max_chain_gap && y - l_len < opt.max_chain_gap) res = 2;
-					}
-					if (res == 2) {
-						ssg_wave_ldssync();
-						if (lane == 0) {
-							L.nx[ls] = (uint16_t)sid; L.ls[fl] = (uint16_t)sid; L.a8[fl] = rbeg; L.lq[fl] = (uint8_t)qbeg; L.ll[fl] = (uint8_t)len;
-							L.n[fl] = (uint16_t)((((n16 & 0x1fff) + 1) & 0x1fff) | (n16 & 0x2000) | (unsigned)(qbeg >> 8 & 1) << 14 | (unsigned)(len >> 8 & 1) << 15);
-						}
-						ssg_wave_ldssync();
-					}
-				}
-				/* not covered here: the caller redoes the read.  (Decided on a scalar, outside the lane-conditional regions, so that the exit out of
-				 * both loops is a plain scalar branch.) */
-				if (wv_get((res == 0 && (two_equal || nc >= capc_lim)) ? 1 : 0, 0)) { fail = 1; break; }
-				if (res == 0) { /* new chain; its place in position order is its seed's rank */
-					ssg_wave_ldssync();
-					if (lane == 0) {
-						L.bm[bw] = mw | 1ull << bit;
-						if (!mw) L.bms[bw >> 6] |= 1ull << (bw & 63);
-						L.b8[rk] = rbeg; L.a8[rk] = rbeg; L.new_chain(rk, qbeg, len);
-						L.fs[rk] = L.ls[rk] = (uint16_t)sid; L.rid[rk] = (int16_t)prid;
-					}
-					ssg_wave_ldssync();
-					if (pf_t == t + 1 && pf_w == bw) pf_m |= 1ull << bit;
-					++nc; n_dup += wv_get(eqp2, 0);
-				}
 			}
 		}
 	} else
@@ -443,102 +375,81 @@ SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt
 	if (n_chn > 0) {
 		/* ---- upstream mem_chain_flt ---- */
 		const unsigned long long ph_t3 = ssg_clock();
-		if ((wave_sort & 1) && n_chn > 24) wv_introsort_whi(L, n_chn); else if (lane == 0) ssg_introsort(L.b8, (long)n_chn, ssg_whi_gt());
+		if (n_chn > 24) wv_introsort_whi(L, n_chn); else if (lane == 0) ssg_introsort(L.b8, (long)n_chn, ssg_whi_gt());
 		ssg_wave_ldssync();
 		const unsigned long long ph_t4 = ssg_clock();
 		for (i = lane; i < n_chn; i += 64) L.rid[i] = 0;
 		int nk = 0;
-		if (wave_sort & 4) {
-			/* 64 chains of the sorted list at a time, a lane each, against the kept chains in order.  (One chain at a time against 64 kept chains, below, spends most
-			 * of its ~2 200 cycles per chain on the round trips around the few tests it makes.)  A kept chain is one word: query begin | end << 9 | w << 18 in the
-			 * high half of a8[k], the first chain it shadows in the low 16 bits.  The sequential loop's order is kept: a lane stops caring at its first `break'
-			 * (the tests before it have their side effect, the ones after it none); `first' of a kept chain goes to the smallest i that reaches it with an overlap;
-			 * within the block the lanes become kept chains in order, each tested by the later lanes still running. */
-			/* The heaviest chains first, all at once: w descends, so a chain that cannot `break' against chain 0 by the weights alone (w < w0 x drop_ratio and w0 - w >=
-			 * 2 min_seed_len are both monotone in w) breaks against no chain: these form a prefix [0, m) of the list and are all kept.  What the sequential loop leaves
-			 * behind for them: `first' of kept chain e = the first later chain that overlaps it, and large_ovlp of chain e = some earlier chain overlaps it -- two scans
-			 * per lane that stop at their first hit (in a repeat family everything overlaps everything: the quadratic loop becomes linear). */
-			int m = n_chn;
-			{
-				const int w0 = (int)(L.b8[0] >> 32);
-				for (int i0 = 0; i0 < n_chn; i0 += 64) {
-					const int ci = i0 + lane;
-					const int wc = ci < n_chn ? (int)(L.b8[ci] >> 32) : 0;
-					const unsigned long long um = wv_ballot(ci < n_chn && ((wc < w0 * opt.drop_ratio) & (w0 - wc >= opt.min_seed_len << 1)));
-					if (um) { m = i0 + (int)__builtin_ctzll(um); break; }
-				}
+		/* 64 chains of the sorted list at a time, a lane each, against the kept chains in order.  (One chain at a time against 64 kept chains spent most
+		 * of its ~2 200 cycles per chain on the round trips around the few tests it makes.)  A kept chain is one word: query begin | end << 9 | w << 18 in the
+		 * high half of a8[k], the first chain it shadows in the low 16 bits.  The sequential loop's order is kept: a lane stops caring at its first `break'
+		 * (the tests before it have their side effect, the ones after it none); `first' of a kept chain goes to the smallest i that reaches it with an overlap;
+		 * within the block the lanes become kept chains in order, each tested by the later lanes still running. */
+		/* The heaviest chains first, all at once: w descends, so a chain that cannot `break' against chain 0 by the weights alone (w < w0 x drop_ratio and w0 - w >=
+		 * 2 min_seed_len are both monotone in w) breaks against no chain: these form a prefix [0, m) of the list and are all kept.  What the sequential loop leaves
+		 * behind for them: `first' of kept chain e = the first later chain that overlaps it, and large_ovlp of chain e = some earlier chain overlaps it -- two scans
+		 * per lane that stop at their first hit (in a repeat family everything overlaps everything: the quadratic loop becomes linear). */
+		int m = n_chn;
+		{
+			const int w0 = (int)(L.b8[0] >> 32);
+			for (int i0 = 0; i0 < n_chn; i0 += 64) {
+				const int ci = i0 + lane;
+				const int wc = ci < n_chn ? (int)(L.b8[ci] >> 32) : 0;
+				const unsigned long long um = wv_ballot(ci < n_chn && ((wc < w0 * opt.drop_ratio) & (w0 - wc >= opt.min_seed_len << 1)));
+				if (um) { m = i0 + (int)__builtin_ctzll(um); break; }
 			}
-			ssg_wave_ldssync();
-			for (int e = lane; e < m; e += 64) {
-				const int64_t me = L.b8[e];
-				const int id = (int)(uint32_t)me, wi = (int)(me >> 32);
-				L.a8[e] = (int64_t)(((uint64_t)(uint32_t)(L.get_fq(id) | (L.get_lq(id) + L.get_ll(id)) << 9 | wi << 18)) << 32 | 0xffffu);
-			}
-			ssg_wave_ldssync();
-			for (int e0 = 0; e0 < m; e0 += 64) {
-				const int e = e0 + lane; const bool act = e < m;
-				const int hwe = act ? (int)(L.a8[e] >> 32) : 0;
-				const int ib = hwe & 511, ie = hwe >> 9 & 511;
-				int f = 0xffff, lo = 0;
-				for (int dir = 0; dir < 2; ++dir) {   /* forward: the first later chain of the prefix that overlaps; backward: any earlier one */
-					int q = dir ? e - 1 : e + 1;
-					bool run = act && (dir ? q >= 0 : q < m);
-					while (wv_ballot(run)) {
-						if (run) {
-							const int hw = (int)(L.a8[q] >> 32);
-							const int jb = hw & 511, je = hw >> 9 & 511;
-							const int b_max = jb > ib ? jb : ib, e_min = je < ie ? je : ie;
-							bool ov = false;
-							if (e_min > b_max) { const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj; ov = e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap; }
-							if (ov) { if (dir) lo = 1; else f = q; run = false; }
-							else { q += dir ? -1 : 1; run = dir ? q >= 0 : q < m; }
-						}
-					}
-				}
-				ssg_wave_ldssync();
-				if (act) { L.a8[e] = (int64_t)(((uint64_t)(uint32_t)hwe) << 32 | (uint32_t)f); L.rid[e] = lo ? 2 : 3; }
-			}
-			nk = m;
-			ssg_wave_ldssync();
-			for (int i0 = m; i0 < n_chn; i0 += 64) {
-				const int ci = i0 + lane; const bool act = ci < n_chn;
-				const int64_t me = act ? L.b8[ci] : 0;
-				const int id = (int)(uint32_t)me, wi = (int)(me >> 32);
-				const int ib = act ? L.get_fq(id) : 0, ie = act ? L.get_lq(id) + L.get_ll(id) : 0;
-				int lo = 0, broke = !act, myfirst = 0xffff;
-				const int nk0 = nk;
-				for (int k0 = 0; k0 < nk0; k0 += 64) {
-					if (!wv_ballot(!broke)) break;
-					const int kk = k0 + lane;
-					const int64_t kw = kk < nk0 ? L.a8[kk] : 0;
-					const int kwh = (int)(kw >> 32), kwl = (int)(uint32_t)kw;
-					const int cnt = nk0 - k0 < 64 ? nk0 - k0 : 64;
-					for (int j = 0; j < cnt; ++j) {
-						const int hw = wv_get(kwh, j);
-						const int jb = hw & 511, je = hw >> 9 & 511, wj = (int)((unsigned)hw >> 18);
-						int ov = 0, brk = 0;
+		}
+		ssg_wave_ldssync();
+		for (int e = lane; e < m; e += 64) {
+			const int64_t me = L.b8[e];
+			const int id = (int)(uint32_t)me, wi = (int)(me >> 32);
+			L.a8[e] = (int64_t)(((uint64_t)(uint32_t)(L.get_fq(id) | (L.get_lq(id) + L.get_ll(id)) << 9 | wi << 18)) << 32 | 0xffffu);
+		}
+		ssg_wave_ldssync();
+		for (int e0 = 0; e0 < m; e0 += 64) {
+			const int e = e0 + lane; const bool act = e < m;
+			const int hwe = act ? (int)(L.a8[e] >> 32) : 0;
+			const int ib = hwe & 511, ie = hwe >> 9 & 511;
+			int f = 0xffff, lo = 0;
+			for (int dir = 0; dir < 2; ++dir) {   /* forward: the first later chain of the prefix that overlaps; backward: any earlier one */
+				int q = dir ? e - 1 : e + 1;
+				bool run = act && (dir ? q >= 0 : q < m);
+				while (wv_ballot(run)) {
+					if (run) {
+						const int hw = (int)(L.a8[q] >> 32);
+						const int jb = hw & 511, je = hw >> 9 & 511;
 						const int b_max = jb > ib ? jb : ib, e_min = je < ie ? je : ie;
-						if (!broke && e_min > b_max) {
-							const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj;
-							if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
-								ov = 1;
-								brk = (wi < wj * opt.drop_ratio) & (wj - wi >= opt.min_seed_len << 1);
-							}
-						}
-						const unsigned long long ovm = wv_ballot(ov);
-						if (ovm) {
-							lo |= ov; broke |= brk;
-							if ((wv_get(kwl, j) & 0xffff) == 0xffff && lane == 0) L.a8[k0 + j] = (int64_t)(((uint64_t)(uint32_t)hw << 32) | (uint32_t)(i0 + (int)__builtin_ctzll(ovm)));
-						}
+						bool ov = false;
+						if (e_min > b_max) { const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj; ov = e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap; }
+						if (ov) { if (dir) lo = 1; else f = q; run = false; }
+						else { q += dir ? -1 : 1; run = dir ? q >= 0 : q < m; }
 					}
 				}
-				const int cnt_b = n_chn - i0 < 64 ? n_chn - i0 : 64;
-				for (int t = 0; t < cnt_b; ++t) {
-					if (wv_get(broke, t)) continue;
-					const int jb = wv_get(ib, t), je = wv_get(ie, t), wj = wv_get(wi, t);
+			}
+			ssg_wave_ldssync();
+			if (act) { L.a8[e] = (int64_t)(((uint64_t)(uint32_t)hwe) << 32 | (uint32_t)f); L.rid[e] = lo ? 2 : 3; }
+		}
+		nk = m;
+		ssg_wave_ldssync();
+		for (int i0 = m; i0 < n_chn; i0 += 64) {
+			const int ci = i0 + lane; const bool act = ci < n_chn;
+			const int64_t me = act ? L.b8[ci] : 0;
+			const int id = (int)(uint32_t)me, wi = (int)(me >> 32);
+			const int ib = act ? L.get_fq(id) : 0, ie = act ? L.get_lq(id) + L.get_ll(id) : 0;
+			int lo = 0, broke = !act, myfirst = 0xffff;
+			const int nk0 = nk;
+			for (int k0 = 0; k0 < nk0; k0 += 64) {
+				if (!wv_ballot(!broke)) break;
+				const int kk = k0 + lane;
+				const int64_t kw = kk < nk0 ? L.a8[kk] : 0;
+				const int kwh = (int)(kw >> 32), kwl = (int)(uint32_t)kw;
+				const int cnt = nk0 - k0 < 64 ? nk0 - k0 : 64;
+				for (int j = 0; j < cnt; ++j) {
+					const int hw = wv_get(kwh, j);
+					const int jb = hw & 511, je = hw >> 9 & 511, wj = (int)((unsigned)hw >> 18);
 					int ov = 0, brk = 0;
 					const int b_max = jb > ib ? jb : ib, e_min = je < ie ? je : ie;
-					if (!broke && lane > t && e_min > b_max) {
+					if (!broke && e_min > b_max) {
 						const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj;
 						if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
 							ov = 1;
@@ -546,49 +457,35 @@ SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt
 						}
 					}
 					const unsigned long long ovm = wv_ballot(ov);
-					if (ovm) { lo |= ov; broke |= brk; if (lane == t) myfirst = i0 + (int)__builtin_ctzll(ovm); }
-				}
-				const unsigned long long keptm = wv_ballot(!broke);
-				ssg_wave_ldssync();
-				if (!broke) {
-					L.a8[nk + wv_rank_of(keptm)] = (int64_t)(((uint64_t)(uint32_t)(ib | ie << 9 | wi << 18)) << 32 | (uint32_t)myfirst);
-					L.rid[ci] = lo ? 2 : 3;
-				}
-				nk += __popcll(keptm);
-				ssg_wave_ldssync();
-			}
-		} else
-		for (i = 0; i < n_chn; ++i) {
-			const int64_t me = L.b8[i];
-			const int id = (int)(uint32_t)me, wi = (int)(me >> 32);
-			const int ib = L.get_fq(id), ie = L.get_lq(id) + L.get_ll(id);
-			int large_ovlp = 0, broke = 0;
-			for (int k0 = 0; k0 < nk && !broke; k0 += 64) {
-				const int kk = k0 + lane;
-				int ov = 0, brk = 0;
-				if (kk < nk) {
-					const int jb = L.ids[kk], je = L.ls[kk], wj = (int)(L.a8[kk] >> 32);
-					const int b_max = jb > ib ? jb : ib, e_min = je < ie ? je : ie;
-					if (e_min > b_max) {
-						const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj;
-						if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
-							ov = 1;
-							brk = (wi < wj * opt.drop_ratio) & (wj - wi >= opt.min_seed_len << 1);
-						}
+					if (ovm) {
+						lo |= ov; broke |= brk;
+						if ((wv_get(kwl, j) & 0xffff) == 0xffff && lane == 0) L.a8[k0 + j] = (int64_t)(((uint64_t)(uint32_t)hw << 32) | (uint32_t)(i0 + (int)__builtin_ctzll(ovm)));
 					}
 				}
-				const unsigned long long bb = wv_ballot(brk);
-				const int fb = bb ? __builtin_ctzll(bb) : 64;   /* the scalar loop stops at the first break */
-				const int act = ov && lane <= fb;
-				if (act && (L.a8[kk] & 0xffff) == 0xffff) L.a8[kk] = (L.a8[kk] & ~(int64_t)0xffff) | i;
-				large_ovlp |= wv_ballot(act) != 0;
-				broke = bb != 0;
 			}
+			const int cnt_b = n_chn - i0 < 64 ? n_chn - i0 : 64;
+			for (int t = 0; t < cnt_b; ++t) {
+				if (wv_get(broke, t)) continue;
+				const int jb = wv_get(ib, t), je = wv_get(ie, t), wj = wv_get(wi, t);
+				int ov = 0, brk = 0;
+				const int b_max = jb > ib ? jb : ib, e_min = je < ie ? je : ie;
+				if (!broke && lane > t && e_min > b_max) {
+					const int li = ie - ib, lj = je - jb, min_l = li < lj ? li : lj;
+					if (e_min - b_max >= min_l * opt.mask_level && min_l < opt.max_chain_gap) {
+						ov = 1;
+						brk = (wi < wj * opt.drop_ratio) & (wj - wi >= opt.min_seed_len << 1);
+					}
+				}
+				const unsigned long long ovm = wv_ballot(ov);
+				if (ovm) { lo |= ov; broke |= brk; if (lane == t) myfirst = i0 + (int)__builtin_ctzll(ovm); }
+			}
+			const unsigned long long keptm = wv_ballot(!broke);
+			ssg_wave_ldssync();
 			if (!broke) {
-				ssg_wave_ldssync();
-				if (lane == 0) { L.a8[nk] = (int64_t)wi << 32 | (int64_t)i << 16 | 0xffff; L.ids[nk] = (uint16_t)ib; L.ls[nk] = (uint16_t)ie; L.rid[i] = large_ovlp ? 2 : 3; }
-				++nk;
+				L.a8[nk + wv_rank_of(keptm)] = (int64_t)(((uint64_t)(uint32_t)(ib | ie << 9 | wi << 18)) << 32 | (uint32_t)myfirst);
+				L.rid[ci] = lo ? 2 : 3;
 			}
+			nk += __popcll(keptm);
 			ssg_wave_ldssync();
 		}
 		for (k = lane; k < nk; k += 64) { const int f = (int)(L.a8[k] & 0xffff); if (f != 0xffff) L.rid[f] = 1; }
@@ -644,16 +541,16 @@ __global__ void __launch_bounds__(64) ssg_k_chain_wave(ssg_index_view_t ix, ssg_
                             const int64_t *read_off, const ssg_intv_t *intv, const int32_t *n_intv, int cap,
                             const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *seed_rid,
                             ssg_chain_t *chains, int32_t *order, int32_t *chain_seeds, int32_t *n_chain,
-                            const int32_t *work_order, unsigned int *queue, int32_t *kbflag, const uint16_t *hrank, const int64_t *hoff, int capc_lim /* CAP; smaller only in tests */, int wave_sort /* bit 0: the weight sort by the whole wave, bit 1: the insertion 64 seeds a round, bit 2: the filter 64 chains a round (0: one lane / one seed / one chain, A/B and tests) */)
+                            const int32_t *work_order, unsigned int *queue, int32_t *kbflag, const uint16_t *hrank, const int64_t *hoff, int capc_lim /* CAP; smaller only in tests */)
 {
 	__shared__ ssg_chw_lds_t<CAP, CAP> L;
 	for (;;) {
 		const long k = r_first + wv_queue_pop(queue);
 		if (k >= r_end) break;
 		const long r = work_order ? work_order[k] : k;
-		int rc = wv_chain_read<CAP, CAP>(ix, opt, r, read_off, intv, n_intv, cap, seed_off, seeds, seed_rid, chains, order, chain_seeds, n_chain, L, hrank ? hrank + hoff[k] : (const uint16_t*)0, capc_lim, wave_sort, kbflag);
+		int rc = wv_chain_read<CAP, CAP>(ix, opt, r, read_off, intv, n_intv, cap, seed_off, seeds, seed_rid, chains, order, chain_seeds, n_chain, L, hrank ? hrank + hoff[k] : (const uint16_t*)0, capc_lim, kbflag);
 		rc = wv_get(rc, 0);
-		if (rc) rc = wv_chain_read<CAP, CAP>(ix, opt, r, read_off, intv, n_intv, cap, seed_off, seeds, seed_rid, chains, order, chain_seeds, n_chain, L, (const uint16_t*)0, CAP, wave_sort, kbflag);
+		if (rc) rc = wv_chain_read<CAP, CAP>(ix, opt, r, read_off, intv, n_intv, cap, seed_off, seeds, seed_rid, chains, order, chain_seeds, n_chain, L, (const uint16_t*)0, CAP, kbflag);
 	}
 }
 

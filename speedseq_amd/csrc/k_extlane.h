@@ -9,7 +9,7 @@
  * for repeat-heavy reads (hundreds of chains, one extended seed each) these extensions are ~all of the
  * Smith-Waterman work.  So:
  *   ssg_k_ext_prep   one lane per chain: reference window (rmax) and best seed -> job record
- *   ssg_k_ext_lane   one lane per job and side (left, then right with the left score as h0): a scalar
+ *   ssg_k_ext_lane_dyn  one lane per job and side (left, then right with the left score as h0): a scalar
  *                    restatement of ksw_extend2 per lane, 64 independent extensions per wavefront.  The
  *                    DP row {H,E} and the query live in LDS, one 32-bit word per column and lane
  *                    (h:16 | e:13 | query code:3; word (j*64 + lane) -> bank = lane, conflict free for
@@ -93,9 +93,8 @@ SSG_DEVFN int ssg_xl_pred_rows(const ssg_index_view_t &ix, const ssg_mem_opt_t &
 /* one lane per surviving chain g (global numbering: chain_off[r] + position in the read's order[]) */
 __global__ void __launch_bounds__(256) ssg_k_ext_prep(ssg_index_view_t ix, ssg_mem_opt_t opt, int n_reads, long n_jobs, const int64_t *read_off,
                                const int64_t *seed_off, const ssg_seed_t *seeds, const ssg_chain_t *chains, const int32_t *order,
-                               const int32_t *chain_seeds, const int64_t *chain_off, int twin_cap,
-                               ssg_xjob_t *jobs, uint64_t *key_l, uint64_t *key_r, int short_cap, unsigned int *n_long /* [2]: sides longer than short_cap */,
-                               const uint8_t *seq, int rows_key /* 0: order by side length alone */)
+                               const int32_t *chain_seeds, const int64_t *chain_off, const uint8_t *seq, int twin_cap,
+                               ssg_xjob_t *jobs, uint64_t *key_l, uint64_t *key_r)
 {
 	const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (g >= n_jobs) return;
@@ -139,7 +138,7 @@ __global__ void __launch_bounds__(256) ssg_k_ext_prep(ssg_index_view_t ix, ssg_m
 	jobs[g] = jb;
 	const int ql = jb.flag ? 0 : s.qbeg, qr = jb.flag ? 0 : l_query - s.qbeg - s.len;
 	int pl = 0, pr = 0;
-	if (rows_key && !jb.flag) {
+	if (!jb.flag) {
 		const uint8_t *query = seq + read_off[r];
 		pl = ssg_xl_pred_rows(ix, opt, query + s.qbeg - 1, -1, ql, (int)(s.rbeg - rmax0), s.rbeg - 1, -1, s.len * opt.a);
 		pr = ssg_xl_pred_rows(ix, opt, query + s.qbeg + s.len, 1, qr, (int)(rmax1 - (s.rbeg + s.len)), s.rbeg + s.len, 1, s.len * opt.a);
@@ -148,10 +147,6 @@ __global__ void __launch_bounds__(256) ssg_k_ext_prep(ssg_index_view_t ix, ssg_m
 	/* ascending sort = longest query side first (511 = nothing to do on this side), and among sides of one length the one expected to run most rows first */
 	key_l[g] = (uint64_t)(511 - ql) << 41 | (uint64_t)(511 - pl) << 32 | (uint64_t)g;
 	key_r[g] = (uint64_t)(511 - qr) << 41 | (uint64_t)(511 - pr) << 32 | (uint64_t)g;
-	{	/* one atomic per wave and side */
-		const unsigned long long bl = wv_ballot(ql > short_cap), br = wv_ballot(qr > short_cap), act = wv_ballot(1);
-		if (wv_lane() == (int)__builtin_ctzll(act)) { if (bl) atomicAdd(&n_long[0], (unsigned)__popcll(bl)); if (br) atomicAdd(&n_long[1], (unsigned)__popcll(br)); }
-	}
 }
 
 /* LDS word of a column: h:13 | e:13 | 6 x query code:6 (DP values stay below 8191: checked on the host).  The query field is the
@@ -276,7 +271,7 @@ SSG_DEVFN ssg_ext_res_t ln_extend2(const ssg_mem_opt_t &opt, const ssg_index_vie
 #define SSG_XL_BAND_TRY 2   /* == SSG_MAX_BAND_TRY (upstream MAX_BAND_TRY) */
 
 /* side 0: left extensions (query and reference walked backwards from the seed); side 1: right extensions.
- * sorted[t] = (511 - side length) << 41 | (511 - expected rows) << 32 | job id; QCAP+1 columns of LDS per lane. */
+ * sorted[t] = (511 - side length) << 41 | (511 - expected rows) << 32 | job id; qcap+1 columns of LDS per lane. */
 /* one job of one side; L: the workgroup's (qcap + 2 U) x 64 words of LDS */
 template <int U>
 SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt, const int side, const long job_first, const long n_jobs, const uint64_t *sorted,
@@ -351,19 +346,9 @@ SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t 
 #endif
 }
 
-template <int QCAP>
-__global__ void __launch_bounds__(64) ssg_k_ext_lane(ssg_index_view_t ix, ssg_mem_opt_t opt, int side, long job_first, long n_jobs, const uint64_t *sorted,
-                               const ssg_xjob_t *jobs, const uint8_t *seq, const int64_t *read_off, ssg_xres_t *res_l, ssg_xres_t *res_r,
-                               unsigned long long *cells)
-{
-	constexpr int U = QCAP > 72 ? 4 : 2;
-	__shared__ uint32_t L[(QCAP + 2 * U) * 64];   /* columns 0..qlen, and the 2U - 1 the cell loop may read ahead */
-	ssg_ext_lane_job<U>(ix, opt, side, job_first, n_jobs, sorted, jobs, seq, read_off, res_l, res_r, cells, L, QCAP);
-}
-
-/* The same with as much LDS as the launch asks for ((qcap + 2 U) x 256 bytes): the host cuts the sorted job list into classes of 8 more columns each, so that a wave
- * holds what its longest side needs -- 73..80 columns: 22 KB, seven waves a CU; 129..136: 37 KB, four (what the fixed class above gives every side beyond 72); a side
- * of 100 of a 250-base read: 28 KB instead of the 68 KB of the 256-column class (two waves a CU). */
+/* The kernel, with as much LDS as the launch asks for ((qcap + 2 U) x 256 bytes: columns 0..qlen, and the 2U - 1 the cell loop may read ahead): the host cuts the
+ * sorted job list into classes of 8 more columns each, so that a wave holds what its longest side needs -- 73..80 columns: 22 KB, seven waves a CU; 129..136: 37 KB,
+ * four; a side of 100 of a 250-base read: 28 KB instead of the 68 KB of a fixed 256-column class (two waves a CU). */
 template <int U>
 __global__ void __launch_bounds__(64) ssg_k_ext_lane_dyn(ssg_index_view_t ix, ssg_mem_opt_t opt, int side, long job_first, long n_jobs, const uint64_t *sorted,
                                const ssg_xjob_t *jobs, const uint8_t *seq, const int64_t *read_off, ssg_xres_t *res_l, ssg_xres_t *res_r,

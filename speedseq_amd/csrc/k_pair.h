@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256, SSG_SW_WAVES_PER_SIMD) ssg_k_matesw(ssg_i
                              ssg_alnreg_t *bcopy, uint8_t *tglb, unsigned long long *bglb, int32_t *err, unsigned long long *cells, unsigned long long *n_rescue,
                              const int32_t *work_order, unsigned int *queue, ssg_sdp_big_t *sdpbig, const unsigned int *n_todo /* work_order[] holds this many pairs */,
                              const ssg_msres_t *jres, const int64_t *jbase /* forward passes of the windows of pair kq's sides: slots jbase[2 kq + i] + 4 j + r (k_mswlane.h); or null */,
-                             const uint8_t *sdp_fixed /* per read: the list is a fixed point of mem_sort_dedup_patch's scan already (k_extend.h); or null */)
+                             const uint8_t *sdp_fixed /* per read: the list is a fixed point of mem_sort_dedup_patch's scan already (k_extend.h) */)
 {
 	__shared__ uint8_t revlds[SSG_WAVES_PER_WG][320];
 	__shared__ ssg_sdp_lds_t sdplds[SSG_WAVES_PER_WG];
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256, SSG_SW_WAVES_PER_SIMD) ssg_k_matesw(ssg_i
 			if (nb[i] > 64) { nb[i] = 64; myerr = 3; }
 		}
 		if (nb[0] + nb[1] > 0) {
-			int fixed[2] = { sdp_fixed ? (int)sdp_fixed[2*p] : 0, sdp_fixed ? (int)sdp_fixed[2*p + 1] : 0 };   /* a[i] is the output of a plain re-sort (stage 1's, or this kernel's): the next one is incremental */
+			int fixed[2] = { (int)sdp_fixed[2*p], (int)sdp_fixed[2*p + 1] };   /* a[i] is the output of a plain re-sort (stage 1's, or this kernel's): the next one is incremental */
 			ssg_wave_memsync();
 			for (int i2 = 0; i2 < 2; ++i2) { /* the first nb[i2] qualifying hits, in list order: 64 per step */
 				const int thr = an[i2] ? a[i2][0].score - opt.pen_unpaired : 0;

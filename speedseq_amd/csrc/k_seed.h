@@ -5,7 +5,7 @@
  *   ssg_k_smem_lane one lane per read, nested loops as upstream writes them: the reference form on the device (SSG_SMEM_KERNEL=lane) and
  *                   the fall-back for reads whose lists outgrow the product kernels' capacities: the three SMEM passes of upstream
  *                   mem_collect_intv (bwt_smem1a x2 + bwt_seed_strategy1), intervals sorted by (start,end).
- *   ssg_k_smem_sort upstream's ks_introsort(mem_intv) per read, for the kernels that append in discovery order.
+ *   ssg_k_smem_sort_rank / _wave  upstream's ks_introsort(mem_intv) per read, for the kernels that append in discovery order.
  *   ssg_k_sal_count per interval: number of sampled occurrences (<= max_occ) -> prefix sum.
  *   ssg_k_sal       one lane per (interval, occurrence): upstream bwt_sa LF-walk + sampled-SA
  *                   gather, then bns_intv2rid; writes mem_seed_t in upstream visiting order.
@@ -168,18 +168,9 @@ __global__ void __launch_bounds__(64) ssg_k_smem_lane(ssg_index_view_t ix, ssg_m
 	if (n_extend && my_nx) atomicAdd(n_extend, my_nx);
 }
 
-/* one lane per read: intervals by (start,end), upstream's ks_introsort(mem_intv) */
-__global__ void __launch_bounds__(64) ssg_k_smem_sort(int n_reads, ssg_intv_t *intv, const int32_t *n_intv, int cap)
-{
-	const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (r >= n_reads) return;
-	const int n = n_intv[r];
-	if (n > 1 && n <= cap) ssg_introsort(intv + r * cap, (long)n, ssg_intv_lt());
-}
-
-/* The same for the lists of up to LC intervals (nearly all) without introsort's per-lane control flow: the lanes of a wave sort lists of different lengths and
- * contents, so the wave walks the union of 64 different introsort paths, every compare a dependent load on the lane's own lines (3.7 ms per million pairs at
- * 1 % of the VALU rate, profiles/r06_pmc_sq.json).  Here a lane copies its records into LDS (four at a time, independent loads), holds the keys in registers,
+/* Upstream's ks_introsort(mem_intv) of a read's intervals by (start,end), for the lists of up to LC intervals (nearly all), without introsort's per-lane control
+ * flow (as a lane per read, the lanes of a wave sort lists of different lengths and contents, so the wave walks the union of 64 different introsort paths, every compare a dependent load on the lane's own lines (3.7 ms per million pairs at
+ * 1 % of the VALU rate, profiles/r06_pmc_sq.json)).  Here a lane copies its records into LDS (four at a time, independent loads), holds the keys in registers,
  * ranks every key against the others in fully unrolled, predicated loops (no memory in the rank phase: a first form that read the keys from LDS in an n x n loop
  * took 4.5 ms, r06U), and writes record i to place rank(i).  LDS word (8 bytes) w of lane l at [w * 64 + l]: bank = lane whatever w.
  * The key is (start, end) = `info`; two intervals of a read with equal keys are intervals of the same pattern, hence the same 32 bytes (the order in which a
@@ -254,13 +245,13 @@ SSG_DEVFN int ssg_intv_nocc(const ssg_mem_opt_t &opt, uint64_t x2)
 }
 
 /* per read: total #occurrences over its intervals (for the prefix sum that places seeds) */
-__global__ void ssg_k_sal_count(ssg_mem_opt_t opt, int n_reads, const ssg_intv_t *intv, const int32_t *n_intv, int cap, int32_t *n_seed, int32_t *pre /* optional [n_reads x cap]: occurrences of the read's earlier intervals */)
+__global__ void ssg_k_sal_count(ssg_mem_opt_t opt, int n_reads, const ssg_intv_t *intv, const int32_t *n_intv, int cap, int32_t *n_seed, int32_t *pre /* [n_reads x cap]: occurrences of the read's earlier intervals */)
 {
 	long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= n_reads) return;
 	int n = n_intv[r], tot = 0;
 	const ssg_intv_t *p = intv + r * cap;
-	for (int i = 0; i < n; ++i) { if (pre) pre[r * cap + i] = tot; tot += ssg_intv_nocc(opt, p[i].x2); }
+	for (int i = 0; i < n; ++i) { pre[r * cap + i] = tot; tot += ssg_intv_nocc(opt, p[i].x2); }
 	n_seed[r] = tot;
 }
 
@@ -277,28 +268,22 @@ __global__ void ssg_k_sal_mark(int n_reads, const int64_t *seed_off, int32_t *re
  * Invalid seeds (bns_intv2rid < 0) get len = -1 and are skipped by the chaining kernel.
  */
 __global__ void ssg_k_sal(ssg_index_view_t ix, ssg_mem_opt_t opt, int n_reads, const ssg_intv_t *intv, const int32_t *n_intv, int cap,
-                          const int64_t *seed_off, ssg_seed_t *seeds, int32_t *seed_rid, const int32_t *pre /* from ssg_k_sal_count, or null */,
-                          const int32_t *read_of /* per seed: its read (ssg_k_sal_mark + a running maximum), or null: bisection of seed_off */)
+                          const int64_t *seed_off, ssg_seed_t *seeds, int32_t *seed_rid, const int32_t *pre /* from ssg_k_sal_count */,
+                          const int32_t *read_of /* per seed: its read (ssg_k_sal_mark + a running maximum; a bisection of seed_off would be 21 dependent loads for two million reads) */)
 {	/* one lane per SEED (sampled occurrence): every lane does one independent <=31-step LF walk, so the
 	 * random 64-byte fetches of a wave are 64 independent chains and long intervals cost no tail */
 	const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (g >= seed_off[n_reads]) return;
-	long lo = 0, hi = n_reads;                       /* last r with seed_off[r] <= g */
-	if (read_of) lo = read_of[g];                    /* (21 dependent loads for two million reads, by every lane) */
-	else while (lo < hi) { long mid = (lo + hi + 1) >> 1; if (seed_off[mid] <= g) lo = mid; else hi = mid - 1; }
-	const long r = lo;
+	const long r = read_of[g];
 	const ssg_intv_t *p = intv + r * cap;
 	long k = g - seed_off[r];
-	int ii = 0, c;
-	if (pre) {   /* the seed's interval by bisection of the read's running counts: the walk along the list below is a dependent load per interval, and the 64 seeds
-	              * of a wave that lies inside a repeat-heavy read (lists of a hundred intervals, hundreds of occurrences each) all walk most of it */
-		const int32_t *pr = pre + r * cap;
-		int lo2 = 0, hi2 = n_intv[r] - 1;
-		while (lo2 < hi2) { const int mid = (lo2 + hi2 + 1) >> 1; if ((long)pr[mid] <= k) lo2 = mid; else hi2 = mid - 1; }
-		ii = lo2; k -= pr[ii];
-	} else
-	while ((c = ssg_intv_nocc(opt, p[ii].x2)) <= k) { k -= c; ++ii; }
-	const ssg_intv_t v = p[ii];
+	/* the seed's interval by bisection of the read's running counts: a walk along the list is a dependent load per interval, and the 64 seeds
+	 * of a wave that lies inside a repeat-heavy read (lists of a hundred intervals, hundreds of occurrences each) would all walk most of it */
+	const int32_t *pr = pre + r * cap;
+	int lo = 0, hi = n_intv[r] - 1;
+	while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if ((long)pr[mid] <= k) lo = mid; else hi = mid - 1; }
+	k -= pr[lo];
+	const ssg_intv_t v = p[lo];
 	const uint64_t step = v.x2 > (uint64_t)opt.max_occ ? v.x2 / (uint64_t)opt.max_occ : 1;
 	ssg_seed_t s;
 	s.rbeg = (int64_t)ssg_bwt_sa(ix, v.x0 + (uint64_t)k * step);

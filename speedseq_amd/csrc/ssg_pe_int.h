@@ -30,5 +30,5 @@ int ssg_pe_core(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_pairs, con
                 const int32_t *d_pair_batch, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep);
 /* exclusive prefix sum of n int32 counts into n + 1 int64 offsets, on the device; *total = out[n] */
 int ssg_dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t *total);
-#define SSG_MAX_READ_LEN 310   /* 2x300 with room; the kernels' column classes end at 320 (k_sw.h NS = 5, ssg_k_ext_lane<320>, SSG_S2_QWORDS) */
+#define SSG_MAX_READ_LEN 310   /* 2x300 with room; the kernels' column classes end at 320 (k_sw.h NS = 5, the 320-column class of ssg_k_ext_lane_dyn, SSG_S2_QWORDS) */
 #endif

@@ -30,7 +30,7 @@ extern "C" int ssg_seed_smem2(const ssg_index *idx, const ssg_mem_opt_t *opt, in
 	const long nthreads = std::min<long>(((long)n_reads + block - 1) / block * block, 256L * env_int("SSG_SMEM_WAVES_PER_CU", 16) * 64)   /* resident waves per CU, measured (round 4, 1 M pairs): with the table 52.2 ms at 16, 57.4 at 12, 72.6 at 8; without it 12 was best (58.0 vs 61.6 at 16) */;
 	const int scap = max_len + 2;
 	/* the table of short-pattern intervals: used when the index has one and its patterns are shorter than a seed (the third pass jumps kt_k bases in) */
-	const int kt_want = idx->ktab && env_int("SSG_SMEM_USE_KTAB", 1) ? std::min(idx->ktab_k, opt->min_seed_len - 1) : 0;   /* (every level below the table's K is there too: `-k' at or below K uses the levels under it) */
+	const int kt_want = idx->ktab ? std::min(idx->ktab_k, opt->min_seed_len - 1) : 0;   /* (every level below the table's K is there too: `-k' at or below K uses the levels under it) */
 	const int kt_k = kt_want >= 2 ? kt_want : 0;
 	const ssg_pk2_t *const kt = kt_k ? (const ssg_pk2_t*)idx->ktab : (const ssg_pk2_t*)0;
 	dbuf<ssg_pk2_t> scratch((size_t)nthreads * 2 * scap + 64);

@@ -3,7 +3,7 @@
  * Compiled by hipcc for gfx950 (product) or by g++ with -DSSG_EMU against tests/emu (CPU tests).
  *
  * Stage order for a batch of reads (all intermediates stay in HBM):
- *   ssg_k_smem2 (+ ssg_k_smem_heavy; ssg_seed.cpp) -> ssg_k_smem_sort -> ssg_k_sal_count -> [prefix sum] -> ssg_k_sal -> ssg_k_chain -> ssg_k_chain2aln
+ *   ssg_k_smem2 (+ ssg_k_smem_heavy; ssg_seed.cpp) -> ssg_k_smem_sort_rank (+ ssg_k_smem_sort_wave) -> ssg_k_sal_count -> [prefix sum] -> ssg_k_sal -> ssg_k_chain -> ssg_k_chain2aln
  * Per-read variable-length outputs are placed by prefix sums over per-read counts; fixed-capacity
  * stages report overflow and the affected reads are re-run with a larger capacity -- nothing is
  * dropped silently and nothing falls back to the CPU.
@@ -506,7 +506,7 @@ static int run_msw_lane(const ssg_index_t *idx, const ssg_mem_opt_t *opt, long n
 	if (rev) { if (lanes == 4) SSG_ML_GO(4, true); else if (lanes == 2) SSG_ML_GO(2, true); else SSG_ML_GO(1, true); }
 	else { if (lanes == 4) SSG_ML_GO(4, false); else if (lanes == 2) SSG_ML_GO(2, false); else SSG_ML_GO(1, false); }
 #undef SSG_ML_GO
-	if (!rev && env_int("SSG_MSW_REV", 1)) {	/* the reverse passes (KSW_XSTART) of the windows that call for one, the same way */
+	if (!rev) {	/* the reverse passes (KSW_XSTART) of the windows that call for one, the same way */
 		dbuf<uint64_t> d_rkeys((size_t)nj); dbuf<unsigned int> d_nr(2);
 		CHKA(d_rkeys); CHKA(d_nr); CHK(d_nr.zero());
 		SSG_LAUNCH(ssg_k_msw_revlist, (nj + 63) / 64, 64, 0, nj, d_sorted.p, d_jobs, d_res, n_slots, d_rkeys.p, d_nr.p);
@@ -599,11 +599,9 @@ struct seed_stage_t {
  * private large capacity and copies their lists back; on return every n_intv[r] >= 0. */
 static int dev_class_counts(const int32_t *d_key, long n, int tA, int tB, int tC, unsigned int out[5]);
 static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n);
-/* upstream's ks_introsort(mem_intv) of every read's list (k_seed.h): a lane per read ranks the lists of up to 24 intervals, a wave per read the longer ones;
- * SSG_SMEM_SORT_RANK=0: introsort by a lane per read for all (until r06V) */
+/* upstream's ks_introsort(mem_intv) of every read's list (k_seed.h): a lane per read ranks the lists of up to 24 intervals, a wave per read the longer ones */
 static int launch_smem_sort(int n_reads, ssg_intv_t *d_intv, const int32_t *d_n, int cap)
 {
-	if (env_int("SSG_SMEM_SORT_RANK", 1) == 0) { SSG_LAUNCH(ssg_k_smem_sort, (n_reads + 63) / 64, 64, 0, n_reads, d_intv, d_n, cap); return 0; }
 	dbuf<int32_t> d_todo((size_t)n_reads); dbuf<unsigned int> d_nt(1);
 	if (!d_todo.ok() || !d_nt.ok()) { ssg_err_msg = "device allocation failed: interval sort work list"; return SSG_ENOMEM; }
 	CHK(d_nt.zero());
@@ -786,6 +784,31 @@ struct align1_dev_t {	/* device-resident result of stages 1-4 */
 	std::vector<int64_t> h_seed_off; int64_t tot_seeds;
 };
 
+/* The locate stage (upstream mem_chain's walk over the sampled occurrences of every interval): per read its seed count, and per interval the occurrences of
+ * the read's earlier ones (d_pre); the seeds placed by a scan into seed_off (n_reads + 1, the caller's); every seed's read by a running maximum over marks at the
+ * reads' first seeds (a coalesced load instead of a bisection of seed_off); then ssg_k_sal, one lane per seed, finds the seed's interval by bisection of d_pre.
+ * seeds, srid and the scratch mark / read_of are allocated here, tot + 1 entries each; the scratch is the caller's to use again (run_align1 lends d_order / d_kept). */
+static int run_locate(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const ssg_intv_t *d_intv, const int32_t *d_nintv, int cap, int32_t *d_nseed,
+                      int64_t *seed_off, int64_t *tot, dbuf<ssg_seed_t> &seeds, dbuf<int32_t> &srid, dbuf<int32_t> &mark, dbuf<int32_t> &read_of)
+{
+	const int block = 256;
+	dbuf<int32_t> d_pre((size_t)n_reads * cap);
+	if (!d_pre.ok()) { ssg_err_msg = "device allocation failed: d_pre"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_sal_count, (n_reads + block - 1) / block, block, 0, *opt, n_reads, d_intv, d_nintv, cap, d_nseed, d_pre.p);
+	CHK(rt_sync());
+	STAGE("sal_count");
+	CHK(dev_exclusive_scan(d_nseed, seed_off, n_reads, tot));
+	const long g = (long)*tot;
+	if (!seeds.alloc((size_t)g + 1) || !srid.alloc((size_t)g + 1) || !mark.alloc((size_t)g + 1) || !read_of.alloc((size_t)g + 1)) { ssg_err_msg = "device allocation failed: seeds"; return SSG_ENOMEM; }
+	if (g > 0) {
+		CHK(rt_memset(mark.p, 0, (size_t)g * 4));
+		SSG_LAUNCH(ssg_k_sal_mark, (n_reads + block - 1) / block, block, 0, n_reads, (const int64_t*)seed_off, mark.p);
+		CHK(dev_scan_max_i32(mark.p, read_of.p, g));
+	}
+	SSG_LAUNCH(ssg_k_sal, (g + block - 1) / block, block, 0, idx->v, *opt, n_reads, d_intv, d_nintv, cap, (const int64_t*)seed_off, seeds.p, srid.p, (const int32_t*)d_pre.p, (const int32_t*)read_of.p);
+	return 0;   /* d_pre (1.5 GB per million pairs) back to the lane's arena: whatever takes it next is queued behind the kernel above */
+}
+
 static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len,
                       align1_dev_t &o, uint64_t stats[8])
 {
@@ -801,13 +824,6 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	CHKA(d_nintv); CHKA(d_nseed);
 	dbuf<unsigned long long> d_next(1);
 	CHKA(d_next);
-	/* One call at a time in the seeding stage of a device.  Two calls in flight (bin/bwa: a lane each) gain only where their stages differ -- seeding is bound by
-	 * the memory, extension by the vector units, the wave kernels by latency -- and lose nothing but the overlap when they run the same stage side by side; runs
-	 * of the 8 M-pair script leg fell into two groups, 2.7 s and 3.7 s of alignment, by whether the two lanes happened to stay out of step.  A call that finds the
-	 * other one seeding waits here once, and from then on they alternate.  Off unless SSG_SEED_TOKEN=1: on a second box every run was of the fast kind with and without it (profiles/r06y_literal_seed_token.json). */
-	static std::mutex seed_token[16];
-	std::unique_lock<std::mutex> seed_lock(seed_token[ssg_cur_dev & 15], std::defer_lock);
-	if (env_int("SSG_SEED_TOKEN", 0) != 0) seed_lock.lock();
 	for (;;) {
 		int need = 0;
 		if (!d_intv.alloc((size_t)n_reads * cap)) { ssg_err_msg = "device allocation failed: d_intv"; return SSG_ENOMEM; }
@@ -819,36 +835,18 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		if (ssg_debug()) fprintf(stderr, "[ssgpu] SMEM interval capacity widened to %d per read\n", cap);
 	}
 	if (stats) { unsigned long long c; CHK(d_next.down(&c, 1)); stats[5] = c; }
-	if (seed_lock.owns_lock()) { CHK(rt_sync()); seed_lock.unlock(); }
 	STAGE("smem");
-	const int block = 256;
-	dbuf<int32_t> d_pre;   /* per interval: occurrences of the read's earlier ones (ssg_k_sal finds a seed's interval by bisection); SSG_SAL_PREFIX=0: the walk along the list */
-	if (env_int("SSG_SAL_PREFIX", 1) && !d_pre.alloc((size_t)n_reads * cap)) { ssg_err_msg = "device allocation failed: d_pre"; return SSG_ENOMEM; }
-	SSG_LAUNCH(ssg_k_sal_count, (n_reads + block - 1) / block, block, 0, *opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, d_pre.p);
-	CHK(rt_sync());
-	STAGE("sal_count");
 	int64_t tot = 0;
 	if (!o.seed_off.alloc(n_reads + 1)) { ssg_err_msg = "device allocation failed: seed_off"; return SSG_ENOMEM; }
-	CHK(dev_exclusive_scan(d_nseed.p, o.seed_off.p, n_reads, &tot));
+	dbuf<ssg_seed_t> d_seeds; dbuf<int32_t> d_srid, d_order, d_kept;
+	CHK(run_locate(idx, opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, &tot, d_seeds, d_srid, d_order, d_kept));   /* (d_order / d_kept are free until the chaining stage) */
 	o.tot_seeds = tot; o.h_seed_off.clear();
 	size_t ts = (size_t)tot + 1;
-	dbuf<ssg_seed_t> d_seeds(ts); dbuf<int32_t> d_srid(ts), d_order(ts), d_kept(ts), d_cseeds(ts), d_nchain(n_reads), d_err(n_reads);
+	dbuf<int32_t> d_cseeds(ts), d_nchain(n_reads), d_err(n_reads);
 	dbuf<ssg_chain_t> d_chains(ts); dbuf<uint64_t> d_srt(ts); dbuf<unsigned long long> d_cells(1);
-	CHKA(d_seeds); CHKA(d_srid); CHKA(d_order); CHKA(d_kept); CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_err); CHKA(d_chains); CHKA(d_srt); CHKA(d_cells);
+	CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_err); CHKA(d_chains); CHKA(d_srt); CHKA(d_cells);
 	if (!o.regs.alloc(ts) || !o.n_reg.alloc(n_reads)) { ssg_err_msg = "device allocation failed: regs"; return SSG_ENOMEM; }
 	CHK(d_cells.zero());
-	{
-		long g = (long)tot;
-		/* every seed's read by a running maximum over marks at the reads' first seeds (d_order / d_kept are free until the chaining stage); SSG_SAL_READ_OF=0: bisection of seed_off by every lane */
-		const bool rof = g > 0 && env_int("SSG_SAL_READ_OF", 1) != 0;
-		if (rof) {
-			CHK(rt_memset(d_order.p, 0, (size_t)g * 4));
-			SSG_LAUNCH(ssg_k_sal_mark, (n_reads + block - 1) / block, block, 0, n_reads, o.seed_off.p, d_order.p);
-			CHK(dev_scan_max_i32(d_order.p, d_kept.p, g));
-		}
-		SSG_LAUNCH(ssg_k_sal, (g + block - 1) / block, block, 0, idx->v, *opt, n_reads, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p, (const int32_t*)d_pre.p, rof ? (const int32_t*)d_kept.p : (const int32_t*)0);
-		{ dbuf<int32_t> done; done.swap(d_pre); }   /* 1.5 GB per million pairs back to the lane's arena (whatever takes it next is queued behind the kernel above) */
-	}
 	STAGE("sal");
 	/* heaviest-first work order (seed count): the per-read cost of chaining / extension is heavy-tailed */
 	dbuf<int32_t> d_work(n_reads); dbuf<unsigned int> d_queue(8);
@@ -869,7 +867,6 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		const int T = idx->v.n_ctg > 32767 ? 1 << 30 : std::max(1, env_int("SSG_CHAIN_WAVE_MIN", 48));
 		const int TB = env_int("SSG_CHAIN_WAVE_BIG", 0) > 0 ? env_int("SSG_CHAIN_WAVE_BIG", 0) : 1 << 30;
 		const bool ranked = env_int("SSG_CHAIN_RANKED", 1) != 0;
-		const int wsort = (env_int("SSG_CHAIN_WSORT", 1) ? 1 : 0) | (env_int("SSG_CHAIN_SPEC", 1) ? 2 : 0) | (env_int("SSG_CHAIN_BFLT", 1) ? 4 : 0);   /* the wave kernels' weight sort by the whole wave (k_chainw.h wv_introsort_whi) insertion 64 seeds a round and filter 64 chains a round; 0: by one lane / seed by seed / chain by chain (A/B, tests) */
 		const int cap_lim = env_int("SSG_CHAIN_CAP_TEST", 1 << 30);   /* tests: pretend the ranked form holds fewer chains, to walk its fall-back (the shifting form) */
 		int g[7], gl[3];   /* gl: reads with more than 63 / 31 / 15 seeds (the classes of the light reads' LDS kernel) */
 		{	/* "greater than" counts of the seeds-per-read array (d_work sorts it descending: a binary search per threshold; thresholds descending: the counts ascend) */
@@ -903,7 +900,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 			                   d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p, dbgp, d_work.p, kbf);
 #define SSG_CL_LAUNCH(CC, LN, from, to) do { if ((to) > (from)) SSG_LAUNCH_ON(2, (ssg_k_chain_lds<CC, LN>), ((to) - (from) + (LN) - 1) / (LN), (LN), 0, idx->v, *opt, (from), (to), d_off, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p, \
 			d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, kbf); } while (0)
-			if (env_int("SSG_CHAIN_LDS64_LANES", 32) == 32) SSG_CL_LAUNCH(64, 32, b63, b31); else SSG_CL_LAUNCH(64, 64, b63, b31);   /* 47 KB a workgroup instead of 94: fits beside the wave kernels' blocks */
+			SSG_CL_LAUNCH(64, 32, b63, b31);   /* 32 reads a workgroup: 47 KB instead of 94, fits beside the wave kernels' blocks */
 			SSG_CL_LAUNCH(32, 64, b31, b15);
 			SSG_CL_LAUNCH(16, 64, b15, n_reads);
 #undef SSG_CL_LAUNCH
@@ -933,7 +930,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		ssg_fork(2);   /* (again, the wave kernels' two streams: they read the ranks) */
 		int r0 = nC;
 #define SSG_CHW_LAUNCH(si, CC, cnt, maxwg, qi) do { if ((cnt) > 0) SSG_LAUNCH_ON(si, ssg_k_chain_wave<CC>, std::min((int)(cnt), (int)(maxwg)), 64, 0, idx->v, *opt, r0, r0 + (cnt), d_off, d_intv.p, d_nintv.p, cap, \
-		o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p + (qi), kbf, hr, ho, std::min((int)(CC), cap_lim), wsort); r0 += (cnt); } while (0)
+		o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p + (qi), kbf, hr, ho, std::min((int)(CC), cap_lim)); r0 += (cnt); } while (0)
 		SSG_CHW_LAUNCH(0, 5120, n5120, 256, 1);
 		SSG_CHW_LAUNCH(1, 2048, n2048, 512, 3);
 		SSG_CHW_LAUNCH(1, 1024, n1024, 1280, 2);   /* (behind the 2048 class: this stream + two side streams + the light reads' stream are the four hardware queues; a fifth stream shares one) */
@@ -986,63 +983,46 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		if (opt->min_chain_weight > 0 && 2.8f * (float)opt->min_chain_weight <= 0.05f * (float)max_len) {   /* upstream mem_flt_chained_seeds would run (MEM_HSP_COEF x W <= MEM_SEEDSW_COEF x l): its seed-level SW is not built */
 			ssg_err_msg = "-W this small against this read length turns on upstream's chained-seed filter (long-read path), which this build does not have"; return SSG_EINVAL; }
 		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
-		const int short_cap = 72;   /* sides up to 72 bases run with half the LDS per wave (two waves per SIMD) */
-		dbuf<unsigned int> d_nlong(2);
-		CHKA(d_nlong); CHK(d_nlong.zero());
 		SSG_LAUNCH(ssg_k_ext_prep, (n_jobs + 255) / 256, 256, 0, idx->v, *opt, n_reads, n_jobs, d_off, o.seed_off.p, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p,
-		           d_choff.p, (int)SSG_TWIN_GLB, d_xjobs.p, d_kl.p, d_kr.p, short_cap, d_nlong.p, d_seq, env_int("SSG_EXT_ROWS_KEY", 1));
+		           d_choff.p, d_seq, (int)SSG_TWIN_GLB, d_xjobs.p, d_kl.p, d_kr.p);
 		CHK(sort_keys_u64(d_kl.p, d_sl.p, n_jobs, 32, 50)); CHK(sort_keys_u64(d_kr.p, d_sr.p, n_jobs, 32, 50));   /* 9 + 9 bits: 511 - side length, 511 - expected rows */
-		unsigned int h_nlong[2];
-		CHK(d_nlong.down(h_nlong, 2));
-		if (ssg_debug()) fprintf(stderr, "[ssgpu] ext jobs %ld, long sides %u / %u\n", n_jobs, h_nlong[0], h_nlong[1]);
+		if (ssg_debug()) fprintf(stderr, "[ssgpu] ext jobs %ld\n", n_jobs);
 		/* Classes of 8 more columns each, a launch per class with the LDS its longest side needs (k_extlane.h ssg_k_ext_lane_dyn): the list is sorted longest side first, the
 		 * class boundaries are binary searches; a side's classes go round three queues (no tail of one launch before the next starts, and a CU holds a mix of block sizes),
-		 * the right sides after all left ones (they start from the left side's score).  SSG_EXT_DYN=0: the fixed classes below. */
-		const bool ext_dyn = env_int("SSG_EXT_DYN", 1) != 0;
-		if (ext_dyn) {
-			ssg_thr64_t th; int caps[64], ncap = 0;
-			caps[ncap++] = 40; caps[ncap++] = 72;
-			for (int c = 80; c < max_len + 8 && c <= 320; c += 8) caps[ncap++] = c;
-			th.n = ncap + 1;
-			for (int k = 0; k < ncap; ++k) th.t[k] = 511 - caps[k];   /* #sides longer than caps[k] */
-			th.t[ncap] = 511;                                        /* #sides longer than 0 */
-			dbuf<unsigned int> d_b(128); unsigned int hb[2][64];
-			CHKA(d_b);
-			SSG_LAUNCH(ssg_k_sorted_hi_below, 1, 64, 0, d_sl.p, n_jobs, th, d_b.p);
-			SSG_LAUNCH(ssg_k_sorted_hi_below, 1, 64, 0, d_sr.p, n_jobs, th, d_b.p + 64);
-			CHK(d_b.down(&hb[0][0], 128));
+		 * the right sides after all left ones (they start from the left side's score). */
+		ssg_thr64_t th; int caps[64], ncap = 0;
+		caps[ncap++] = 40; caps[ncap++] = 72;
+		for (int c = 80; c < max_len + 8 && c <= 320; c += 8) caps[ncap++] = c;
+		th.n = ncap + 1;
+		for (int k = 0; k < ncap; ++k) th.t[k] = 511 - caps[k];   /* #sides longer than caps[k] */
+		th.t[ncap] = 511;                                        /* #sides longer than 0 */
+		dbuf<unsigned int> d_b(128); unsigned int hb[2][64];
+		CHKA(d_b);
+		SSG_LAUNCH(ssg_k_sorted_hi_below, 1, 64, 0, d_sl.p, n_jobs, th, d_b.p);
+		SSG_LAUNCH(ssg_k_sorted_hi_below, 1, 64, 0, d_sr.p, n_jobs, th, d_b.p + 64);
+		CHK(d_b.down(&hb[0][0], 128));
 #ifndef SSG_EMU
-			if (max_len > 240) {   /* blocks above 64 KB */
-				static bool attr_set[SSG_MAX_DEV] = { false };
-				if (!attr_set[ssg_cur_dev]) { (void)hipFuncSetAttribute((const void*)ssg_k_ext_lane_dyn<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (320 + 8) * 256); attr_set[ssg_cur_dev] = true; }
-			}
+		if (max_len > 240) {   /* blocks above 64 KB */
+			static bool attr_set[SSG_MAX_DEV] = { false };
+			if (!attr_set[ssg_cur_dev]) { (void)hipFuncSetAttribute((const void*)ssg_k_ext_lane_dyn<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (320 + 8) * 256); attr_set[ssg_cur_dev] = true; }
+		}
 #endif
-			for (int side = 0; side < 2; ++side) {
-				const uint64_t *srt = side ? d_sr.p : d_sl.p;
-				ssg_fork(2);
-				for (int k = ncap - 1, q = 0; k >= 0; --k) {   /* longest class first */
-					const long from = (long)hb[side][k], to = (long)hb[side][k == 0 ? ncap : k - 1];
-					if (to <= from) continue;
-					/* (eight columns per trip instead of four -- twice the LDS loads in flight for the classes that run one wave a SIMD -- was measured slower on the MI355X:
-					 * 125.3 vs 119.4 ms at 2x150, 157.7 vs 151.3 at 2x250, profiles/r06f_ext_unroll_ab*.json: the cell loop waits for its own dependent VALU chain, not for LDS) */
-					const int c = caps[k], U = c > 72 ? 4 : 2; const size_t lds = (size_t)(c + 2 * U) * 256;
-#define SSG_XL_GO(LAUNCH, ...) do { if (U == 4) LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<4>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); \
-                                    else LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<2>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); } while (0)
-					if (q % 3 == 0) SSG_XL_GO(SSG_LAUNCH); else if (q % 3 == 1) SSG_XL_GO(SSG_LAUNCH_ON, 0,); else SSG_XL_GO(SSG_LAUNCH_ON, 1,);
-#undef SSG_XL_GO
-					++q;
-				}
-				ssg_join(2);
-			}
-		} else
 		for (int side = 0; side < 2; ++side) {
 			const uint64_t *srt = side ? d_sr.p : d_sl.p;
-			const long nl = (long)h_nlong[side];   /* jobs are sorted longest side first */
-			if (max_len <= 136 + opt->min_seed_len) {
-				if (nl) SSG_LAUNCH(ssg_k_ext_lane<136>, (nl + 63) / 64, 64, 0, idx->v, *opt, side, 0L, nl, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p);
-				if (n_jobs > nl) SSG_LAUNCH(ssg_k_ext_lane<72>, (n_jobs - nl + 63) / 64, 64, 0, idx->v, *opt, side, nl, n_jobs, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p);
-			} else if (max_len <= 256) SSG_LAUNCH(ssg_k_ext_lane<256>, (n_jobs + 63) / 64, 64, 0, idx->v, *opt, side, 0L, n_jobs, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p);
-			else SSG_LAUNCH(ssg_k_ext_lane<320>, (n_jobs + 63) / 64, 64, 0, idx->v, *opt, side, 0L, n_jobs, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p);
+			ssg_fork(2);
+			for (int k = ncap - 1, q = 0; k >= 0; --k) {   /* longest class first */
+				const long from = (long)hb[side][k], to = (long)hb[side][k == 0 ? ncap : k - 1];
+				if (to <= from) continue;
+				/* (eight columns per trip instead of four -- twice the LDS loads in flight for the classes that run one wave a SIMD -- was measured slower on the MI355X:
+				 * 125.3 vs 119.4 ms at 2x150, 157.7 vs 151.3 at 2x250, profiles/r06f_ext_unroll_ab*.json: the cell loop waits for its own dependent VALU chain, not for LDS) */
+				const int c = caps[k], U = c > 72 ? 4 : 2; const size_t lds = (size_t)(c + 2 * U) * 256;
+#define SSG_XL_GO(LAUNCH, ...) do { if (U == 4) LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<4>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); \
+                                    else LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<2>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); } while (0)
+				if (q % 3 == 0) SSG_XL_GO(SSG_LAUNCH); else if (q % 3 == 1) SSG_XL_GO(SSG_LAUNCH_ON, 0,); else SSG_XL_GO(SSG_LAUNCH_ON, 1,);
+#undef SSG_XL_GO
+				++q;
+			}
+			ssg_join(2);
 		}
 	}
 	STAGE("ext_lane");
@@ -1080,24 +1060,23 @@ int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_read
 	CHKA(d_seq); CHKA(d_off); CHKA(d_soff); CHKA(d_nintv); CHKA(d_nseed);
 	CHK(d_seq.up(seq, off[n_reads])); CHK(d_off.up(off, n_reads + 1));
 	dbuf<ssg_intv_t> d_intv;
-	for (int cap = std::max(64, max_len / 2); ; ) {   /* the dense interval layout widens itself, as in run_align1 */
+	int cap = std::max(64, max_len / 2);
+	for (;;) {   /* the dense interval layout widens itself, as in run_align1 */
 		int need = 0;
 		if (!d_intv.alloc((size_t)n_reads * cap)) { ssg_err_msg = "device allocation failed: d_intv"; return SSG_ENOMEM; }
 		CHK(run_smem(idx, opt, n_reads, d_seq.p, d_off.p, max_len, cap, d_intv.p, d_nintv.p, 0, &need));
-		if (need > cap) { cap = (need + 31) / 32 * 32; continue; }
-		SSG_LAUNCH(ssg_k_sal_count, (n_reads + 255) / 256, 256, 0, *opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, (int32_t*)0);
-		int64_t tot = 0;
-		CHK(dev_exclusive_scan(d_nseed.p, d_soff.p, n_reads, &tot));
-		dbuf<ssg_seed_t> d_seeds((size_t)tot + 1); dbuf<int32_t> d_srid((size_t)tot + 1);
-		CHKA(d_seeds); CHKA(d_srid);
-		if (tot > 0) SSG_LAUNCH(ssg_k_sal, (tot + 255) / 256, 256, 0, idx->v, *opt, n_reads, d_intv.p, d_nintv.p, cap, d_soff.p, d_seeds.p, d_srid.p, (const int32_t*)0, (const int32_t*)0);
-		CHK(rt_sync());
-		CHK(d_soff.down(seed_off, (size_t)n_reads + 1));
-		*seeds = (ssg_seed_t*)malloc(sizeof(ssg_seed_t) * (size_t)(tot + 1)); *rids = (int32_t*)malloc(4 * (size_t)(tot + 1));
-		if (!*seeds || !*rids) { free(*seeds); free(*rids); *seeds = 0; *rids = 0; ssg_err_msg = "host allocation failed"; return SSG_ENOMEM; }
-		CHK(d_seeds.down(*seeds, (size_t)tot)); CHK(d_srid.down(*rids, (size_t)tot));
-		return 0;
+		if (need <= cap) break;
+		cap = (need + 31) / 32 * 32;
 	}
+	int64_t tot = 0;
+	dbuf<ssg_seed_t> d_seeds; dbuf<int32_t> d_srid, d_mark, d_read_of;
+	CHK(run_locate(idx, opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, d_soff.p, &tot, d_seeds, d_srid, d_mark, d_read_of));
+	CHK(rt_sync());
+	CHK(d_soff.down(seed_off, (size_t)n_reads + 1));
+	*seeds = (ssg_seed_t*)malloc(sizeof(ssg_seed_t) * (size_t)(tot + 1)); *rids = (int32_t*)malloc(4 * (size_t)(tot + 1));
+	if (!*seeds || !*rids) { free(*seeds); free(*rids); *seeds = 0; *rids = 0; ssg_err_msg = "host allocation failed"; return SSG_ENOMEM; }
+	CHK(d_seeds.down(*seeds, (size_t)tot)); CHK(d_srid.down(*rids, (size_t)tot));
+	return 0;
 }
 
 int ssg_align1_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
@@ -1296,15 +1275,14 @@ static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 					CHK(d_nj.down(njt, 2));
 					const unsigned int nj = njt[0];
 					CHK(run_msw_lane(idx, opt, (long)nj, d_keys.p, d_jobs.p, d_seq.p, d_jres.p, (max_len + 15) / 16 * 16, (int)njt[1], ml_lanes, 0, (long)nslot, (long)seq_bytes));
-					have_slots = env_int("SSG_MSW_USE", 1) != 0;   /* 0: diagnostic -- the windows are computed and not used */
+					have_slots = true;
 					if (ssg_debug()) fprintf(stderr, "[ssgpu] mate rescue: %u listed pairs, %lld slots, %u windows ahead of the decision\n", n_todo, (long long)nslot, nj);
 				}
 			}
 		}
 		SSG_LAUNCH_W(max_len > 255, ssg_k_matesw, nwg, wpb * 64, 0, idx->v, *opt, n_pairs, d_seq.p, d_off.p, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p,
 		           d_bcopy.p, d_tglb.p, d_bglb.p, d_perr.p, d_cnt.p, d_cnt.p + 1, d_mtodo.p, d_q.p, d_sdpbig.p, d_nmtodo.p,
-		           have_slots ? (const ssg_msres_t*)d_jres.p : (const ssg_msres_t*)0, have_slots ? (const int64_t*)d_jbase.p : (const int64_t*)0,
-		           env_int("SSG_MSW_FIXED", 1) ? (const uint8_t*)a1.sdp_fixed.p : (const uint8_t*)0);
+		           have_slots ? (const ssg_msres_t*)d_jres.p : (const ssg_msres_t*)0, have_slots ? (const int64_t*)d_jbase.p : (const int64_t*)0, (const uint8_t*)a1.sdp_fixed.p);
 		CHK(rt_sync());
 		if (ssg_debug()) { unsigned long long c[3]; CHK(d_cnt.down(c, 3)); fprintf(stderr, "[ssgpu] mate rescue: %llu windows aligned, %llu of them ahead of the decision\n", c[1], c[2]); }
 	}

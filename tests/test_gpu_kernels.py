@@ -118,17 +118,10 @@ def test_gpu_repeats_align1(gpu_lib, oracle, repeat_prefix, monkeypatch):
     monkeypatch.setenv("SSG_CHAIN_WAVE_MIN", "4")
     assert common.check_align1(gpu_lib, oracle, 150, seed=22, prefix=repeat_prefix) > 5000
     monkeypatch.setenv("SSG_CHAIN_RANKED", "0")         # the array-shifting insertion instead of the position-rank bitmap
-    monkeypatch.setenv("SSG_CHAIN_WSORT", "0")          # and the weight sort on one lane,
-    monkeypatch.setenv("SSG_CHAIN_BFLT", "0")           # the filter one chain at a time
-    monkeypatch.setenv("SSG_CHAIN_SPEC", "0")           # (and, below with the bitmap again, the insertion seed by seed instead of 64 seeds a round)
     common.check_align1(gpu_lib, oracle, 300, seed=22, prefix=repeat_prefix)
     monkeypatch.delenv("SSG_CHAIN_RANKED")
-    monkeypatch.delenv("SSG_CHAIN_WSORT")
-    monkeypatch.delenv("SSG_CHAIN_BFLT")
     monkeypatch.setenv("SSG_CHAIN_CAP_TEST", "40")      # the ranked form gives up at 40 chains: its fall-back, the shifting form, redoes those reads
-    common.check_align1(gpu_lib, oracle, 300, seed=22, prefix=repeat_prefix)
-    monkeypatch.delenv("SSG_CHAIN_SPEC")
-    common.check_align1(gpu_lib, oracle, 300, seed=22, prefix=repeat_prefix)   # the same give-up out of a round of 64 seeds
+    common.check_align1(gpu_lib, oracle, 300, seed=22, prefix=repeat_prefix)   # (the give-up out of a round of 64 seeds)
     monkeypatch.delenv("SSG_CHAIN_CAP_TEST")
     monkeypatch.setenv("SSG_CHAIN_WAVE_MIN", "100000")  # and the lane-per-read kernel on the same reads
     monkeypatch.setenv("SSG_CHAIN_WAVE_BIG", "100000")
@@ -167,11 +160,9 @@ def test_gpu_chain_filter_options(gpu_lib, oracle, repeat_mid_prefix, monkeypatc
 
 
 def test_gpu_extension_column_classes(gpu_lib, oracle, monkeypatch):
-    # the lane-per-extension kernel with the LDS its class's longest side needs (classes of 8 columns, three queues), then the fixed classes (72 / 136 / 256 / 320 columns)
-    for dyn in ("1", "0"):
-        monkeypatch.setenv("SSG_EXT_DYN", dyn)
-        for k, rl in enumerate((150, 250, 300, 101)):
-            assert common.check_align1(gpu_lib, oracle, 1500, seed=50 + k, read_len=rl) > 1500
+    # the lane-per-extension kernel with the LDS its class's longest side needs (classes of 8 columns, three queues)
+    for k, rl in enumerate((150, 250, 300, 101)):
+        assert common.check_align1(gpu_lib, oracle, 1500, seed=50 + k, read_len=rl) > 1500
 
 
 def test_gpu_chains_at_equal_positions(gpu_lib, oracle, monkeypatch):
@@ -179,9 +170,8 @@ def test_gpu_chains_at_equal_positions(gpu_lib, oracle, monkeypatch):
     # (the ranked wave form gives the read up and redoes it) -- through the lane kernels (LDS, global) and every form of the wave kernels
     seqs = common.reads_with_inner_repeats(common.EXAMPLE_FA, 1500, 5) + common.reads_with_inner_repeats(common.EXAMPLE_FA, 1000, 6, rl=150)
     counts = set()
-    for env in ({}, {"SSG_CHAIN_LDS": "0"}, {"SSG_CHAIN_WAVE_MIN": "1"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_SPEC": "0"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_RANKED": "0"},
-                {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_BFLT": "0", "SSG_CHAIN_WSORT": "0"}):
-        for k in ("SSG_CHAIN_LDS", "SSG_CHAIN_WAVE_MIN", "SSG_CHAIN_SPEC", "SSG_CHAIN_RANKED", "SSG_CHAIN_BFLT", "SSG_CHAIN_WSORT"):
+    for env in ({}, {"SSG_CHAIN_LDS": "0"}, {"SSG_CHAIN_WAVE_MIN": "1"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_RANKED": "0"}):
+        for k in ("SSG_CHAIN_LDS", "SSG_CHAIN_WAVE_MIN", "SSG_CHAIN_RANKED"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -246,7 +236,6 @@ def test_gpu_smem_table_of_short_pattern_intervals(gpu_lib, oracle, repeat_prefi
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "300")
     common.check_smem(gpu_lib, oracle, 1500, seed=53, n_frac=0.01)
     monkeypatch.delenv("SSG_SMEM_MAX_EXT")
-    monkeypatch.setenv("SSG_SMEM_USE_KTAB", "0")       # a table in the index, not used
     common.check_smem(gpu_lib, oracle, 1500, seed=51)
 
 
@@ -256,14 +245,6 @@ def test_gpu_smem_kernel_variants(gpu_lib, oracle, monkeypatch):
     monkeypatch.delenv("SSG_SMEM_KERNEL")
     monkeypatch.setenv("SSG_SA_INTV", "32")   # the file's own suffix-array density
     assert common.check_align1(gpu_lib, oracle, 1500, seed=33) > 1500
-    monkeypatch.delenv("SSG_SA_INTV")
-    # the forms the round's last kernels replaced stay behind switches: introsort by a lane per read; the locate stage's walks instead of running counts / running maximum
-    monkeypatch.setenv("SSG_SMEM_SORT_RANK", "0")
-    common.check_smem(gpu_lib, oracle, 1500, seed=35)
-    monkeypatch.delenv("SSG_SMEM_SORT_RANK")
-    monkeypatch.setenv("SSG_SAL_PREFIX", "0")
-    monkeypatch.setenv("SSG_SAL_READ_OF", "0")
-    assert common.check_align1(gpu_lib, oracle, 1500, seed=36) > 1500
 
 
 @pytest.mark.parametrize("read_len", [150, 250])

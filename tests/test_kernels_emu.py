@@ -93,17 +93,10 @@ def test_emu_repeats_align1(emu_lib, oracle, repeat_prefix, monkeypatch):
     monkeypatch.setenv("SSG_CHAIN_WAVE_MIN", "4")
     assert common.check_align1(emu_lib, oracle, 12, seed=22, prefix=repeat_prefix) > 500
     monkeypatch.setenv("SSG_CHAIN_RANKED", "0")         # the array-shifting insertion instead of the position-rank bitmap
-    monkeypatch.setenv("SSG_CHAIN_WSORT", "0")          # and the weight sort on one lane,
-    monkeypatch.setenv("SSG_CHAIN_BFLT", "0")           # the filter one chain at a time
-    monkeypatch.setenv("SSG_CHAIN_SPEC", "0")           # (and, below with the bitmap again, the insertion seed by seed instead of 64 seeds a round)
     common.check_align1(emu_lib, oracle, 12, seed=22, prefix=repeat_prefix)
     monkeypatch.delenv("SSG_CHAIN_RANKED")
-    monkeypatch.delenv("SSG_CHAIN_WSORT")
-    monkeypatch.delenv("SSG_CHAIN_BFLT")
     monkeypatch.setenv("SSG_CHAIN_CAP_TEST", "40")      # the ranked form gives up at 40 chains: its fall-back, the shifting form, redoes those reads
-    common.check_align1(emu_lib, oracle, 12, seed=22, prefix=repeat_prefix)
-    monkeypatch.delenv("SSG_CHAIN_SPEC")
-    common.check_align1(emu_lib, oracle, 12, seed=22, prefix=repeat_prefix)   # the same give-up out of a round of 64 seeds
+    common.check_align1(emu_lib, oracle, 12, seed=22, prefix=repeat_prefix)   # (the give-up out of a round of 64 seeds)
     monkeypatch.delenv("SSG_CHAIN_CAP_TEST")
     monkeypatch.setenv("SSG_CHAIN_WAVE_MIN", "100000")  # and the lane-per-read kernel on the same reads
     monkeypatch.setenv("SSG_CHAIN_WAVE_BIG", "100000")
@@ -142,11 +135,9 @@ def test_emu_chain_filter_options(emu_lib, oracle, repeat_mid_prefix, monkeypatc
 
 
 def test_emu_extension_column_classes(emu_lib, oracle, monkeypatch):
-    # the lane-per-extension kernel with the LDS its class's longest side needs (classes of 8 columns, three queues), then the fixed classes (72 / 136 / 256 / 320 columns)
-    for dyn in ("1", "0"):
-        monkeypatch.setenv("SSG_EXT_DYN", dyn)
-        for k, rl in enumerate((150, 250, 300, 101)):
-            assert common.check_align1(emu_lib, oracle, 40, seed=50 + k, read_len=rl) > 40
+    # the lane-per-extension kernel with the LDS its class's longest side needs (classes of 8 columns, three queues)
+    for k, rl in enumerate((150, 250, 300, 101)):
+        assert common.check_align1(emu_lib, oracle, 40, seed=50 + k, read_len=rl) > 40
 
 
 def test_emu_chains_at_equal_positions(emu_lib, oracle, monkeypatch):
@@ -154,9 +145,8 @@ def test_emu_chains_at_equal_positions(emu_lib, oracle, monkeypatch):
     # (the ranked wave form gives the read up and redoes it) -- through the lane kernels (LDS, global) and every form of the wave kernels
     seqs = common.reads_with_inner_repeats(common.EXAMPLE_FA, 120, 5) + common.reads_with_inner_repeats(common.EXAMPLE_FA, 80, 6, rl=150)
     counts = set()
-    for env in ({}, {"SSG_CHAIN_LDS": "0"}, {"SSG_CHAIN_WAVE_MIN": "1"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_SPEC": "0"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_RANKED": "0"},
-                {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_BFLT": "0", "SSG_CHAIN_WSORT": "0"}):
-        for k in ("SSG_CHAIN_LDS", "SSG_CHAIN_WAVE_MIN", "SSG_CHAIN_SPEC", "SSG_CHAIN_RANKED", "SSG_CHAIN_BFLT", "SSG_CHAIN_WSORT"):
+    for env in ({}, {"SSG_CHAIN_LDS": "0"}, {"SSG_CHAIN_WAVE_MIN": "1"}, {"SSG_CHAIN_WAVE_MIN": "1", "SSG_CHAIN_RANKED": "0"}):
+        for k in ("SSG_CHAIN_LDS", "SSG_CHAIN_WAVE_MIN", "SSG_CHAIN_RANKED"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -181,7 +171,7 @@ def test_emu_repeats_pe_sam(emu_lib, oracle, repeat_prefix):
 
 def test_emu_pe_sam_300(emu_lib, oracle, tmp_path, repeat_prefix):
     # 2x300 (the reference's script takes any read length, bin/speedseq:196-200): the column classes above 256 -- fifth register column of the
-    # wave SW (k_sw.h), ssg_k_ext_lane<320>, 9-bit column tags of the lane kernels, 16-bit query coordinates of the wave chaining, 40 LDS words of
+    # wave SW (k_sw.h), the 320-column class of ssg_k_ext_lane_dyn, 9-bit column tags of the lane kernels, 16-bit query coordinates of the wave chaining, 40 LDS words of
     # the seeding kernels -- end to end against the oracle, and the stage twins at those lengths
     text, stats = common.check_pe_sam(emu_lib, oracle, 250, seed=19, read_len=300, ins_mean=900, ins_std=150)
     assert text.count("\n") >= 500
@@ -235,7 +225,6 @@ def test_emu_smem_table_of_short_pattern_intervals(emu_lib, oracle, repeat_prefi
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "300")
     common.check_smem(emu_lib, oracle, 60, seed=53, n_frac=0.01)
     monkeypatch.delenv("SSG_SMEM_MAX_EXT")
-    monkeypatch.setenv("SSG_SMEM_USE_KTAB", "0")       # a table in the index, not used
     common.check_smem(emu_lib, oracle, 60, seed=51)
 
 
@@ -246,15 +235,7 @@ def test_emu_smem_kernel_variants(emu_lib, oracle, repeat_prefix, monkeypatch):
     monkeypatch.setenv("SSG_SA_INTV", "32")
     assert common.check_align1(emu_lib, oracle, 150, seed=33) > 150
     monkeypatch.delenv("SSG_SA_INTV")
-    # the forms the round's last kernels replaced stay behind switches: introsort by a lane per read; the locate stage's walks instead of running counts / running maximum
-    monkeypatch.setenv("SSG_SMEM_SORT_RANK", "0")
-    common.check_smem(emu_lib, oracle, 60, seed=35)
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
-    monkeypatch.delenv("SSG_SMEM_SORT_RANK")
     common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)   # lists beyond 24 intervals: the wave form of the sort
-    monkeypatch.setenv("SSG_SAL_PREFIX", "0")
-    monkeypatch.setenv("SSG_SAL_READ_OF", "0")
-    assert common.check_align1(emu_lib, oracle, 150, seed=36) > 150
 
 
 @pytest.mark.parametrize("read_len", [150, 250])
