@@ -1,6 +1,7 @@
 """Shared test helpers: seeded inputs and the comparison routines used by both the CPU-side tests
 (host-emulation build of the kernel sources) and the `-m gpu` parity tests (HIP build)."""
 import os
+import time
 
 import numpy as np
 
@@ -32,7 +33,23 @@ def mutate(rng, q, max_sub=8, max_indel=3):
     return tl
 
 
-def make_extend_jobs(n, seed, max_qlen=200):
+def scored_opts(lib, oracle, scores):
+    """(option block of the library, option block of the oracle or None) with scores = (a, b, o_del, e_del, o_ins, e_ins); None: the defaults"""
+    opt = lib.opt_init() if lib is not None else None
+    if not scores:
+        return opt, None
+    if opt is not None:
+        for k, v in zip(("a", "b", "o_del", "e_del", "o_ins", "e_ins"), scores):
+            opt[k] = v
+        m = opt["mat"][0]
+        for x in range(4):
+            for y in range(4):
+                m[x * 5 + y] = scores[0] if x == y else -scores[1]
+    return opt, (oracle.opt_scores(*scores) if oracle is not None else None)
+
+
+def make_extend_jobs(n, seed, max_qlen=200, scores=None, end_bonus=5):
+    """scores: the anchor's score h0 is drawn in matches (1 .. 159 times a), as upstream's seeds give it"""
     rng = np.random.default_rng(seed)
     jobs, qs, ts, qo, to = [], [], [], 0, 0
     for _ in range(n):
@@ -53,7 +70,7 @@ def make_extend_jobs(n, seed, max_qlen=200):
         h0 = int(rng.integers(1, 160))
         w = int(rng.choice([100, 200, 5, 20]))
         zd = int(rng.choice([100, 100, 0, 20]))
-        jobs.append((qo, qlen, to, len(t), w, 5, zd, h0))
+        jobs.append((qo, qlen, to, len(t), w, end_bonus, zd, h0 * (scores[0] if scores else 1)))
         qs.append(q)
         ts.append(t)
         qo += qlen
@@ -61,7 +78,13 @@ def make_extend_jobs(n, seed, max_qlen=200):
     return np.array(jobs, dtype=capi.EXT_JOB_DT), qs, ts
 
 
-def make_local_jobs(n, seed, qlens=(150, 150, 100, 76, 36, 250, 200)):
+def local_xtra(qlen, scores=None):
+    """xtra as mate rescue sets it: 8-bit cells where the best possible score stays under 250, the seed's score as the threshold"""
+    a = scores[0] if scores else 1
+    return KSW_XSUBO | KSW_XSTART | (KSW_XBYTE if qlen * a < 250 else 0) | (19 * a)
+
+
+def make_local_jobs(n, seed, qlens=(150, 150, 100, 76, 36, 250, 200), scores=None):
     rng = np.random.default_rng(seed)
     jobs, qs, ts, qo, to = [], [], [], 0, 0
     for _ in range(n):
@@ -74,7 +97,7 @@ def make_local_jobs(n, seed, qlens=(150, 150, 100, 76, 36, 250, 200)):
                      list(rng.integers(0, 4, size=int(rng.integers(0, 300)))), dtype=np.uint8)
         if rng.random() < 0.3:
             t = np.concatenate([t, np.array(mutate(rng, q), dtype=np.uint8)])
-        xtra = KSW_XSUBO | KSW_XSTART | (KSW_XBYTE if qlen < 250 else 0) | 19
+        xtra = local_xtra(qlen, scores)
         jobs.append((qo, qlen, to, len(t), xtra, 0))
         qs.append(q)
         ts.append(t)
@@ -83,7 +106,8 @@ def make_local_jobs(n, seed, qlens=(150, 150, 100, 76, 36, 250, 200)):
     return np.array(jobs, dtype=capi.SW_JOB_DT), qs, ts
 
 
-def make_global_jobs(n, seed):
+def make_global_jobs(n, seed, scores=None):
+    """scores: accepted like the other generators'; a global job carries no field that scales with the scoring, so the jobs do not depend on it"""
     rng = np.random.default_rng(seed)
     jobs, qs, ts, qo, to = [], [], [], 0, 0
     for _ in range(n):
@@ -110,31 +134,234 @@ def sim_reads(n_pairs, seed, read_len=150, fasta=EXAMPLE_FA, **kw):
     return pairs, seqs, np.concatenate(seqs), off
 
 
+
+COLUMN_CLASSES = (40, 72, 136, 256, 320)
+
+
+def _edge_qlens(max_qlen, extra=()):
+    """1, 2, either side of every column class, and the longest query the entry point takes with the one before it"""
+    ls = {1, 2, max_qlen - 1, max_qlen}
+    for cap in COLUMN_CLASSES:
+        ls.update((cap - 1, cap, cap + 1))
+    ls.update(extra)
+    return sorted(l for l in ls if 1 <= l <= max_qlen)
+
+
+def fixed_extend_shapes(seed, max_qlen, scores=None):
+    """The shapes a random draw only meets by chance, as (q, t, w, zdrop, h0 in matches): query lengths 1, 2 and either side of every column
+    class, a target of one base, an all-N query, a target that matches nowhere (the first row dies), h0 = 1, a target shorter than the
+    band, a target longer than qlen + w."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for ql in _edge_qlens(max_qlen):
+        q = rng.integers(0, 4, size=ql, dtype=np.uint8)
+        t = np.array(mutate(rng, q, 4, 2) + list(rng.integers(0, 4, size=int(rng.integers(0, 30)))), dtype=np.uint8)
+        if t.size == 0:
+            t = q.copy()
+        out.append((q, t, int(rng.choice([100, 20])), 100, int(rng.integers(1, 40))))
+    ql = min(60, max_qlen)
+    q = rng.integers(0, 4, size=ql, dtype=np.uint8)
+    out.append((q, q[:1].copy(), 100, 100, 30))                                           # tlen 1
+    out.append((np.full(ql, 4, dtype=np.uint8), rng.integers(0, 4, size=ql + 10, dtype=np.uint8), 100, 100, 25))   # all N
+    out.append((np.zeros(ql, dtype=np.uint8), np.full(ql + 5, 1, dtype=np.uint8), 100, 100, 1))    # no base matches: the first row is dead
+    out.append((q, np.concatenate([q, q[:20]]), 100, 0, 1))                               # h0 == 1 on a perfect target: a live cell at the lowest score
+    out.append((q, q[:7].copy(), 20, 100, 40))                                            # target shorter than the band
+    out.append((q, np.concatenate([q, rng.integers(0, 4, size=5 + 40, dtype=np.uint8)]), 5, 0, 40))   # target longer than qlen + w, no z-drop
+    return out
+
+
+def add_extend_shapes(jobs, qs, ts, shapes, scores=None, end_bonus=5):
+    a = scores[0] if scores else 1
+    qs, ts, rows = list(qs), list(ts), [tuple(j) for j in jobs]
+    qo, to = sum(len(q) for q in qs), sum(len(t) for t in ts)
+    for q, t, w, zd, h0 in shapes:
+        rows.append((qo, len(q), to, len(t), w, end_bonus, zd, h0 * a if h0 > 1 else 1))
+        qs.append(q); ts.append(t)
+        qo += len(q); to += len(t)
+    return np.array(rows, dtype=capi.EXT_JOB_DT), qs, ts
+
+
+def fixed_local_shapes(seed, max_qlen=320, scores=None):
+    """(q, t) for the local alignment: query lengths 1, 2, either side of every column class, 249 / 250 and the last length with 8-bit cells at this match
+    score with the first one with 16-bit cells (249 // a, 249 // a + 1: where local_xtra switches KSW_XBYTE), 257 and 320; a target of one base; an all-N
+    query; a target that matches nowhere"""
+    rng = np.random.default_rng(seed)
+    out = []
+    a = scores[0] if scores else 1
+    for ql in _edge_qlens(max_qlen, (249, 250, 257, 320, 249 // a, 249 // a + 1)):
+        q = rng.integers(0, 4, size=ql, dtype=np.uint8)
+        t = np.array(list(rng.integers(0, 4, size=int(rng.integers(0, 60)))) + mutate(rng, q, 5, 2) + list(rng.integers(0, 4, size=int(rng.integers(1, 60)))), dtype=np.uint8)
+        out.append((q, t))
+    q = rng.integers(0, 4, size=50, dtype=np.uint8)
+    out.append((q, q[10:11].copy()))
+    out.append((np.full(50, 4, dtype=np.uint8), rng.integers(0, 4, size=80, dtype=np.uint8)))
+    out.append((np.zeros(50, dtype=np.uint8), np.full(70, 1, dtype=np.uint8)))
+    return out
+
+
+def add_local_shapes(jobs, qs, ts, shapes, scores=None):
+    qs, ts, rows = list(qs), list(ts), [tuple(j) for j in jobs]
+    qo, to = sum(len(q) for q in qs), sum(len(t) for t in ts)
+    for q, t in shapes:
+        rows.append((qo, len(q), to, len(t), local_xtra(len(q), scores), 0))
+        qs.append(q); ts.append(t)
+        qo += len(q); to += len(t)
+    return np.array(rows, dtype=capi.SW_JOB_DT), qs, ts
+
+
+def fixed_global_shapes(seed, max_qlen=318):
+    """(q, t, w) for the global alignment: w == |tlen - qlen| (the band's corner is the last cell), w larger than both lengths, qlen 1, tlen 1, query lengths
+    either side of every column class, an all-N query, a target that matches nowhere"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for ql in _edge_qlens(max_qlen):
+        q = rng.integers(0, 4, size=ql, dtype=np.uint8)
+        t = np.array(mutate(rng, q, 5, 3), dtype=np.uint8)
+        if t.size == 0:
+            t = q.copy()
+        out.append((q, t, abs(len(t) - ql) + int(rng.integers(0, 12))))
+    for _ in range(4):                                                                   # w == |tlen - qlen|, the lengths different
+        q = rng.integers(0, 4, size=int(rng.integers(20, 120)), dtype=np.uint8)
+        t = np.array(mutate(rng, q, 5, 3), dtype=np.uint8)
+        if len(t) == len(q):
+            t = np.concatenate([t[:10], t[13:]])
+        out.append((q, t, abs(len(t) - len(q))))
+    q = rng.integers(0, 4, size=30, dtype=np.uint8)
+    out.append((q, q.copy(), 0))                                                         # equal lengths, w == 0: the diagonal alone
+    out.append((q, np.array(mutate(rng, q, 4, 2), dtype=np.uint8), 100))                 # w larger than both lengths
+    out.append((q[:1].copy(), q[:9].copy(), 8))                                          # qlen 1
+    out.append((q[:9].copy(), q[3:4].copy(), 8))                                         # tlen 1
+    out.append((q[:1].copy(), q[:1].copy(), 3))
+    out.append((np.full(30, 4, dtype=np.uint8), q[:27].copy(), 6))
+    out.append((np.zeros(30, dtype=np.uint8), np.full(33, 1, dtype=np.uint8), 5))
+    return out
+
+
+def add_global_shapes(jobs, qs, ts, shapes):
+    qs, ts, rows = list(qs), list(ts), [tuple(j) for j in jobs]
+    qo, to = sum(len(q) for q in qs), sum(len(t) for t in ts)
+    for q, t, w in shapes:
+        rows.append((qo, len(q), to, len(t), w, 0))
+        qs.append(q); ts.append(t)
+        qo += len(q); to += len(t)
+    return np.array(rows, dtype=capi.GLB_JOB_DT), qs, ts
+
+
+class RefTally:
+    """what a run compared with the full-matrix reference: jobs, and the jobs whose gtle the `gscore <= 0' rule left out"""
+    def __init__(self):
+        self.jobs = self.ext_jobs = self.gtle_excluded = 0
+        self.seconds = 0.0   # spent inside tests/dp_reference.py: what the tests' job counts are sized by
+
+    def check_share(self):
+        """under one in ten of the extension jobs"""
+        assert self.jobs > 0 and self.ext_jobs > 0 and 10 * self.gtle_excluded < self.ext_jobs, "gtle left uncompared on %d of %d extensions" % (self.gtle_excluded, self.ext_jobs)
+
+
+DEFAULT_SCORES = (1, 4, 6, 1, 6, 1)
+
+
+def ref_check_extend(got, q, t, scores, w, end_bonus, zdrop, h0, tally, who, ctx):
+    """got = (score, qle, tle, gtle, gscore, max_off) against tests/dp_reference.py: score, qle, tle, max_off equal; gscore equal or both <= 0; gtle equal
+    where gscore > 0"""
+    import dp_reference
+    t0 = time.perf_counter()
+    r = dp_reference.extend(q, t, scores or DEFAULT_SCORES, w, end_bonus, zdrop, h0)
+    tally.seconds += time.perf_counter() - t0
+    msg = ("%s disagrees with the full-matrix reference" % who, ctx, "got", got, "reference", r)
+    assert (got[0], got[1], got[2], got[5]) == (r[0], r[1], r[2], r[5]), msg
+    assert got[4] == r[4] or (got[4] <= 0 and r[4] <= 0), msg
+    if r[4] > 0:
+        assert got[3] == r[3], msg
+    elif got[3] != r[3]:
+        tally.gtle_excluded += 1
+    tally.jobs += 1
+    tally.ext_jobs += 1
+
+
+def ref_check_local(got, q, t, xtra, scores, tally, who, ctx):
+    """got = (score, te, qe, score2, te2, tb, qb): score is the maximum of the reference's H, H[te][qe] holds it, and where a start is reported the global
+    alignment of q[qb..qe] and t[tb..te] earns the same.  score2 / te2 are not the reference's business."""
+    import dp_reference
+    sc = scores or DEFAULT_SCORES
+    t0 = time.perf_counter()
+    H = dp_reference.local(q, t, sc)
+    tally.seconds += time.perf_counter() - t0
+    score, te, qe, tb, qb = got[0], got[1], got[2], got[5], got[6]
+    msg = ("%s disagrees with the full-matrix reference" % who, ctx, "got", got, "reference maximum", int(H.max()))
+    assert score == int(H.max()), msg
+    assert -1 <= te < len(t) and -1 <= qe < len(q) and int(H[te + 1][qe + 1]) == score, msg
+    if (xtra & KSW_XSTART) and not ((xtra & KSW_XSUBO) and score < (xtra & 0xffff)):
+        assert 0 <= tb <= te and 0 <= qb <= qe, msg
+        g = dp_reference.global_(q[qb:qe + 1], t[tb:te + 1], sc, len(q) + len(t))
+        assert g == score, msg + ("global score of the reported substrings", g)
+    tally.jobs += 1
+
+
+def ref_check_global(score, n_cigar, cigar, q, t, w, scores, tally, who, ctx):
+    """the score is the reference's banded optimum; the CIGAR consumes both sequences whole, stays in the band and earns that score"""
+    import dp_reference
+    sc = scores or DEFAULT_SCORES
+    t0 = time.perf_counter()
+    r = dp_reference.global_(q, t, sc, w)
+    tally.seconds += time.perf_counter() - t0
+    msg = ("%s disagrees with the full-matrix reference" % who, ctx, "got", int(score), "reference", r)
+    assert int(score) == r, msg
+    assert 0 < n_cigar <= len(cigar), msg
+    rs, qn, tn, off = dp_reference.rescore(cigar[:n_cigar], q, t, sc)
+    assert (qn, tn) == (len(q), len(t)) and off <= w and rs == r, msg + ("cigar", [(int(c) & 0xf, int(c) >> 4) for c in cigar[:n_cigar]], "earns", rs, "consumes", qn, tn, "leaves the diagonal by", off)
+    tally.jobs += 1
+
+
 REG_FIELDS = ["rb", "re", "qb", "qe", "rid", "score", "truesc", "sub", "csub", "w", "seedcov", "seedlen0", "n_comp", "frac_rep"]
 
 
-def check_extend(lib, oracle, n, seed, max_qlen=200):
-    jobs, qs, ts = make_extend_jobs(n, seed, max_qlen=max_qlen)
-    res, cells = lib.extend_batch(lib.opt_init(), jobs, np.concatenate(qs), np.concatenate(ts))
-    for i in range(n):
-        o = oracle.extend2(qs[i], ts[i], int(jobs[i]["w"]), 5, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]))
-        assert o == tuple(int(x) for x in res[i]), (i, jobs[i], o, res[i])
+def check_extend(lib, oracle, n, seed, max_qlen=200, scores=None, end_bonus=5, ref=None, fixed=False):
+    """ref: a RefTally -- every job is compared with tests/dp_reference.py too; fixed: the shapes of fixed_extend_shapes follow the random jobs"""
+    jobs, qs, ts = make_extend_jobs(n, seed, max_qlen=max_qlen, scores=scores, end_bonus=end_bonus)
+    if fixed:
+        jobs, qs, ts = add_extend_shapes(jobs, qs, ts, fixed_extend_shapes(seed, max_qlen, scores), scores, end_bonus)
+    opt, oopt = scored_opts(lib, oracle, scores)
+    res, cells = lib.extend_batch(opt, jobs, np.concatenate(qs), np.concatenate(ts))
+    for i in range(len(jobs)):
+        o = oracle.extend2(qs[i], ts[i], int(jobs[i]["w"]), end_bonus, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]), oopt)
+        got = tuple(int(x) for x in res[i])
+        assert o == got, ("extend_batch disagrees with the oracle", scores, i, jobs[i], o, res[i])
+        if ref is not None:
+            ref_check_extend(got, qs[i], ts[i], scores, int(jobs[i]["w"]), end_bonus, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]), ref, "extend_batch", (scores, i, jobs[i]))
     assert cells > 0
 
 
-def check_extend_lane(lib, oracle, n, seed, workdir, qcaps=(72, 136, 256)):
+def check_extend_lane(lib, oracle, n, seed, workdir, qcaps=(72, 136, 256), scores=None, end_bonus=5, ref=None, fixed=False):
     """ksw_extend2 through the lane-per-extension kernel code of the product's mem_chain2aln path (ssg_k_ext_lane's ln_extend2: packed 13-bit
     cells in LDS, 6-bit score table, targets read from the 2-bit reference) against the oracle: the jobs of make_extend_jobs (w 5 / 20 / 100 /
     200, zdrop 0 / 20 / 100, N in the query, h0 1..160) plus h0 up to the 13-bit ceiling, their targets laid out as a reference of their
-    own, read forward, backward and from the reverse strand (the four ways the product's left / right extensions walk the reference)."""
+    own, read forward, backward and from the reverse strand (the four ways the product's left / right extensions walk the reference).
+    scores / end_bonus: queries no longer than the 13-bit cells hold at that match score; ref / fixed: as check_extend."""
     rng = np.random.default_rng(seed)
     fa = os.path.join(str(workdir), "extlane_%d.fa" % seed)
     done = 0
+    a = scores[0] if scores else 1
+    opt, oopt = scored_opts(lib, oracle, scores)
     for qcap in qcaps:
-        jobs, qs, ts = make_extend_jobs(n, seed + qcap, max_qlen=min(qcap, 318) + 1)
+        max_qlen = min(qcap, 318, (8190 - end_bonus - 1) // a)   # h0 >= 1 must still fit
+        jobs, qs, ts = make_extend_jobs(n, seed + qcap, max_qlen=max_qlen + 1, scores=scores, end_bonus=end_bonus)
         for i in range(n):   # a share of the jobs with start scores near the ceiling of the packed cells (h0 + qlen * a + end_bonus < 8191)
+            ceil = 8190 - int(jobs[i]["qlen"]) * a - end_bonus
             if rng.random() < 0.15:
-                jobs[i]["h0"] = 8190 - int(jobs[i]["qlen"]) - 5 - int(rng.integers(0, 60))
+                jobs[i]["h0"] = max(1, ceil - int(rng.integers(0, 60)))
+            elif jobs[i]["h0"] > ceil:
+                jobs[i]["h0"] = ceil
+        if fixed:   # appended after the draw above: the fixed shapes keep their own h0, lowered only where the cells could not hold it
+            jobs, qs, ts = add_extend_shapes(jobs, qs, ts, fixed_extend_shapes(seed + qcap, max_qlen, scores), scores, end_bonus)
+            for i in range(len(ts)):   # the targets come from a 2-bit reference, and a job's target is not empty
+                if ts[i].size == 0:
+                    ts[i] = qs[i][:1].copy() if qs[i][0] < 4 else np.zeros(1, dtype=np.uint8)
+            jobs["tlen"] = [t.size for t in ts]
+            jobs["toff"] = np.concatenate([[0], np.cumsum([t.size for t in ts])[:-1]])
+            for i in range(n, len(jobs)):
+                jobs[i]["h0"] = min(int(jobs[i]["h0"]), 8190 - int(jobs[i]["qlen"]) * a - end_bonus)
+        m = len(jobs)
         tcat = np.concatenate(ts)
         with open(fa, "w") as f:
             f.write(">t\n")
@@ -149,23 +376,33 @@ def check_extend_lane(lib, oracle, n, seed, workdir, qcaps=(72, 136, 256)):
         modes = [("fwd +1", starts, 1, lambda t: t), ("fwd -1", starts + tl - 1, -1, lambda t: t[::-1]),
                  ("rev +1", 2 * L - starts - tl, 1, lambda t: comp(t[::-1])), ("rev -1", 2 * L - 1 - starts, -1, lambda t: comp(t))]
         for name, tpos, d, view in modes:
-            res, cells = lib.extend_lane_batch(idx, lib.opt_init(), jobs, tpos, d, np.concatenate(qs), qcap)
+            res, cells = lib.extend_lane_batch(idx, opt, jobs, tpos, d, np.concatenate(qs), qcap)
             assert cells > 0
-            for i in range(n):
-                o = oracle.extend2(qs[i], np.ascontiguousarray(view(ts[i])), int(jobs[i]["w"]), 5, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]))
-                assert o == tuple(int(x) for x in res[i]), (qcap, name, i, jobs[i], o, res[i])
-            done += n
+            for i in range(m):
+                tv = np.ascontiguousarray(view(ts[i]))
+                o = oracle.extend2(qs[i], tv, int(jobs[i]["w"]), end_bonus, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]), oopt)
+                got = tuple(int(x) for x in res[i])
+                assert o == got, ("extend_lane_batch disagrees with the oracle", scores, qcap, name, i, jobs[i], o, res[i])
+                if ref is not None:
+                    ref_check_extend(got, qs[i], tv, scores, int(jobs[i]["w"]), end_bonus, int(jobs[i]["zdrop"]), int(jobs[i]["h0"]), ref, "extend_lane_batch", (scores, qcap, name, i, jobs[i]))
+            done += m
         lib.index_destroy(idx)
     return done
 
 
-def check_local_lane(lib, oracle, n, seed, workdir, lanes=(1, 2, 4), scores=None, qlens=None):
+def check_local_lane(lib, oracle, n, seed, workdir, lanes=(1, 2, 4), scores=None, qlens=None, ref=None, fixed=False, expect_lane=True):
     """ksw_align2 as mate rescue runs it in the product path (k_mswlane.h: forward pass by the lane kernel -- strips of 8 target rows in
     registers, packed 13-bit strip boundaries in LDS, 5-bit score table, targets from the 2-bit reference --, reverse pass by the wave code)
     against the oracle: make_local_jobs' queries (36 .. 250 bases, some with N) and targets (hits, half hits, second hits, none), the targets
-    laid out as a reference of their own and read from both strands, 1 / 2 / 4 lanes per job."""
+    laid out as a reference of their own and read from both strands, 1 / 2 / 4 lanes per job.
+    ref: a RefTally -- xtra follows the scores (local_xtra) and every job is compared with tests/dp_reference.py too; fixed: the shapes of
+    fixed_local_shapes follow the random jobs; expect_lane False: scoring the lane kernel must refuse -- every job through the wave form."""
     rng = np.random.default_rng(seed)
-    jobs, qs, ts = make_local_jobs(n, seed, qlens) if qlens else make_local_jobs(n, seed)
+    kw = dict(scores=scores) if ref is not None else {}
+    jobs, qs, ts = make_local_jobs(n, seed, qlens, **kw) if qlens else make_local_jobs(n, seed, **kw)
+    if fixed:
+        jobs, qs, ts = add_local_shapes(jobs, qs, ts, fixed_local_shapes(seed, scores=scores), scores)
+        n = len(jobs)
     for i in range(n):
         if rng.random() < 0.2:   # N bases in the query
             q = qs[i].copy(); q[rng.random(q.size) < 0.03] = 4; qs[i] = q
@@ -185,27 +422,26 @@ def check_local_lane(lib, oracle, n, seed, workdir, lanes=(1, 2, 4), scores=None
     L = int(tcat.size)
     starts = jobs["toff"].astype(np.int64)
     tl = jobs["tlen"].astype(np.int64)
-    opt, oopt = lib.opt_init(), None
-    if scores:   # (a, b, o_del, e_del, o_ins, e_ins)
-        for k, v in zip(("a", "b", "o_del", "e_del", "o_ins", "e_ins"), scores):
-            opt[k] = v
-        m = opt["mat"][0]
-        for x in range(4):
-            for y in range(4):
-                m[x * 5 + y] = scores[0] if x == y else -scores[1]
-        oopt = oracle.opt_scores(*scores)
+    opt, oopt = scored_opts(lib, oracle, scores)   # (a, b, o_del, e_del, o_ins, e_ins)
     done = taken = 0
     rc = lambda a: np.where(a[::-1] < 4, 3 - a[::-1], 4).astype(np.uint8)
     for name, tpos, view, qview in (("fwd", starts, lambda t: t, lambda q: q), ("rev", 2 * L - starts - tl, rc, rc)):   # the reverse strand reads the windows reverse-complemented: so are the queries, or nothing would hit
         qv = [np.ascontiguousarray(qview(q)) for q in qs]
-        want = [oracle.align2(qv[i], np.ascontiguousarray(view(ts[i])), int(jobs[i]["xtra"]), oopt) for i in range(n)]
+        tv = [np.ascontiguousarray(view(t)) for t in ts]
+        want = [oracle.align2(qv[i], tv[i], int(jobs[i]["xtra"]), oopt) for i in range(n)]
+        if ref is not None:   # the oracle's answer once per strand; the kernel's must equal it for every lane count below
+            for i in range(n):
+                ref_check_local(want[i], qv[i], tv[i], int(jobs[i]["xtra"]), scores, ref, "the oracle", (scores, name, i, jobs[i]))
         for nl in lanes:
             res, from_lane = lib.align2_lane_batch(idx, opt, jobs, tpos, np.concatenate(qv), nl)
             for i in range(n):
-                assert want[i] == tuple(int(x) for x in res[i]), (nl, name, i, jobs[i], want[i], res[i], int(from_lane[i]))
+                assert want[i] == tuple(int(x) for x in res[i]), ("align2_lane_batch disagrees with the oracle", scores, nl, name, i, jobs[i], want[i], res[i], int(from_lane[i]))
             done += n
             taken += int((from_lane > 0).sum())
-            assert (from_lane == 2).sum() > n // 4, "the reverse passes did not go through the lane kernel"
+            if expect_lane:
+                assert (from_lane == 2).sum() > n // 4, "the reverse passes did not go through the lane kernel"
+            else:
+                assert (from_lane == 0).all(), "scoring beyond the lane kernel's fields went through it"
     lib.index_destroy(idx)
     return done, taken
 
@@ -227,20 +463,35 @@ def check_seeds(lib, oracle, n_pairs, seed, prefix=EXAMPLE_FA, read_len=150):
     return tot
 
 
-def check_local(lib, oracle, n, seed):
-    jobs, qs, ts = make_local_jobs(n, seed)
-    res = lib.align2_batch(lib.opt_init(), jobs, np.concatenate(qs), np.concatenate(ts))
-    for i in range(n):
-        o = oracle.align2(qs[i], ts[i], int(jobs[i]["xtra"]))
-        assert o == tuple(int(x) for x in res[i]), (i, jobs[i], o, res[i])
+def check_local(lib, oracle, n, seed, scores=None, ref=None, fixed=False):
+    """ref / fixed: as check_local_lane"""
+    jobs, qs, ts = make_local_jobs(n, seed, scores=scores)
+    if fixed:
+        jobs, qs, ts = add_local_shapes(jobs, qs, ts, fixed_local_shapes(seed, scores=scores), scores)
+    opt, oopt = scored_opts(lib, oracle, scores)
+    res = lib.align2_batch(opt, jobs, np.concatenate(qs), np.concatenate(ts))
+    for i in range(len(jobs)):
+        o = oracle.align2(qs[i], ts[i], int(jobs[i]["xtra"]), oopt)
+        got = tuple(int(x) for x in res[i])
+        assert o == got, ("align2_batch disagrees with the oracle", scores, i, jobs[i], o, res[i])
+        if ref is not None:
+            ref_check_local(got, qs[i], ts[i], int(jobs[i]["xtra"]), scores, ref, "align2_batch", (scores, i, jobs[i]))
 
 
-def check_global(lib, oracle, n, seed):
-    jobs, qs, ts = make_global_jobs(n, seed)
-    sc, nc, cg = lib.global_batch(lib.opt_init(), jobs, np.concatenate(qs), np.concatenate(ts))
-    for i in range(n):
-        osc, on, ocg = oracle.global2(qs[i], ts[i], int(jobs[i]["w"]))
-        assert osc == sc[i] and on == nc[i] and np.array_equal(ocg[:on], cg[i, :on]), (i, jobs[i])
+def check_global(lib, oracle, n, seed, scores=None, ref=None, fixed=False):
+    """ref: a RefTally -- score and CIGAR are checked against tests/dp_reference.py too (the CIGAR buffers are then long enough for every path); fixed: the
+    shapes of fixed_global_shapes follow the random jobs"""
+    jobs, qs, ts = make_global_jobs(n, seed, scores=scores)
+    if fixed:
+        jobs, qs, ts = add_global_shapes(jobs, qs, ts, fixed_global_shapes(seed))
+    opt, oopt = scored_opts(lib, oracle, scores)
+    cap = 64 if ref is None else 1024
+    sc, nc, cg = lib.global_batch(opt, jobs, np.concatenate(qs), np.concatenate(ts), cap=cap)
+    for i in range(len(jobs)):
+        osc, on, ocg = oracle.global2(qs[i], ts[i], int(jobs[i]["w"]), cap=cap, opt=oopt)
+        assert osc == sc[i] and on == nc[i] and np.array_equal(ocg[:on], cg[i, :on]), ("global_batch disagrees with the oracle", scores, i, jobs[i])
+        if ref is not None:
+            ref_check_global(sc[i], int(nc[i]), cg[i], qs[i], ts[i], int(jobs[i]["w"]), scores, ref, "global_batch", (scores, i, jobs[i]))
 
 
 def check_smem(lib, oracle, n_pairs, seed, read_len=150, prefix=EXAMPLE_FA, n_frac=0.0, cap=96):

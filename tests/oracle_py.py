@@ -41,9 +41,9 @@ class Oracle:
             assert self.l.orc_idx_save(h, fasta.encode()) == 0
         return h
 
-    def extend2(self, q, t, w, end_bonus, zdrop, h0):
+    def extend2(self, q, t, w, end_bonus, zdrop, h0, opt=None):
         out = (C.c_int * 6)()
-        self.l.orc_api_extend2(self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(w), C.c_int(end_bonus), C.c_int(zdrop), C.c_int(h0), out)
+        self.l.orc_api_extend2(opt or self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(w), C.c_int(end_bonus), C.c_int(zdrop), C.c_int(h0), out)
         return tuple(out)
 
     def opt_scores(self, a, b, o_del, e_del, o_ins, e_ins):
@@ -63,10 +63,10 @@ class Oracle:
         self.l.orc_api_align2(opt or self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(xtra), out)
         return tuple(out)
 
-    def global2(self, q, t, w, cap=64):
+    def global2(self, q, t, w, cap=64, opt=None):
         n = C.c_int(0)
         cig = np.zeros(cap, dtype=np.uint32)
-        sc = self.l.orc_api_global2(self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(w), C.byref(n), _ptr(cig), C.c_int(cap))
+        sc = self.l.orc_api_global2(opt or self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(w), C.byref(n), _ptr(cig), C.c_int(cap))
         return sc, n.value, cig
 
     def collect_intv(self, idx, seq, cap=4096):
