@@ -28,6 +28,9 @@ void orc_api_opt_scores(orc_opt_t *o, int a, int b, int o_del, int e_del, int o_
 /* the chain filter's knobs (bwa mem -D, -W, -N and the compiled-in mask_level / max_chain_gap), for the chaining kernels' tests */
 void orc_api_opt_chain(orc_opt_t *o, float drop_ratio, float mask_level, int min_chain_weight, int max_chain_extend, int max_chain_gap)
 { o->drop_ratio = drop_ratio; o->mask_level = mask_level; o->min_chain_weight = min_chain_weight; o->max_chain_extend = max_chain_extend; o->max_chain_gap = max_chain_gap; }
+/* the seeding stage's knobs (bwa mem -k, -r, -c, -y and the compiled-in split_width), for the seeding reference's tests */
+void orc_api_opt_seed(orc_opt_t *o, int min_seed_len, float split_factor, int split_width, int max_occ, int64_t max_mem_intv)
+{ o->min_seed_len = min_seed_len; o->split_factor = split_factor; o->split_width = split_width; o->max_occ = max_occ; o->max_mem_intv = (uint64_t)max_mem_intv; }
 void orc_api_free(void *p) { free(p); }
 
 /* mem_collect_intv for one read; returns the number of intervals (out may be smaller than needed) */

@@ -446,8 +446,9 @@ def check_local_lane(lib, oracle, n, seed, workdir, lanes=(1, 2, 4), scores=None
     return done, taken
 
 
-def check_seeds(lib, oracle, n_pairs, seed, prefix=EXAMPLE_FA, read_len=150):
-    """the seeds mem_chain visits (interval -> sampled occurrences -> bwt_sa + bns_intv2rid, upstream's order) straight from ssg_k_sal against the oracle"""
+def check_seeds(lib, oracle, n_pairs, seed, prefix=EXAMPLE_FA, read_len=150, ref=None, ref_n=16):
+    """the seeds mem_chain visits (interval -> sampled occurrences -> bwt_sa + bns_intv2rid, upstream's order) straight from ssg_k_sal against the oracle;
+    ref: a SeedTally -- the first ref_n reads are compared with tests/seed_reference.py too"""
     oidx, gidx = oracle.idx_load(prefix), lib.index_load(prefix)
     _, seqs, seq, off = sim_reads(n_pairs, seed, read_len, fasta=prefix)
     seed_off, seeds, rids = lib.seeds_batch(gidx, lib.opt_init(), seq, off)
@@ -458,7 +459,11 @@ def check_seeds(lib, oracle, n_pairs, seed, prefix=EXAMPLE_FA, read_len=150):
         assert len(o) == len(g), (r, len(o), len(g))
         assert np.array_equal(o[:, 0], g["rbeg"]) and np.array_equal(o[:, 1], g["qbeg"]) and np.array_equal(o[:, 2], g["len"]), r
         assert np.array_equal(o[:, 3], rids[seed_off[r]:seed_off[r + 1]]), r
+        if ref is not None and r < ref_n:
+            ref_check_seeds(g, rids[seed_off[r]:seed_off[r + 1]], s, None, seed_ref(prefix), ref, "seeds_batch", (prefix, seed, r))
         tot += len(o)
+    if ref is not None:
+        ref.check()
     lib.index_destroy(gidx)
     return tot
 
@@ -494,8 +499,9 @@ def check_global(lib, oracle, n, seed, scores=None, ref=None, fixed=False):
             ref_check_global(sc[i], int(nc[i]), cg[i], qs[i], ts[i], int(jobs[i]["w"]), scores, ref, "global_batch", (scores, i, jobs[i]))
 
 
-def check_smem(lib, oracle, n_pairs, seed, read_len=150, prefix=EXAMPLE_FA, n_frac=0.0, cap=96):
-    """seeding intervals (upstream mem_collect_intv) of every read against the oracle; n_frac: share of the bases turned into N"""
+def check_smem(lib, oracle, n_pairs, seed, read_len=150, prefix=EXAMPLE_FA, n_frac=0.0, cap=96, ref=None, ref_n=16):
+    """seeding intervals (upstream mem_collect_intv) of every read against the oracle; n_frac: share of the bases turned into N;
+    ref: a SeedTally -- the first ref_n reads are compared with tests/seed_reference.py too"""
     oidx, gidx = oracle.idx_load(prefix), lib.index_load(prefix)
     _, seqs, seq, off = sim_reads(n_pairs, seed, read_len, fasta=prefix)
     if n_frac > 0:
@@ -507,6 +513,10 @@ def check_smem(lib, oracle, n_pairs, seed, read_len=150, prefix=EXAMPLE_FA, n_fr
     for r, s in enumerate(seqs):
         o = oracle.collect_intv(oidx, s)
         assert len(o) == cnt[r] and np.array_equal(o, intv[r, :cnt[r]]), r
+        if ref is not None and r < ref_n:
+            ref_check_smem(intv[r, :cnt[r]], s, None, seed_ref(prefix), ref, "smem_batch", (prefix, seed, r))
+    if ref is not None:
+        ref.check()
     lib.index_destroy(gidx)
 
 
@@ -861,3 +871,212 @@ def check_hotpath(lib, oracle, n_pairs, per, read_len, to_dev):
     n_disc, n_spl = len(od) // 2, len(os_)
     assert (int(s16[8]), int(s16[9])) == (len(od), n_spl) and n_disc > 0 and (n_spl > 0 or n_pairs < 2000), (s16, n_disc, n_spl)
     return int(s16[10]), int(s16[1]), len(od), n_spl
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# seeding against tests/seed_reference.py
+# ------------------------------------------------------------------------------------------------------------------------------
+_SEED_REFS = {}
+
+
+def seed_ref(prefix):
+    """the reference of an index (doubled text + suffix array by sorting), made once per index in a process"""
+    import seed_reference
+    if prefix not in _SEED_REFS:
+        _SEED_REFS[prefix] = seed_reference.SeedRef.from_index(prefix)
+    return _SEED_REFS[prefix]
+
+
+class SeedTally:
+    """what a run compared with tests/seed_reference.py: reads submitted and compared, the reads whose reference list holds an interval of pass 2 / of
+    pass 3, the x2 values and the seeds with rid < 0 that the reference saw"""
+    def __init__(self):
+        self.submitted = self.compared = self.pass2 = self.pass3 = self.neg_rid = self.seeds = 0
+        self.x2 = set()
+        self.seconds = 0.0   # spent inside tests/seed_reference.py
+
+    def check(self, passes=True):
+        assert self.submitted > 0 and self.compared == self.submitted, "%d of %d reads compared with the seeding reference" % (self.compared, self.submitted)
+        if passes:
+            assert self.pass2 > 0 and self.pass3 > 0, "no read with an interval of pass 2 (%d) or of pass 3 (%d)" % (self.pass2, self.pass3)
+
+
+def seed_opts(lib, oracle, sopt):
+    """(option block of the library, option block of the oracle or None, seed_reference.SeedOpts) with sopt = (min_seed_len, split_factor, split_width, max_occ,
+    max_mem_intv); None: the defaults, the blocks untouched"""
+    import seed_reference
+    opt = lib.opt_init() if lib is not None else None
+    if not sopt:
+        return opt, None, seed_reference.DEFAULTS
+    if opt is not None:
+        for k, v in zip(("min_seed_len", "split_factor", "split_width", "max_occ", "max_mem_intv"), sopt):
+            opt[k] = v
+    return opt, (oracle.opt_seed(*sopt) if oracle is not None else None), seed_reference.SeedOpts(*sopt)
+
+
+def seed_reference_lists(sref, reads, ropt, tally=None):
+    """[(intervals, (n1, n2, n3), seeds)] of every read from tests/seed_reference.py"""
+    t0 = time.perf_counter()
+    out = []
+    for q in reads:
+        iv, ps = sref.collect_intv(q, ropt, passes=True)
+        out.append((iv, ps, sref.seeds_of(iv, ropt)))
+    if tally is not None:
+        tally.seconds += time.perf_counter() - t0
+    return out
+
+
+def ref_check_smem(got, q, ropt, sref, tally, who, ctx, want=None):
+    """got: INTV_DT rows of one read.  Exact equality of the whole list with the reference's: x0, x1, x2, info and the count."""
+    import seed_reference
+    tally.submitted += 1
+    if want is None:
+        want = seed_reference_lists(sref, [q], ropt or seed_reference.DEFAULTS, tally)[0]
+    iv, ps, _ = want
+    g = [(int(r["x0"]), int(r["x1"]), int(r["x2"]), int(r["info"])) for r in got]
+    assert g == iv, ("%s disagrees with the seeding reference" % who, ctx, "got", g, "reference", iv, "passes", ps)
+    tally.pass2 += ps[1] > 0
+    tally.pass3 += ps[2] > 0
+    tally.x2.update(t[2] for t in iv)
+    tally.compared += 1
+
+
+def ref_check_seeds(got, rids, q, ropt, sref, tally, who, ctx, want=None):
+    """got: SEED_DT rows (or rows of (rbeg, qbeg, len, rid) when rids is None) of one read.  rbeg, qbeg, len, rid equal the reference's, in order."""
+    import seed_reference
+    tally.submitted += 1
+    if want is None:
+        want = seed_reference_lists(sref, [q], ropt or seed_reference.DEFAULTS, tally)[0]
+    iv, ps, sd = want
+    if rids is None:
+        g = [tuple(int(x) for x in r) for r in got]
+    else:
+        g = [(int(r["rbeg"]), int(r["qbeg"]), int(r["len"]), int(k)) for r, k in zip(got, rids)]
+    assert g == sd, ("%s disagrees with the seeding reference" % who, ctx, "got", len(g), "reference", len(sd), [x for x in zip(g, sd) if x[0] != x[1]][:4])
+    tally.pass2 += ps[1] > 0
+    tally.pass3 += ps[2] > 0
+    tally.x2.update(t[2] for t in iv)
+    tally.neg_rid += sum(1 for t in sd if t[3] < 0)
+    tally.seeds += len(sd)
+    tally.compared += 1
+
+
+PLANTED_FAMILIES = (10, 11, 19, 20, 21, 39, 40, 41, 100, 520, 1003)   # copies, both strands together: x2 of a read inside the family
+
+
+def planted_reference(oracle, dirname, seed=9):
+    """Writes a reference of three contigs with families of IDENTICAL copies on both strands and its index (built by the oracle) into dirname; returns
+    (prefix, what was planted).  A family of k copies is one random stretch F (40 bases, 30 for the two large families) planted k times as A F A or
+    its reverse complement, so every occurrence of F in the doubled text reads A F A: a read that carries C F C matches F and not a base more, and its
+    interval has x2 == k.  k lands on both sides of split_width (10, 11), max_mem_intv (19, 20, 21), of -c 20 (20, 21, 39, 40, 41, 100: step 1, 1, 1, 2,
+    2, 5) and of the default -c (520, 1003).  The middle 24 bases of each family up to 41 copies are planted 5 more times, so that a re-seeding finds them.
+    Further: a tandem repeat of a 7-base unit (30 units); a stretch that is its own reverse complement (60 bases); for the list-capacity cases every
+    20-base window of one random 330-base string R, each between bases that R does not continue with (the read R has an interval at every start); a run
+    of 30 N in the FASTA, which the index turns into random bases plus an .amb hole."""
+    prefix = os.path.join(str(dirname), "planted.fa")
+    rng = np.random.default_rng(seed)
+    comp = lambda a: (3 - a[::-1]).astype(np.uint8)
+    rnd = lambda n: rng.integers(0, 4, size=int(n)).astype(np.uint8)
+    A = np.zeros(1, dtype=np.uint8)
+    fams, units = {}, []
+    for k in PLANTED_FAMILIES:
+        F = rnd(30 if k > 100 else 40)
+        while F[0] == 0 or F[-1] == 0 or F[0] == 3 or F[-1] == 3:    # (the flanks stay distinguishable on both strands)
+            F = rnd(F.size)
+        fams[k] = F
+        u = np.concatenate([A, F, A])
+        units += [u if rng.random() < 0.5 else comp(u) for _ in range(k)]
+        if k <= 41:
+            c = np.concatenate([A, F[8:32], A])
+            units += [c if rng.random() < 0.5 else comp(c) for _ in range(5)]
+    R = rnd(330)
+    for j in range(R.size - 20 + 1):
+        before = (R[j - 1] + 1 + rng.integers(0, 3)) % 4 if j > 0 else rng.integers(0, 4)
+        after = (R[j + 20] + 1 + rng.integers(0, 3)) % 4 if j + 20 < R.size else rng.integers(0, 4)
+        units.append(np.concatenate([[before], R[j:j + 20], [after]]).astype(np.uint8))
+    order = rng.permutation(len(units))
+    tandem = np.tile(rnd(7), 30)
+    half = rnd(30)
+    selfrc = np.concatenate([half, comp(half)])
+    pieces = [rnd(400)]
+    for i in order:
+        pieces += [units[i], rnd(rng.integers(4, 10))]
+    pieces += [rnd(300), tandem, rnd(300), selfrc, rnd(400)]
+    seq = np.concatenate(pieces)
+    cuts = (seq.size // 3, seq.size * 2 // 3)
+    ctgs = [seq[:cuts[0]], seq[cuts[0]:cuts[1]], seq[cuts[1]:]]
+    n_at = 200                                                      # the N run, inside the first contig's leading random stretch
+    meta = dict(families=fams, tandem=tandem, selfrc=selfrc, many=R, ctg_len=[c.size for c in ctgs], n_run=(n_at, 30))
+    if not os.path.exists(prefix + ".bwt"):
+        with open(prefix, "w") as fh:
+            for name, c in zip(("pl1", "pl2", "pl3"), ctgs):
+                txt = "".join("ACGT"[x] for x in c)
+                if name == "pl1":
+                    txt = txt[:n_at] + "N" * 30 + txt[n_at + 30:]
+                fh.write(">%s\n" % name)
+                for i in range(0, len(txt), 60):
+                    fh.write(txt[i:i + 60] + "\n")
+        oracle.idx_build(prefix, save=True)
+    return prefix, meta
+
+
+def fixed_seed_reads(sref, seed, planted=None, n_sim=0, fasta=None):
+    """The reads a simulation only meets by chance, as (name, codes), from the reference's own text (sref: a seed_reference.SeedRef): lengths 0 (the shortest
+    the entry points take), 1, 18, 19, 20, 21 and 310; all N; an N at the first base, at the last base, every 20th base (runs of exactly 19) and every 19th
+    (runs of 18); an exact copy of the text; a mismatch every 10 bases; matches of exactly 27 and 28 bases between mismatches; the first and the last 150 bases
+    of each strand; reads across the strand junction (one of them its own reverse complement) and, with more than one contig, across a contig boundary;
+    planted: a read inside each planted family (C F C between random bases), the self-reverse-complement stretch, the tandem repeat, and the read with an
+    interval at every start (310 bases of it, and 100; named many*: their lists outgrow the capacities, so they run in batches of their own)."""
+    rng = np.random.default_rng(seed)
+    t2, l = sref.t2, sref.l_pac
+    rnd = lambda n: rng.integers(0, 4, size=int(n)).astype(np.uint8)
+    out = []
+    if n_sim:
+        _, seqs, _, _ = sim_reads(n_sim // 2, seed, 150, fasta=fasta)
+        for i, s in enumerate(seqs):
+            s = s.copy()
+            if i % 2:
+                s[rng.random(s.size) < 0.03] = 4
+            out.append(("sim%d" % i, s))
+    base = int(l * 0.37)                                             # 310 bases of the forward strand in which every 16-mer occurs once: the copies below match there alone
+    while not all(sref.occ(t2[base + j:base + j + 16]) == 1 for j in range(0, 310 - 15, 7)):
+        base += 37
+        assert base + 310 <= l, "no stretch of unique sequence in this text"
+    copy = lambda n, at=base: t2[at:at + n].copy()
+    for n in (0, 1, 18, 19, 20, 21, 310):
+        out.append(("len%d" % n, copy(n)))
+    out.append(("allN", np.full(60, 4, dtype=np.uint8)))
+    q = copy(150); q[0] = 4; out.append(("N_first", q))
+    q = copy(150); q[-1] = 4; out.append(("N_last", q))
+    q = copy(150); q[19::20] = 4; out.append(("N_every20", q))
+    q = copy(150); q[18::19] = 4; out.append(("N_every19", q))
+    out.append(("exact", copy(150)))
+    q = copy(150); q[9::10] = (q[9::10] + 1) % 4; out.append(("mm_every10", q))
+    q = copy(150)
+    for p in (27, 56, 84, 113):
+        q[p] = (q[p] + 2) % 4
+    out.append(("runs27_28", q))
+    out.append(("fwd_first", t2[:150].copy())); out.append(("fwd_last", t2[l - 150:l].copy()))
+    out.append(("rev_first", t2[l:l + 150].copy())); out.append(("rev_last", t2[2 * l - 150:].copy()))
+    out.append(("junction_selfrc", t2[l - 75:l + 75].copy())); out.append(("junction", t2[l - 100:l + 50].copy()))
+    for k in range(1, len(sref.ctg_off)):
+        b = sref.ctg_off[k]
+        out.append(("boundary%d" % k, t2[b - 70:b + 80].copy()))
+    if planted is not None:
+        C = np.ones(1, dtype=np.uint8)
+        for k, F in planted["families"].items():
+            out.append(("family%d" % k, np.concatenate([rnd(12), C, F, C, rnd(12)])))
+            out.append(("family%d_rc" % k, (3 - np.concatenate([rnd(12), C, F, C, rnd(12)])[::-1]).astype(np.uint8)))
+        out.append(("selfrc", np.concatenate([rnd(20), planted["selfrc"], rnd(20)])))
+        out.append(("tandem", planted["tandem"][3:3 + 120].copy()))
+        out.append(("tandem_mm", np.concatenate([rnd(15), planted["tandem"][:90], rnd(15)])))
+        out.append(("many310", planted["many"][:310].copy()))
+        out.append(("many100", planted["many"][5:105].copy()))
+    return out
+
+
+def cat_reads(reads):
+    seqs = [np.ascontiguousarray(q, dtype=np.uint8) for _, q in reads]
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs])
+    return seqs, np.concatenate(seqs), off

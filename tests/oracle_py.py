@@ -58,6 +58,12 @@ class Oracle:
         self.l.orc_api_opt_chain(o, C.c_float(drop_ratio), C.c_float(mask_level), C.c_int(min_chain_weight), C.c_int(max_chain_extend), C.c_int(max_chain_gap))
         return o
 
+    def opt_seed(self, min_seed_len, split_factor, split_width, max_occ, max_mem_intv):
+        """an option block of its own with these seeding settings"""
+        o = C.c_void_p(self.l.orc_api_opt_new())
+        self.l.orc_api_opt_seed(o, C.c_int(min_seed_len), C.c_float(split_factor), C.c_int(split_width), C.c_int(max_occ), C.c_int64(max_mem_intv))
+        return o
+
     def align2(self, q, t, xtra, opt=None):
         out = (C.c_int * 7)()
         self.l.orc_api_align2(opt or self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(xtra), out)
@@ -69,16 +75,16 @@ class Oracle:
         sc = self.l.orc_api_global2(opt or self.opt, C.c_int(len(q)), _ptr(q), C.c_int(len(t)), _ptr(t), C.c_int(w), C.byref(n), _ptr(cig), C.c_int(cap))
         return sc, n.value, cig
 
-    def collect_intv(self, idx, seq, cap=4096):
+    def collect_intv(self, idx, seq, cap=4096, opt=None):
         out = np.zeros(cap, dtype=INTV_DT)
-        n = self.l.orc_api_collect_intv(self.opt, idx, C.c_int(len(seq)), _ptr(seq), _ptr(out), C.c_int(cap))
+        n = self.l.orc_api_collect_intv(opt or self.opt, idx, C.c_int(len(seq)), _ptr(seq), _ptr(out), C.c_int(cap))
         return out[:n]
 
-    def seeds(self, idx, seq, cap=1 << 16):
+    def seeds(self, idx, seq, cap=1 << 16, opt=None):
         """(rbeg, qbeg, len, rid) of every seed mem_chain visits for the read, in its order"""
         out = np.zeros((cap, 4), dtype=np.int64)
         self.l.orc_api_seeds.restype = C.c_int64
-        n = self.l.orc_api_seeds(self.opt, idx, C.c_int(len(seq)), _ptr(seq), _ptr(out), C.c_int64(cap))
+        n = self.l.orc_api_seeds(opt or self.opt, idx, C.c_int(len(seq)), _ptr(seq), _ptr(out), C.c_int64(cap))
         assert n <= cap
         return out[:n]
 

@@ -21,8 +21,8 @@ def test_gpu_extend_lane_kernel(gpu_lib, oracle, tmp_path):
 
 def test_gpu_seeds_sal(gpu_lib, oracle, repeat_prefix):
     # row a3: ssg_k_sal's seed lists (bwt_sa + bns_intv2rid) directly, also on a repeat-rich reference and at the file's SA density
-    assert common.check_seeds(gpu_lib, oracle, 1500, seed=62) > 1000
-    assert common.check_seeds(gpu_lib, oracle, 10, seed=63, prefix=repeat_prefix) > 1000
+    assert common.check_seeds(gpu_lib, oracle, 1500, seed=62, ref=common.SeedTally()) > 1000
+    assert common.check_seeds(gpu_lib, oracle, 10, seed=63, prefix=repeat_prefix, ref=common.SeedTally()) > 1000
 
 
 def test_gpu_local(gpu_lib, oracle):
@@ -45,7 +45,7 @@ def test_gpu_global(gpu_lib, oracle):
 
 
 def test_gpu_smem(gpu_lib, oracle):
-    common.check_smem(gpu_lib, oracle, 2000, seed=14)
+    common.check_smem(gpu_lib, oracle, 2000, seed=14, ref=common.SeedTally())
 
 
 def test_gpu_align1_150(gpu_lib, oracle):
@@ -72,7 +72,7 @@ def test_gpu_pe_sam_300(gpu_lib, oracle, tmp_path, repeat_prefix):
     common.check_extend(gpu_lib, oracle, 1500, seed=21, max_qlen=318)
     done, taken = common.check_local_lane(gpu_lib, oracle, 400, seed=22, workdir=tmp_path, lanes=(4, 2, 1), qlens=(300, 300, 310, 280, 257, 264))
     assert done == 2400 and taken > 2000
-    common.check_smem(gpu_lib, oracle, 600, seed=23, read_len=300, cap=192)
+    common.check_smem(gpu_lib, oracle, 600, seed=23, read_len=300, cap=192, ref=common.SeedTally())
     assert common.check_align1(gpu_lib, oracle, 200, seed=24, read_len=300, prefix=repeat_prefix) > 5000   # wave-per-read chaining: query coordinates beyond 255
 
 
@@ -210,17 +210,17 @@ def test_gpu_pair_wave_kernel_forced(gpu_lib, oracle, repeat_pe_prefix, monkeypa
 def test_gpu_smem_budget_and_wave_kernel(gpu_lib, oracle, repeat_prefix, monkeypatch):
     # extension budget of the lane kernel: given-up reads are redone by the wave-per-read kernel (k_smem2.h)
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "1")        # every read given up at once: the wave kernel does them all, both list classes
-    common.check_smem(gpu_lib, oracle, 1500, seed=41)
-    common.check_smem(gpu_lib, oracle, 500, seed=42, read_len=250)
-    common.check_smem(gpu_lib, oracle, 500, seed=44, n_frac=0.02)
-    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(gpu_lib, oracle, 1500, seed=41, ref=common.SeedTally())
+    common.check_smem(gpu_lib, oracle, 500, seed=42, read_len=250, ref=common.SeedTally())
+    common.check_smem(gpu_lib, oracle, 500, seed=44, n_frac=0.02, ref=common.SeedTally())
+    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "700")      # some of each
     monkeypatch.setenv("SSG_SMEM_MAX_ROW", "18")       # ... and reads whose first row is longer than this
-    common.check_smem(gpu_lib, oracle, 1500, seed=41)
-    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(gpu_lib, oracle, 1500, seed=41, ref=common.SeedTally())
+    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "2147483647")   # no budget: the lane kernel alone, also on ambiguous bases and repeats
-    common.check_smem(gpu_lib, oracle, 500, seed=44, n_frac=0.02)
-    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(gpu_lib, oracle, 500, seed=44, n_frac=0.02, ref=common.SeedTally())
+    common.check_smem(gpu_lib, oracle, 40, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
 
 
 def test_gpu_smem_table_of_short_pattern_intervals(gpu_lib, oracle, repeat_prefix, monkeypatch):
@@ -229,19 +229,19 @@ def test_gpu_smem_table_of_short_pattern_intervals(gpu_lib, oracle, repeat_prefi
     for k in ("2", "5", "11", "0", "25"):              # 25: capped by what the index is worth (log4 of the text + 2) and by min_seed_len - 1 in the kernel
         monkeypatch.setenv("SSG_KTAB_K", k)
         monkeypatch.setenv("SSG_KTAB_VERIFY", "1")
-        common.check_smem(gpu_lib, oracle, 1500, seed=51)
-        common.check_smem(gpu_lib, oracle, 1500, seed=52, n_frac=0.03)
+        common.check_smem(gpu_lib, oracle, 1500, seed=51, ref=common.SeedTally())
+        common.check_smem(gpu_lib, oracle, 1500, seed=52, n_frac=0.03, ref=common.SeedTally())
     monkeypatch.setenv("SSG_KTAB_K", "9")
-    common.check_smem(gpu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(gpu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "300")
-    common.check_smem(gpu_lib, oracle, 1500, seed=53, n_frac=0.01)
+    common.check_smem(gpu_lib, oracle, 1500, seed=53, n_frac=0.01, ref=common.SeedTally())
     monkeypatch.delenv("SSG_SMEM_MAX_EXT")
-    common.check_smem(gpu_lib, oracle, 1500, seed=51)
+    common.check_smem(gpu_lib, oracle, 1500, seed=51, ref=common.SeedTally())
 
 
 def test_gpu_smem_kernel_variants(gpu_lib, oracle, monkeypatch):
     monkeypatch.setenv("SSG_SMEM_KERNEL", "lane")     # the nested-loop form (the product kernels' fall-back), on the same reads
-    common.check_smem(gpu_lib, oracle, 1500, seed=31)
+    common.check_smem(gpu_lib, oracle, 1500, seed=31, ref=common.SeedTally())
     monkeypatch.delenv("SSG_SMEM_KERNEL")
     monkeypatch.setenv("SSG_SA_INTV", "32")   # the file's own suffix-array density
     assert common.check_align1(gpu_lib, oracle, 1500, seed=33) > 1500

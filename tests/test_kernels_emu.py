@@ -17,8 +17,8 @@ def test_emu_extend_lane_kernel(emu_lib, oracle, tmp_path):
 
 def test_emu_seeds_sal(emu_lib, oracle, repeat_prefix):
     # row a3: ssg_k_sal's seed lists (bwt_sa + bns_intv2rid) directly, also on a repeat-rich reference and at the file's SA density
-    assert common.check_seeds(emu_lib, oracle, 40, seed=62) > 1000
-    assert common.check_seeds(emu_lib, oracle, 10, seed=63, prefix=repeat_prefix) > 1000
+    assert common.check_seeds(emu_lib, oracle, 40, seed=62, ref=common.SeedTally()) > 1000
+    assert common.check_seeds(emu_lib, oracle, 10, seed=63, prefix=repeat_prefix, ref=common.SeedTally()) > 1000
 
 
 def test_emu_local(emu_lib, oracle):
@@ -38,7 +38,7 @@ def test_emu_global(emu_lib, oracle):
 
 
 def test_emu_smem(emu_lib, oracle):
-    common.check_smem(emu_lib, oracle, 150, seed=4)
+    common.check_smem(emu_lib, oracle, 150, seed=4, ref=common.SeedTally())
 
 
 def test_emu_align1_150(emu_lib, oracle):
@@ -199,17 +199,17 @@ def test_emu_pair_wave_kernel_forced(emu_lib, oracle, repeat_pe_prefix, monkeypa
 def test_emu_smem_budget_and_wave_kernel(emu_lib, oracle, repeat_prefix, monkeypatch):
     # extension budget of the lane kernel: given-up reads are redone by the wave-per-read kernel (k_smem2.h)
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "1")        # every read given up at once: the wave kernel does them all, both list classes
-    common.check_smem(emu_lib, oracle, 60, seed=41)
-    common.check_smem(emu_lib, oracle, 30, seed=42, read_len=250)
-    common.check_smem(emu_lib, oracle, 40, seed=44, n_frac=0.02)
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(emu_lib, oracle, 60, seed=41, ref=common.SeedTally())
+    common.check_smem(emu_lib, oracle, 30, seed=42, read_len=250, ref=common.SeedTally())
+    common.check_smem(emu_lib, oracle, 40, seed=44, n_frac=0.02, ref=common.SeedTally())
+    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "700")      # some of each
     monkeypatch.setenv("SSG_SMEM_MAX_ROW", "18")       # ... and reads whose first row is longer than this
-    common.check_smem(emu_lib, oracle, 60, seed=41)
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(emu_lib, oracle, 60, seed=41, ref=common.SeedTally())
+    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "2147483647")   # no budget: the lane kernel alone, also on ambiguous bases and repeats
-    common.check_smem(emu_lib, oracle, 40, seed=44, n_frac=0.02)
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(emu_lib, oracle, 40, seed=44, n_frac=0.02, ref=common.SeedTally())
+    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
 
 
 def test_emu_smem_table_of_short_pattern_intervals(emu_lib, oracle, repeat_prefix, monkeypatch):
@@ -218,24 +218,24 @@ def test_emu_smem_table_of_short_pattern_intervals(emu_lib, oracle, repeat_prefi
     for k in ("2", "5", "11", "0", "25"):              # 25: capped by what the index is worth (log4 of the text + 2) and by min_seed_len - 1 in the kernel
         monkeypatch.setenv("SSG_KTAB_K", k)
         monkeypatch.setenv("SSG_KTAB_VERIFY", "1")
-        common.check_smem(emu_lib, oracle, 60, seed=51)
-        common.check_smem(emu_lib, oracle, 60, seed=52, n_frac=0.03)
+        common.check_smem(emu_lib, oracle, 60, seed=51, ref=common.SeedTally())
+        common.check_smem(emu_lib, oracle, 60, seed=52, n_frac=0.03, ref=common.SeedTally())
     monkeypatch.setenv("SSG_KTAB_K", "9")
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)
+    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())
     monkeypatch.setenv("SSG_SMEM_MAX_EXT", "300")
-    common.check_smem(emu_lib, oracle, 60, seed=53, n_frac=0.01)
+    common.check_smem(emu_lib, oracle, 60, seed=53, n_frac=0.01, ref=common.SeedTally())
     monkeypatch.delenv("SSG_SMEM_MAX_EXT")
-    common.check_smem(emu_lib, oracle, 60, seed=51)
+    common.check_smem(emu_lib, oracle, 60, seed=51, ref=common.SeedTally())
 
 
 def test_emu_smem_kernel_variants(emu_lib, oracle, repeat_prefix, monkeypatch):
     monkeypatch.setenv("SSG_SMEM_KERNEL", "lane")     # the nested-loop form (the product kernels' fall-back), on the same reads
-    common.check_smem(emu_lib, oracle, 150, seed=31)
+    common.check_smem(emu_lib, oracle, 150, seed=31, ref=common.SeedTally())
     monkeypatch.delenv("SSG_SMEM_KERNEL")
     monkeypatch.setenv("SSG_SA_INTV", "32")
     assert common.check_align1(emu_lib, oracle, 150, seed=33) > 150
     monkeypatch.delenv("SSG_SA_INTV")
-    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512)   # lists beyond 24 intervals: the wave form of the sort
+    common.check_smem(emu_lib, oracle, 8, seed=43, prefix=repeat_prefix, cap=512, ref=common.SeedTally())   # lists beyond 24 intervals: the wave form of the sort
 
 
 @pytest.mark.parametrize("read_len", [150, 250])
