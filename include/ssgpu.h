@@ -299,12 +299,22 @@ int ssg_coll_alltoallv(ssg_coll_t *c, const void *const *send, const uint64_t *s
 int ssg_coll_alltoall_u64(ssg_coll_t *c, const uint64_t *send, uint64_t *recv, int k);   /* k values to / from every rank */
 void ssg_coll_destroy(ssg_coll_t *c);
 
-/* ---- BGZF deflate on the device (row f1; htslib bgzf.c:298-342 is the format's writer in the reference) ----
- * Block b's payload is payload[cut[b] .. cut[b+1]) (<= 0xff00 bytes, as bgzf_write cuts them); its raw deflate stream (RFC 1951, one final
- * block; stored when it would not shrink) lands at out[out_off[b] .. out_off[b+1]).  The caller frames it: 18-byte BGZF header with the
- * block size, CRC-32 and ISIZE of the payload.  out_cap: bytes available at out (the sum of the payloads + 5 per block always suffices).
- * Host buffers; page-locked ones (ssg_host_alloc) travel at bus speed. */
+/* ---- BGZF on the device (row f1; htslib bgzf.c:298-342 is the format's writer in the reference) ----
+ * Block b's payload is payload[cut[b] .. cut[b+1]) (<= 0xff00 bytes, as bgzf_write cuts them); SSG_EINVAL for a larger one, SSG_EOVERFLOW when out_cap
+ * is too small (nothing is written behind out + out_cap), n_blocks <= 0: out_off[0] = 0 and nothing else.  Host buffers; page-locked ones
+ * (ssg_host_alloc) travel at bus speed.
+ * ssg_bgzf_deflate: the block's raw deflate stream (RFC 1951, one final block; stored when it would not shrink) lands at out[out_off[b] .. out_off[b+1]),
+ * for a caller that frames it itself.  out_cap: the sum of the payloads + 5 per block always suffices. */
 int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off);
+/* ssg_bgzf_compress: ssg_bgzf_deflate plus framing (bgzf.c:298-342): out[out_off[b] .. out_off[b+1]) is the complete BGZF member of block b -- the 18-byte
+ * header with BSIZE, the same deflate stream, CRC-32 and ISIZE of the payload, all made on the device; concatenated they are a BGZF file's body.  A block
+ * without payload becomes the 28-byte end-of-file marker: a caller ends a file by appending one.  crc (may be NULL) receives the payloads' CRC-32. */
+int ssg_bgzf_compress(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc);
+/* an out_cap that always suffices for ssg_bgzf_compress: payload + 31 per block (5 of the stored form, 26 of header and trailer; bgzf.c:298-342) */
+uint64_t ssg_bgzf_bound(uint64_t payload_bytes, long n_blocks);
+/* CRC-32 (zlib's, the one of a BGZF member's trailer, bgzf.c:298-342) of n byte ranges data[cut[i] .. cut[i+1]) of any length, on the device; host buffers.
+ * One wavefront per range: made for many ranges of BGZF-block size; a single range of many megabytes keeps one wavefront of the device busy. */
+int ssg_crc32_batch(const uint8_t *data, const uint64_t *cut, long n, uint32_t *crc);
 void *ssg_host_alloc(size_t n);
 void ssg_host_free(void *p);
 

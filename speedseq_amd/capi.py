@@ -342,6 +342,41 @@ def prof_get(lib, cap=64):
     return out
 
 
+def _bytes_u8(data):
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+
+
+def crc32_batch(lib, data, cut):
+    """ssg_crc32_batch: zlib's CRC-32 of the byte ranges data[cut[i] .. cut[i+1]) (any length each), computed on the device."""
+    data = _bytes_u8(data)
+    cut = np.ascontiguousarray(cut, dtype=np.uint64)
+    n = len(cut) - 1
+    crc = np.zeros(max(n, 0), dtype=np.uint32)
+    lib._chk(lib.l.ssg_crc32_batch(_ptr(data) if data.size else None, _ptr(cut), C.c_long(n), _ptr(crc)))
+    return crc
+
+
+def bgzf_bound(lib, payload_bytes, n_blocks):
+    """ssg_bgzf_bound: an output capacity that always suffices for bgzf_compress (payload + 31 per block)."""
+    lib.l.ssg_bgzf_bound.restype = C.c_uint64
+    return int(lib.l.ssg_bgzf_bound(C.c_uint64(payload_bytes), C.c_long(n_blocks)))
+
+
+def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None):
+    """ssg_bgzf_compress: the blocks payload[cut[b] .. cut[b+1]) (<= 0xff00 bytes each) as complete BGZF members, deflated, checksummed and framed on
+    the device.  Returns (out, out_off, crc): member b is out[out_off[b]:out_off[b+1]], out[:out_off[-1]] a BGZF file's body; crc is None unless wanted."""
+    payload = _bytes_u8(payload)
+    cut = np.ascontiguousarray(cut, dtype=np.uint64)
+    n = len(cut) - 1
+    cap = bgzf_bound(lib, int(cut[-1] - cut[0]) if n > 0 else 0, n) if out_cap is None else int(out_cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+    crc = np.zeros(max(n, 1), dtype=np.uint32) if want_crc else None
+    lib._chk(lib.l.ssg_bgzf_compress(_ptr(payload) if payload.size else None, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off),
+                                     _ptr(crc) if want_crc else None))
+    return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

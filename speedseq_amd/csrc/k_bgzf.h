@@ -15,7 +15,7 @@
  *      (always terminates, always a complete code -- zlib's inflate rejects incomplete ones).  At least two codes per alphabet, as zlib.
  *   3. every lane sizes its symbols, a prefix sum places them, and the lanes write their bits side by side (LSB-first; full words by plain
  *      stores, the word shared with a neighbour by atomic OR into the zeroed output).  A block that does not shrink is stored.
- * Output per block: the raw deflate stream (the caller adds the 18-byte BGZF header, CRC-32 and ISIZE).  Not byte-identical to zlib's
+ * Output per block: the raw deflate stream (the 18-byte BGZF header, CRC-32 and ISIZE: k_bgzf_frame.h, or the caller).  Not byte-identical to zlib's
  * output -- no two deflate implementations are -- but any inflate gives back the payload; tests inflate every block with zlib.
  */
 #ifndef SSG_K_BGZF_H

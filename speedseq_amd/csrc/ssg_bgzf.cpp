@@ -1,6 +1,7 @@
 /*
  * ssg_bgzf.cpp -- BGZF deflate on the device (k_bgzf.h): the host entry point of `sambamba sort`'s last
- * step.  A translation unit of its own (seconds to compile, variants by `make variant VUNITS=ssg_bgzf`).
+ * step.  A translation unit of its own (seconds to compile, variants by `make variant VUNITS=ssg_bgzf`).  ssg_bgzf_compress returns complete BGZF
+ * members: the same deflate kernel, then the CRC-32 and framing kernels of ssg_bgzf_frame.cpp (k_bgzf_frame.h).
  */
 #include <algorithm>
 #include <vector>
@@ -18,18 +19,19 @@ extern "C" {
 void *ssg_host_alloc(size_t n) { return rt_host_alloc(n); }
 void ssg_host_free(void *p) { rt_host_free(p); }
 
-int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off)
+/* the blocks' deflate streams (frame = false: ssg_bgzf_deflate), or their complete members with the payloads' CRC-32 (frame = true: ssg_bgzf_compress) */
+static int bgzf_run(const char *who, const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc, bool frame)
 {
 	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
 	out_off[0] = 0;
 	if (n_blocks <= 0) return 0;
-	for (long b = 0; b < n_blocks; ++b) if (cut[b + 1] < cut[b] || cut[b + 1] - cut[b] > BZ_MAX_PAYLOAD) { ssg_err_msg = "ssg_bgzf_deflate: a block's payload exceeds 0xff00 bytes"; return SSG_EINVAL; }
+	for (long b = 0; b < n_blocks; ++b) if (cut[b + 1] < cut[b] || cut[b + 1] - cut[b] > BZ_MAX_PAYLOAD) { ssg_err_msg = std::string(who) + ": a block's payload exceeds 0xff00 bytes"; return SSG_EINVAL; }
 	const long BB = 4096;   /* blocks per device call: 256 MB of temporary output, 1 GB of symbol lists */
 	const long nbmax = std::min(BB, n_blocks);
-	dbuf<uint8_t> d_pay((size_t)nbmax * BZ_MAX_PAYLOAD + 8), d_tmp((size_t)nbmax * BZ_OUT_STRIDE), d_dense((size_t)nbmax * BZ_OUT_STRIDE);
-	dbuf<uint32_t> d_sym((size_t)nbmax * BZ_STRETCH_CAP * 64), d_size(nbmax);
+	dbuf<uint8_t> d_pay((size_t)nbmax * BZ_MAX_PAYLOAD + 8), d_tmp((size_t)nbmax * BZ_OUT_STRIDE), d_dense((size_t)nbmax * BZ_OUT_STRIDE);   /* (a member is at most 0xff00 + 5 + 26 bytes) */
+	dbuf<uint32_t> d_sym((size_t)nbmax * BZ_STRETCH_CAP * 64), d_size(nbmax), d_crc(frame ? nbmax : 1);
 	dbuf<uint64_t> d_cut(nbmax + 1), d_off(nbmax + 1);
-	if (!d_pay.ok() || !d_tmp.ok() || !d_dense.ok() || !d_sym.ok() || !d_size.ok() || !d_cut.ok() || !d_off.ok()) { ssg_err_msg = "device allocation failed: BGZF deflate"; return SSG_ENOMEM; }
+	if (!d_pay.ok() || !d_tmp.ok() || !d_dense.ok() || !d_sym.ok() || !d_size.ok() || !d_crc.ok() || !d_cut.ok() || !d_off.ok()) { ssg_err_msg = "device allocation failed: BGZF deflate"; return SSG_ENOMEM; }
 	std::vector<uint64_t> rel((size_t)nbmax + 1), off((size_t)nbmax + 1); std::vector<uint32_t> sz((size_t)nbmax);
 	for (long b0 = 0; b0 < n_blocks; b0 += BB) {
 		const long nb = std::min(BB, n_blocks - b0);
@@ -37,17 +39,31 @@ int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks,
 		for (long k = 0; k <= nb; ++k) rel[(size_t)k] = cut[b0 + k] - base;
 		CHK(rt_h2d(d_pay.p, payload + base, bytes)); CHK(d_cut.up(rel.data(), (size_t)nb + 1));
 		SSG_LAUNCH(ssg_k_bgzf_deflate, nb, 64, 0, (const uint8_t*)d_pay.p, (const uint64_t*)d_cut.p, (int)nb, d_tmp.p, d_sym.p, d_size.p);
+		if (frame) CHK(ssg_crc32_ranges_dev(d_pay.p, d_cut.p, nb, d_crc.p));   /* the payload is in HBM for the deflate: its checksum is one more read of it */
 		CHK(rt_sync());
 		CHK(d_size.down(sz.data(), (size_t)nb));
-		off[0] = 0; for (long k = 0; k < nb; ++k) off[(size_t)k + 1] = off[(size_t)k] + sz[(size_t)k];
-		if (out_off[b0] + off[(size_t)nb] > out_cap) { ssg_err_msg = "ssg_bgzf_deflate: output buffer too small"; return SSG_EOVERFLOW; }
+		/* a member: 18 bytes of header, the stream, CRC-32 and ISIZE; without payload the 28-byte end-of-file marker (the stream `03 00', k_bgzf_frame.h) */
+		off[0] = 0; for (long k = 0; k < nb; ++k) off[(size_t)k + 1] = off[(size_t)k] + (!frame ? sz[(size_t)k] : rel[(size_t)k + 1] == rel[(size_t)k] ? 28u : 26u + sz[(size_t)k]);
+		if (out_off[b0] + off[(size_t)nb] > out_cap) { ssg_err_msg = std::string(who) + ": output buffer too small"; return SSG_EOVERFLOW; }
 		CHK(d_off.up(off.data(), (size_t)nb + 1));
-		SSG_LAUNCH(ssg_k_bgzf_compact, nb, 256, 0, (const uint8_t*)d_tmp.p, (const uint64_t*)d_off.p, (int)nb, d_dense.p);
+		if (frame) CHK(ssg_bgzf_frame_dev(d_tmp.p, BZ_OUT_STRIDE, d_cut.p, d_off.p, d_crc.p, nb, d_dense.p));
+		else SSG_LAUNCH(ssg_k_bgzf_compact, nb, 256, 0, (const uint8_t*)d_tmp.p, (const uint64_t*)d_off.p, (int)nb, d_dense.p);
 		CHK(rt_sync());
 		CHK(rt_d2h(out + out_off[b0], d_dense.p, off[(size_t)nb]));
+		if (frame && crc) CHK(d_crc.down(crc + b0, (size_t)nb));
 		for (long k = 0; k < nb; ++k) out_off[b0 + k + 1] = out_off[b0] + off[(size_t)k + 1];
 	}
 	return 0;
+}
+
+int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off)
+{
+	return bgzf_run("ssg_bgzf_deflate", payload, cut, n_blocks, out, out_cap, out_off, 0, false);
+}
+
+int ssg_bgzf_compress(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc)
+{
+	return bgzf_run("ssg_bgzf_compress", payload, cut, n_blocks, out, out_cap, out_off, crc, true);
 }
 
 } /* extern "C" */

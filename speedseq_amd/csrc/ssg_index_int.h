@@ -35,6 +35,9 @@ extern "C" int ssg_index_build_ktab(ssg_index *ix);
 extern "C" int ssg_seed_smem2(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, int cap,
                               ssg_intv_t *d_intv, int32_t *d_n, unsigned long long *n_extend, unsigned int max_ext, uint32_t *d_n_ext_read);
 extern "C" int ssg_sa_verify(const ssg_index *ix, int new_intv, const uint64_t *d_sa_new, long n_new);
+/* ssg_bgzf_frame.cpp: the launchers of the CRC-32 and framing kernels (k_bgzf_frame.h), queued on the calling thread's stream; device buffers */
+extern "C" int ssg_crc32_ranges_dev(const uint8_t *d_data, const uint64_t *d_cut, long n, uint32_t *d_crc);
+extern "C" int ssg_bgzf_frame_dev(const uint8_t *d_tmp, uint32_t tmp_stride, const uint64_t *d_cut, const uint64_t *d_moff, const uint32_t *d_crc, long n_blocks, uint8_t *d_dense);
 
 /* Layout fingerprint of the declarations the translation units of libssgpu share (and that kernels take by value).  Every unit defines
  * one with SSG_ABI_FP_DEFINE(<unit>); ssg_abi_selfcheck() (ssgpu_core.cpp, run before the first index is made) compares them and refuses

@@ -272,6 +272,9 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	/* blocks deflated on the device: the final file of a sort at a compressing level, when there is a device (SSG_BGZF_DEVICE=0 keeps zlib on the
 	 * host's threads; the host emulation of the kernels only does it on request, it is slow) */
 	const char *const bd = getenv("SSG_BGZF_DEVICE");
+	/* ... and the device checksums and frames them too (ssg_bgzf_compress: the payload is in HBM for the deflate anyway), so that the producers' host threads only gather.
+	 * SSG_BGZF_DEVICE_CRC=0: CRC-32 by the gather threads (zlib) and framing on the host around ssg_bgzf_deflate's streams -- the same file, byte for byte (A/B runs, tests) */
+	const char *const bdc = getenv("SSG_BGZF_DEVICE_CRC"); const bool dev_crc = !(bdc && !strcmp(bdc, "0"));
 	/* a run's blocks by the host's zlib pool (level 1), the device left to `bwa mem', where the host has the cores for it (32 usable ones): at 200 M pairs behind a 16-core
 	 * quota both ways end at 0.95-0.97 M pairs/s -- the device way slows bwa's kernels, the host way starves its threads (profiles/r06_soak_200M*.json).  SSG_SORT_RUN_DEVICE=0 / 1 decides. */
 	const char *const rde = getenv("SSG_SORT_RUN_DEVICE");
@@ -339,10 +342,10 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 		}
 		us_gather += my_g; us_deflate += my_d; us_window += my_w;
 	};
-	/* ... or the blocks are deflated on the device (ssg_bgzf_deflate, k_bgzf.h): a few producer threads, each with a stream of its own, take
-	 * batches of 2048 blocks in turn -- gather into page-locked memory + CRC-32 by host threads, deflate on the GPU, framing (BGZF header,
-	 * CRC, ISIZE) -- and hand the groups to the same in-order writer.  The host's cores, which the deflate of a whole genome's records kept busy
-	 * for longer than the alignment took, only copy and checksum. */
+	/* ... or the blocks are made on the device (ssg_bgzf_compress; k_bgzf.h, k_bgzf_frame.h): a few producer threads, each with a stream of its own, take
+	 * batches of 2048 blocks in turn -- gather into page-locked memory by host threads; deflate, CRC-32 and framing (BGZF header, CRC, ISIZE) on the
+	 * GPU -- and hand the groups to the same in-order writer.  The host's cores, which the deflate of a whole genome's records kept busy
+	 * for longer than the alignment took, only copy (with SSG_BGZF_DEVICE_CRC=0 they checksum and frame as well, around ssg_bgzf_deflate). */
 	std::atomic<long> dev_batches(0); const long fail_after = getenv("SSG_BGZF_FAIL_AFTER") ? atol(getenv("SSG_BGZF_FAIL_AFTER")) : -1;   /* tests: the device "fails" from its n-th batch on */
 	auto producer = [&](int t) {
 		if (ssg_set_device(t % n_devs) || ssg_set_lane(1 + (t / n_devs) % 7)) { dev_failed = 1; return; }
@@ -352,7 +355,8 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 		struct slot_t { uint8_t *P; std::vector<uint64_t> rel; std::vector<uint32_t> crc; size_t b0, n_b; std::atomic<int> state; slot_t() : P(0), b0(0), n_b(0), state(0) {} };   /* state: 0 free, 1 gathered, 2 no more batches */
 		slot_t slot[2];
 		for (slot_t &sl : slot) { sl.P = (uint8_t*)ssg_host_alloc(DEV_BATCH * BGZF_MAX_PAYLOAD + 64); sl.rel.resize(DEV_BATCH + 1); sl.crc.resize(DEV_BATCH); }
-		uint8_t *O = (uint8_t*)ssg_host_alloc(DEV_BATCH * (BGZF_MAX_PAYLOAD + 5) + 64);
+		const uint64_t O_cap = (uint64_t)DEV_BATCH * (BGZF_MAX_PAYLOAD + 31) + 64;   /* ssg_bgzf_bound: 5 of a stored block, 26 of the framing */
+		uint8_t *O = (uint8_t*)ssg_host_alloc(O_cap);
 		std::vector<uint64_t> off(DEV_BATCH + 1);
 		std::atomic<long> my_g(0); long my_d = 0; std::atomic<long> my_w(0);
 		const bool mem_ok = slot[0].P && slot[1].P && O;
@@ -367,7 +371,7 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 				const double t0 = wall();
 				for (size_t i = 0; i <= n_b; ++i) sl.rel[i] = cut[b0 + i] - cut[b0];
 				parallel_for((int)std::min<size_t>((size_t)gth, n_b / 8 + 1), n_b, [&](size_t a, size_t e, int) {
-					for (size_t i = a; i < e; ++i) { const size_t w = gather_block(b0 + i, sl.P + sl.rel[i]); sl.crc[i] = (uint32_t)crc32(crc32(0L, Z_NULL, 0), sl.P + sl.rel[i], (uInt)w); }
+					for (size_t i = a; i < e; ++i) { const size_t w = gather_block(b0 + i, sl.P + sl.rel[i]); if (!dev_crc) sl.crc[i] = (uint32_t)crc32(crc32(0L, Z_NULL, 0), sl.P + sl.rel[i], (uInt)w); }
 				});
 				my_g += (long)((wall() - t0) * 1e6);
 				sl.b0 = b0; sl.n_b = n_b;
@@ -387,14 +391,18 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 			if (st != 1) break;
 			const size_t b0 = sl.b0, n_b = sl.n_b, b1 = b0 + n_b, g0 = b0 / GRP, g1 = (b1 + GRP - 1) / GRP;
 			const double t1 = wall();
-			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || ssg_bgzf_deflate(sl.P, sl.rel.data(), (long)n_b, O, (uint64_t)DEV_BATCH * (BGZF_MAX_PAYLOAD + 5) + 64, off.data())) {
+			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || (dev_crc ? ssg_bgzf_compress(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data(), 0) : ssg_bgzf_deflate(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data()))) {
 				fprintf(stderr, "[sambamba] sort: BGZF deflate on the device failed: %s\n", fail_after >= 0 ? "(SSG_BGZF_FAIL_AFTER: test)" : ssg_last_error()); dev_failed = 1; break; }
 			const double t2 = wall();
 			parallel_for((int)std::min<size_t>((size_t)std::min(gth, 8), g1 - g0), g1 - g0, [&](size_t a, size_t e, int) {
 				static const uint8_t hdr[16] = { 0x1f,0x8b,0x08,0x04,0,0,0,0,0,0xff,0x06,0,0x42,0x43,0x02,0 };
 				for (size_t g = g0 + a; g < g0 + e; ++g) {
 					std::vector<uint8_t> ob; std::vector<uint32_t> bsz;
-					for (size_t bk = g * GRP; bk < std::min(nb, (g + 1) * GRP); ++bk) {
+					if (dev_crc) {   /* the members arrive framed: a group is one stretch of them */
+						const size_t i0 = g * GRP - b0, i1 = std::min(nb, (g + 1) * GRP) - b0;
+						ob.assign(O + off[i0], O + off[i1]);
+						for (size_t i = i0; i < i1; ++i) bsz.push_back((uint32_t)(off[i + 1] - off[i]));
+					} else for (size_t bk = g * GRP; bk < std::min(nb, (g + 1) * GRP); ++bk) {
 						const size_t i = bk - b0, clen = (size_t)(off[i + 1] - off[i]), bsize = 18 + clen + 8, at = ob.size();
 						ob.resize(at + bsize);
 						uint8_t *d = ob.data() + at;
@@ -495,7 +503,8 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	if (dbg() && !seg) fprintf(stderr, "[sambamba] sort: write: offsets and block cuts %.2f s, gather + deflate + write of %zu blocks %.2f s (record view for the index %.2f s, %d workers started in %.2f s; writer: waited %.2f s for blocks, wrote for %.2f s; "
 	                   "per worker: gather %.2f s, deflate %.2f s, held back by the writer's window %.2f s)\n", tw1 - tw0, nb, tw2 - tw1, tw_spawn0 - tw1, n_workers, tw_spawn - tw_spawn0, t_wr_wait, t_wr_io,
 	                   us_gather / 1e6 / std::max(1, n_workers + n_prod), us_deflate / 1e6 / std::max(1, n_workers + n_prod), us_window / 1e6 / std::max(1, n_workers + n_prod));
-	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; `gather' = gather + CRC-32 on the host, `deflate' = upload + kernels + download)%s\n", n_devs, n_prod,
+	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; %s)%s\n", n_devs, n_prod,
+	                                    dev_crc ? "`gather' = gather on the host, `deflate' = upload + kernels + download: CRC-32 on the device, framing too" : "`gather' = gather + CRC-32 on the host, `deflate' = upload + kernels + download, then framing on the host",
 	                                    host_slots ? (std::string("; ") + std::to_string(host_slots) + " of every " + std::to_string(slot_round) + " batches by the host's pool (zlib)").c_str() : "");
 	if (seg) seg->coff = coff;
 	if (seg && seg->ent_fd >= 0 && n) {   /* rank mode: what the index of the joined file needs of this stretch */

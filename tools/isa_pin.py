@@ -8,7 +8,11 @@ statement on the MI355X).  A kernel whose code differs from the pin -- because i
 translation unit did: adding a kernel re-schedules its neighbours -- has not been on a GPU yet; the test says so.  The GPU scripts
 (tools/gpu_r*.sh) write the new pin themselves after the suite and the parity gate are green (`--write --golden gpurun_out/...`), and the file is
 copied into tests/golden/ with the commit that ships those kernels.
-usage: isa_pin.py [--write] [--golden FILE] [--lib speedseq_amd/libssgpu.so]"""
+Kernels that a later change adds are pinned in a file of their own next to it (tests/golden/kernel_isa_<what>.sha256, written with --write-new
+once the suite is green on the GPU): the first file stays as it is, line for line, and every file is read.  A kernel may be pinned once;
+--write renews every file in place -- a kernel stays in the file that lists it, one that no file lists goes to kernel_isa.sha256.
+usage: isa_pin.py [--write] [--write-new FILE] [--golden FILE] [--lib speedseq_amd/libssgpu.so]"""
+import glob
 import hashlib
 import os
 import re
@@ -74,19 +78,47 @@ def current(lib):
     return res
 
 
+def read_pins(path):
+    return dict((l.split("  ", 1)[1].strip(), l.split("  ", 1)[0]) for l in open(path) if l.strip())
+
+
 def main():
     lib = os.path.join(ROOT, "speedseq_amd", "libssgpu.so")
     if "--lib" in sys.argv:
         lib = sys.argv[sys.argv.index("--lib") + 1]
     h = current(lib)
     golden = sys.argv[sys.argv.index("--golden") + 1] if "--golden" in sys.argv else GOLDEN   # the GPU scripts write the pin themselves once the suite and the parity gate are green
-    if "--write" in sys.argv:
+    extras = sorted(glob.glob(os.path.join(os.path.dirname(GOLDEN), "kernel_isa_*.sha256"))) if golden == GOLDEN else []
+    if "--write" in sys.argv:                                            # a kernel stays in the file that pins it; one no file knows goes to `golden'
+        elsewhere = set()
+        for extra in extras:
+            keep = sorted(k for k in read_pins(extra) if k in h and k not in elsewhere)
+            elsewhere.update(keep)
+            with open(extra, "w") as f:
+                for k in keep:
+                    f.write("%s  %s\n" % (h[k], k))
         with open(golden, "w") as f:
             for k in sorted(h):
-                f.write("%s  %s\n" % (h[k], k))
+                if k not in elsewhere:
+                    f.write("%s  %s\n" % (h[k], k))
         print("pinned %d kernels" % len(h))
         return 0
-    want = dict((l.split("  ", 1)[1].strip(), l.split("  ", 1)[0]) for l in open(golden) if l.strip())
+    want = read_pins(golden)
+    if "--write-new" in sys.argv:                                        # the kernels the pin does not know, into a file of their own
+        new = sorted(k for k in h if k not in want)
+        with open(sys.argv[sys.argv.index("--write-new") + 1], "w") as f:
+            for k in new:
+                f.write("%s  %s\n" % (h[k], k))
+        print("pinned %d new kernels" % len(new))
+        return 0
+    if golden == GOLDEN:                                                 # ... and those files are part of the pin
+        for extra in extras:
+            more = read_pins(extra)
+            twice = sorted(k for k in more if k in want)
+            if twice:
+                print("PINNED TWICE (%s)" % os.path.basename(extra), twice[0][:150])
+                return 1
+            want.update(more)
     bad = [k for k in want if h.get(k) != want[k]]
     new = [k for k in h if k not in want]
     for k in bad:
