@@ -315,6 +315,27 @@ uint64_t ssg_bgzf_bound(uint64_t payload_bytes, long n_blocks);
 /* CRC-32 (zlib's, the one of a BGZF member's trailer, bgzf.c:298-342) of n byte ranges data[cut[i] .. cut[i+1]) of any length, on the device; host buffers.
  * One wavefront per range: made for many ranges of BGZF-block size; a single range of many megabytes keeps one wavefront of the device busy. */
 int ssg_crc32_batch(const uint8_t *data, const uint64_t *cut, long n, uint32_t *crc);
+/* ---- the records of a sort in HBM, and their sorted stream gathered there (row f1; stands for bgzf_write's copy of a record into the block buffer, htslib
+ * bgzf.c) ----
+ * A device mirror of the chunks `sambamba sort` holds its input in.  A record's location is (chunk << 40 | offset of its block_size word), the encoding the sort
+ * keeps.  All entry points: SSG_ENODEV without a device; SSG_EINVAL from a thread that drives another device than the store's.
+ * ssg_recs_create: a store on the calling thread's device that will hold at most cap_bytes of chunks; nothing is allocated yet.
+ * ssg_recs_append: uploads one chunk (a device allocation of its own) and returns its id; SSG_ENOMEM when the sum of the chunks would pass cap_bytes or the
+ *   device has no room -- the store is unchanged and usable.  One thread appends.
+ * ssg_recs_order: declares the sorted stream: record i lies at loc[i] and occupies bytes cum[i] .. cum[i+1] of it (cum[0] = 0, non-decreasing; n >= 0).  Every
+ *   location and length is checked against the chunks here (SSG_EINVAL with the record in ssg_last_error()): the kernel has no bounds of its own.  Afterwards
+ *   the store is read-only; ssg_recs_gather and ssg_bgzf_compress_recs may be called from several threads at once, each on a lane of its own (ssg_set_lane).
+ * ssg_recs_gather: stream bytes v0 .. v1 into a host buffer: the kernel with nothing around it (tests, debugging).  SSG_EINVAL for v0 > v1 or v1 > cum[n];
+ *   v0 == v1 writes nothing.
+ * ssg_bgzf_compress_recs: ssg_bgzf_compress of the stream bytes cut[0] .. cut[n_blocks] (cut[]: absolute stream offsets) without the payload ever being in host
+ *   memory: the same members, byte for byte, the same errors. */
+typedef struct ssg_recs ssg_recs_t;
+int ssg_recs_create(uint64_t cap_bytes, ssg_recs_t **out);
+int ssg_recs_append(ssg_recs_t *r, const uint8_t *bytes, uint64_t len, uint32_t *chunk_id);
+int ssg_recs_order(ssg_recs_t *r, const uint64_t *loc, const uint64_t *cum, int64_t n);
+int ssg_recs_gather(ssg_recs_t *r, uint64_t v0, uint64_t v1, uint8_t *out);
+int ssg_bgzf_compress_recs(ssg_recs_t *r, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc);
+void ssg_recs_free(ssg_recs_t *r);
 void *ssg_host_alloc(size_t n);
 void ssg_host_free(void *p);
 

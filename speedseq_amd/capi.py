@@ -377,6 +377,66 @@ def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None):
     return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
 
 
+class Recs:
+    """A device-resident record store (ssg_recs_*): freed with the object or by close()."""
+
+    def __init__(self, lib, h):
+        self.lib, self.h = lib, h
+
+    def close(self):
+        if self.h is not None:
+            self.lib.l.ssg_recs_free.argtypes = [C.c_void_p]
+            self.lib.l.ssg_recs_free.restype = None
+            self.lib.l.ssg_recs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def recs_create(lib, cap_bytes):
+    """ssg_recs_create: a store on the calling thread's device for at most cap_bytes of chunks."""
+    h = C.c_void_p()
+    lib._chk(lib.l.ssg_recs_create(C.c_uint64(cap_bytes), C.byref(h)))
+    return Recs(lib, h)
+
+
+def recs_append(lib, recs, data):
+    """ssg_recs_append: uploads one chunk of whole records; returns its id (the upper 24 bits of its records' locations)."""
+    data = _bytes_u8(data)
+    cid = C.c_uint32()
+    lib._chk(lib.l.ssg_recs_append(recs.h, _ptr(data) if data.size else None, C.c_uint64(data.size), C.byref(cid)))
+    return int(cid.value)
+
+
+def recs_order(lib, recs, loc, cum):
+    """ssg_recs_order: record i of the sorted stream lies at loc[i] = chunk << 40 | offset and occupies stream bytes cum[i] .. cum[i+1]."""
+    loc = np.ascontiguousarray(loc, dtype=np.uint64)
+    cum = np.ascontiguousarray(cum, dtype=np.uint64)
+    assert len(cum) == len(loc) + 1
+    lib._chk(lib.l.ssg_recs_order(recs.h, _ptr(loc) if loc.size else None, _ptr(cum), C.c_int64(len(loc))))
+
+
+def recs_gather(lib, recs, v0, v1, out=None):
+    """ssg_recs_gather: stream bytes v0 .. v1, gathered on the device (into out[:v1 - v0] if given)."""
+    if out is None:
+        out = np.zeros(max(int(v1) - int(v0), 1), dtype=np.uint8)
+    lib._chk(lib.l.ssg_recs_gather(recs.h, C.c_uint64(v0), C.c_uint64(v1), _ptr(out)))
+    return out[:max(int(v1) - int(v0), 0)]
+
+
+def bgzf_compress_recs(lib, recs, cut, want_crc=True, out_cap=None):
+    """ssg_bgzf_compress_recs: bgzf_compress of the store's stream bytes cut[0] .. cut[-1] (absolute offsets), the payload gathered on the device."""
+    cut = np.ascontiguousarray(cut, dtype=np.uint64)
+    n = len(cut) - 1
+    cap = bgzf_bound(lib, int(cut[-1] - cut[0]) if n > 0 else 0, n) if out_cap is None else int(out_cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+    crc = np.zeros(max(n, 1), dtype=np.uint32) if want_crc else None
+    lib._chk(lib.l.ssg_bgzf_compress_recs(recs.h, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off), _ptr(crc) if want_crc else None))
+    return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

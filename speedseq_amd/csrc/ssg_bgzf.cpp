@@ -20,7 +20,8 @@ void *ssg_host_alloc(size_t n) { return rt_host_alloc(n); }
 void ssg_host_free(void *p) { rt_host_free(p); }
 
 /* the blocks' deflate streams (frame = false: ssg_bgzf_deflate), or their complete members with the payloads' CRC-32 (frame = true: ssg_bgzf_compress) */
-static int bgzf_run(const char *who, const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc, bool frame)
+/* the payload: a host buffer, or (recs != NULL; ssg_bgzf_compress_recs) the sorted stream of a device-resident record store, cut[] in absolute stream offsets */
+static int bgzf_run(const char *who, const uint8_t *payload, const ssg_recs_t *recs, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc, bool frame)
 {
 	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
 	out_off[0] = 0;
@@ -28,7 +29,7 @@ static int bgzf_run(const char *who, const uint8_t *payload, const uint64_t *cut
 	for (long b = 0; b < n_blocks; ++b) if (cut[b + 1] < cut[b] || cut[b + 1] - cut[b] > BZ_MAX_PAYLOAD) { ssg_err_msg = std::string(who) + ": a block's payload exceeds 0xff00 bytes"; return SSG_EINVAL; }
 	const long BB = 4096;   /* blocks per device call: 256 MB of temporary output, 1 GB of symbol lists */
 	const long nbmax = std::min(BB, n_blocks);
-	dbuf<uint8_t> d_pay((size_t)nbmax * BZ_MAX_PAYLOAD + 8), d_tmp((size_t)nbmax * BZ_OUT_STRIDE), d_dense((size_t)nbmax * BZ_OUT_STRIDE);   /* (a member is at most 0xff00 + 5 + 26 bytes) */
+	dbuf<uint8_t> d_pay((size_t)nbmax * BZ_MAX_PAYLOAD + 16), d_tmp((size_t)nbmax * BZ_OUT_STRIDE), d_dense((size_t)nbmax * BZ_OUT_STRIDE);   /* (a member is at most 0xff00 + 5 + 26 bytes) */
 	dbuf<uint32_t> d_sym((size_t)nbmax * BZ_STRETCH_CAP * 64), d_size(nbmax), d_crc(frame ? nbmax : 1);
 	dbuf<uint64_t> d_cut(nbmax + 1), d_off(nbmax + 1);
 	if (!d_pay.ok() || !d_tmp.ok() || !d_dense.ok() || !d_sym.ok() || !d_size.ok() || !d_crc.ok() || !d_cut.ok() || !d_off.ok()) { ssg_err_msg = "device allocation failed: BGZF deflate"; return SSG_ENOMEM; }
@@ -37,7 +38,9 @@ static int bgzf_run(const char *who, const uint8_t *payload, const uint64_t *cut
 		const long nb = std::min(BB, n_blocks - b0);
 		const uint64_t base = cut[b0], bytes = cut[b0 + nb] - base;
 		for (long k = 0; k <= nb; ++k) rel[(size_t)k] = cut[b0 + k] - base;
-		CHK(rt_h2d(d_pay.p, payload + base, bytes)); CHK(d_cut.up(rel.data(), (size_t)nb + 1));
+		if (recs) CHK(ssg_recs_gather_dev(recs, base, base + bytes, d_pay.p));   /* (the gather kernel's last store may be a whole 16-byte granule: d_pay's slack) */
+		else CHK(rt_h2d(d_pay.p, payload + base, bytes));
+		CHK(d_cut.up(rel.data(), (size_t)nb + 1));
 		SSG_LAUNCH(ssg_k_bgzf_deflate, nb, 64, 0, (const uint8_t*)d_pay.p, (const uint64_t*)d_cut.p, (int)nb, d_tmp.p, d_sym.p, d_size.p);
 		if (frame) CHK(ssg_crc32_ranges_dev(d_pay.p, d_cut.p, nb, d_crc.p));   /* the payload is in HBM for the deflate: its checksum is one more read of it */
 		CHK(rt_sync());
@@ -58,12 +61,18 @@ static int bgzf_run(const char *who, const uint8_t *payload, const uint64_t *cut
 
 int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off)
 {
-	return bgzf_run("ssg_bgzf_deflate", payload, cut, n_blocks, out, out_cap, out_off, 0, false);
+	return bgzf_run("ssg_bgzf_deflate", payload, 0, cut, n_blocks, out, out_cap, out_off, 0, false);
 }
 
 int ssg_bgzf_compress(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc)
 {
-	return bgzf_run("ssg_bgzf_compress", payload, cut, n_blocks, out, out_cap, out_off, crc, true);
+	return bgzf_run("ssg_bgzf_compress", payload, 0, cut, n_blocks, out, out_cap, out_off, crc, true);
+}
+
+int ssg_bgzf_compress_recs(ssg_recs_t *recs, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc)
+{
+	if (!recs && rt_device_count() >= 1) { ssg_err_msg = "ssg_bgzf_compress_recs: no record store"; return SSG_EINVAL; }
+	return bgzf_run("ssg_bgzf_compress_recs", 0, recs, cut, n_blocks, out, out_cap, out_off, crc, true);
 }
 
 } /* extern "C" */

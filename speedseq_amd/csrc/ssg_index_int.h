@@ -38,6 +38,10 @@ extern "C" int ssg_sa_verify(const ssg_index *ix, int new_intv, const uint64_t *
 /* ssg_bgzf_frame.cpp: the launchers of the CRC-32 and framing kernels (k_bgzf_frame.h), queued on the calling thread's stream; device buffers */
 extern "C" int ssg_crc32_ranges_dev(const uint8_t *d_data, const uint64_t *d_cut, long n, uint32_t *d_crc);
 extern "C" int ssg_bgzf_frame_dev(const uint8_t *d_tmp, uint32_t tmp_stride, const uint64_t *d_cut, const uint64_t *d_moff, const uint32_t *d_crc, long n_blocks, uint8_t *d_dense);
+/* ssg_rec_gather.cpp: the launcher of the gather kernel (k_rec_gather.h), queued on the calling thread's stream: bytes v0 .. v1 of the store's sorted stream to
+ * d_out[0 .. v1 - v0), a device buffer with room for v1 - v0 bytes rounded up to 16 */
+struct ssg_recs;
+extern "C" int ssg_recs_gather_dev(const ssg_recs *r, uint64_t v0, uint64_t v1, uint8_t *d_out);
 
 /* Layout fingerprint of the declarations the translation units of libssgpu share (and that kernels take by value).  Every unit defines
  * one with SSG_ABI_FP_DEFINE(<unit>); ssg_abi_selfcheck() (ssgpu_core.cpp, run before the first index is made) compares them and refuses

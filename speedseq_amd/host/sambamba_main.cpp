@@ -188,6 +188,71 @@ static void gpu_perm(const rec_store_t &S, std::vector<uint32_t> &perm)
 	if (ssg_sort_u64_perm(S.key.data(), (int64_t)S.key.size(), perm.data())) die(std::string("sort: ") + ssg_last_error());
 }
 
+/* SSG_SORT_DEVICE_GATHER=1: the records go to the device while they arrive, chunk by chunk as rec_store_t holds them (ssg_recs_append; chunk k of the store is chunk k
+ * there), so that write_sorted can have a kernel build each batch's payload in HBM (ssg_bgzf_compress_recs) where host threads copied record after record into a
+ * page-locked block.  An uploader thread with a lane of its own takes the chunks from a queue the input thread only appends to: it never waits for the bus.  The
+ * host copy stays -- the index thread reads it, and so does the host gather that takes over, with one log line, whenever this stops: the pool is full, an allocation
+ * or a copy fails, a run is spilled.  The file is the same either way. */
+struct dev_gather_t {
+	struct item_t { const uint8_t *p; size_t len; };
+	static const size_t QCAP = 1024;   /* chunks waiting for the bus (pointers: the chunks stay where they are) */
+	std::mutex mu; std::condition_variable cv; std::deque<item_t> q; bool closed;
+	std::thread th; std::atomic<int> failed; std::string why; bool on, said;
+	ssg_recs_t *recs; size_t n_chunks; uint64_t bytes;
+	dev_gather_t() : closed(false), failed(0), on(false), said(false), recs(0), n_chunks(0), bytes(0) {}
+	~dev_gather_t() { stop("the sort ended"); }
+	void fail(const std::string &w) { std::lock_guard<std::mutex> l(mu); if (!failed.load()) { why = w; failed = 1; } cv.notify_all(); }
+	static void say_off(const std::string &w) { if (dbg()) fprintf(stderr, "[sambamba] sort: device gather off (%s): the records are gathered on the host\n", w.c_str()); }
+	void start(uint64_t cap_bytes)
+	{
+		on = true;
+		th = std::thread([this, cap_bytes]() {
+			if (ssg_set_device(0) || ssg_set_lane(7) || ssg_recs_create(cap_bytes, &recs)) fail(ssg_last_error());
+			for (;;) {
+				item_t it;
+				{ std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return !q.empty() || closed; }); if (q.empty()) break; it = q.front(); q.pop_front(); }
+				if (failed.load()) continue;
+				uint32_t id = 0;
+				if (ssg_recs_append(recs, it.p, (uint64_t)it.len, &id)) fail(ssg_last_error());
+				else if (id != (uint32_t)n_chunks) fail("the device's chunk ids left the host's");
+				else { ++n_chunks; bytes += it.len; }
+			}
+			if (failed.load() && recs) { ssg_recs_free(recs); recs = 0; }
+		});
+	}
+	/* the input thread, for every chunk rec_store_t::add_chunk has accepted */
+	void push(const uint8_t *p, size_t len)
+	{
+		if (!on || failed.load()) return;
+		std::lock_guard<std::mutex> l(mu);
+		if (q.size() >= QCAP) { if (!failed.load()) { why = "the uploader fell " + std::to_string(QCAP) + " chunks behind the input"; failed = 1; } }
+		else { item_t it = { p, len }; q.push_back(it); }
+		cv.notify_all();
+	}
+	void join() { { std::lock_guard<std::mutex> l(mu); closed = true; cv.notify_all(); } if (th.joinable()) th.join(); }
+	/* before anything frees a chunk (a spill): the uploader is gone when this returns, and so is the store */
+	void stop(const char *reason)
+	{
+		if (!on) return;
+		fail(reason); join(); on = false;
+		if (recs) { ssg_recs_free(recs); recs = 0; }
+		if (!said && strcmp(reason, "the sort ended")) { said = true; say_off(why); }
+	}
+	/* the end of the input: the store with every chunk in it, or NULL */
+	ssg_recs_t *finish()
+	{
+		if (!on) return 0;
+		const double t0 = wall();
+		join(); on = false;
+		if (failed.load()) { if (!said) { said = true; say_off(why); } return 0; }
+		if (dbg()) fprintf(stderr, "[sambamba] sort: device gather: %zu chunks, %.2f GB of records on the device; waited %.2f s for the uploader at the end of the input\n", n_chunks, (double)bytes / 1e9, wall() - t0);
+		ssg_recs_t *r = recs; recs = 0;
+		return r;
+	}
+};
+/* the blocks of a final file are deflated on the device (write_sorted's rule, which SSG_BGZF_DEVICE=0 / 1 overrides) */
+static bool bgzf_device_wanted() { const char *const bd = getenv("SSG_BGZF_DEVICE"); return !(bd && !strcmp(bd, "0")) && (bd || strcmp(ssg_backend(), "emu") != 0) && ssg_device_count() > 0; }
+
 /* the sorted records as a BGZF stream.  Blocks are cut exactly as bgzf_out_t::record cuts them (a record does not straddle blocks
  * unless it is larger than one); the gather of a block's records and its deflate run on the thread pool, groups of blocks are
  * written in order by the calling thread while later groups are still being compressed. */
@@ -227,7 +292,7 @@ struct seg_out_t {
 	seg_out_t() : first(true), last(false), coff(0), idx_ok(true), no_index(false), hdr_end(0), ent_fd(-1), pending(false), p_tid(0), p_pos(0), p_end(0), p_mapped(false) {}
 };
 static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm, const bam_hdr_t &h, int fd, int level, int threads, const char *bai_path = 0,
-                         const std::vector<size_t> *force_at = 0, std::vector<uint64_t> *force_off = 0, seg_out_t *seg = 0, std::vector<uint64_t> *force_uoff = 0)
+                         const std::vector<size_t> *force_at = 0, std::vector<uint64_t> *force_off = 0, seg_out_t *seg = 0, std::vector<uint64_t> *force_uoff = 0, ssg_recs_t *recs = 0)
 {
 	const bool opens = !seg || seg->first, closes = !seg || seg->last;
 	if (!force_at && opens) { bgzf_out_t out(fd, level, threads); hdr_write(out, h); out.drain(true); }
@@ -280,10 +345,29 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	const char *const rde = getenv("SSG_SORT_RUN_DEVICE");
 	const bool run_on_host = force_at && (rde && *rde ? atoi(rde) == 0 : ssg_usable_cores() >= 32);
 	const bool use_dev = lvl != 0 && nb > 0 && !run_on_host && !(bd && !strcmp(bd, "0")) && (bd || strcmp(ssg_backend(), "emu") != 0) && ssg_device_count() > 0 && GRP * 2 <= 2048 && 2048 % GRP == 0;
+	/* ... and gathers them: recs holds the store's chunks in HBM (dev_gather_t: SSG_SORT_DEVICE_GATHER=1, the final in-memory write only); the sorted order goes up once --
+	 * a location and an offset per record -- and a producer's batch is one call without a payload (ssg_bgzf_compress_recs).  The host's CRC-32 has no payload to read. */
+	bool dev_gather = false;
+	if (recs) {
+		std::string why;
+		if (force_at || seg) why = "not the final in-memory write";
+		else if (!use_dev) why = nb ? "the blocks are not deflated on the device" : "no block to write";
+		else if (!dev_crc) why = "SSG_BGZF_DEVICE_CRC=0: the host has no payload to checksum";
+		else {
+			std::vector<uint64_t> sloc(n);
+			parallel_for((int)std::min<size_t>((size_t)std::max(1, threads), n / 65536 + 1), n, [&](size_t a, size_t b, int) { for (size_t i = a; i < b; ++i) sloc[i] = S.loc[perm[i]]; });
+			if (ssg_set_device(0) || ssg_recs_order(recs, sloc.data(), cum.data(), (int64_t)n)) why = ssg_last_error(); else dev_gather = true;
+		}
+		if (!dev_gather) dev_gather_t::say_off(why);
+	}
 	size_t DEV_BATCH = 2048; { const char *e = getenv("SSG_SORT_DEV_BATCH"); if (e && atol(e) >= (long)GRP && atol(e) <= 2048 && atol(e) % (long)GRP == 0) DEV_BATCH = (size_t)atol(e); }   /* tests: several producers on several devices for a small file */
 	/* every visible device deflates (SSG_SORT_DEVICES caps them): producer t works on device t mod n_dev, lane 1 + t / n_dev -- with one device three
 	 * producers on three lanes as before, with N devices at least two per device; the writer and the index thread do not care who made a block */
 	int n_devs = use_dev ? std::max(1, ssg_device_count()) : 1; { const char *e = getenv("SSG_SORT_DEVICES"); if (e && atoi(e) > 0) n_devs = std::min(n_devs, atoi(e)); }
+	if (dev_gather) {   /* every producer on the device that holds the records */
+		if (n_devs > 1 && dbg()) fprintf(stderr, "[sambamba] sort: write: %d devices visible, the records are on device 0: all producers run there\n", n_devs);
+		n_devs = 1;
+	}
 	/* (SSG_SORT_PRODUCERS overrides; six producers on the one device -- a producer gathers and checksums on the host OR deflates on the device, never both at once --
 	 * were slower than three on the 16-CPU host next to the MI355X: 1.33 vs 1.15 s for 5.1 GB, profiles/r06f_literal_sort_producers.json: the gather threads are the limit) */
 	int want_prod = std::min(3 * n_devs, std::max(3, 2 * n_devs)); { const char *e = getenv("SSG_SORT_PRODUCERS"); if (e && atoi(e) > 0) want_prod = std::min(7 * n_devs, atoi(e)); }
@@ -347,7 +431,40 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	 * GPU -- and hand the groups to the same in-order writer.  The host's cores, which the deflate of a whole genome's records kept busy
 	 * for longer than the alignment took, only copy (with SSG_BGZF_DEVICE_CRC=0 they checksum and frame as well, around ssg_bgzf_deflate). */
 	std::atomic<long> dev_batches(0); const long fail_after = getenv("SSG_BGZF_FAIL_AFTER") ? atol(getenv("SSG_BGZF_FAIL_AFTER")) : -1;   /* tests: the device "fails" from its n-th batch on */
+	/* device gather: no gatherer thread, no payload slots -- a batch is its cuts; only the output block remains */
+	auto producer_recs = [&](int t) {
+		if (ssg_set_device(0) || ssg_set_lane(1 + t % 7)) { dev_failed = 1; return; }
+		const int gth = std::max(1, threads / std::max(1, n_prod));
+		const uint64_t O_cap = (uint64_t)DEV_BATCH * (BGZF_MAX_PAYLOAD + 31) + 64;
+		uint8_t *O = (uint8_t*)ssg_host_alloc(O_cap);
+		std::vector<uint64_t> off(DEV_BATCH + 1);
+		long my_d = 0, my_w = 0;
+		for (size_t b0 = (size_t)t * DEV_BATCH; O && b0 < nb && !dev_failed.load(); b0 += (size_t)slot_round * DEV_BATCH) {
+			const size_t b1 = std::min(nb, b0 + DEV_BATCH), n_b = b1 - b0, g0 = b0 / GRP, g1 = (b1 + GRP - 1) / GRP;
+			if (g0 >= next_write.load(std::memory_order_acquire) + window) { const double t0 = wall(); while (g0 >= next_write.load(std::memory_order_acquire) + window && !dev_failed.load()) nap(200); my_w += (long)((wall() - t0) * 1e6); }
+			if (dev_failed.load()) break;
+			const double t1 = wall();
+			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || ssg_bgzf_compress_recs(recs, &cut[b0], (long)n_b, O, O_cap, off.data(), 0)) {
+				fprintf(stderr, "[sambamba] sort: BGZF deflate on the device failed: %s\n", fail_after >= 0 ? "(SSG_BGZF_FAIL_AFTER: test)" : ssg_last_error()); dev_failed = 1; break; }
+			const double t2 = wall();
+			parallel_for((int)std::min<size_t>((size_t)std::min(gth, 8), g1 - g0), g1 - g0, [&](size_t a, size_t e, int) {
+				for (size_t g = g0 + a; g < g0 + e; ++g) {   /* the members arrive framed: a group is one stretch of them */
+					std::vector<uint8_t> ob; std::vector<uint32_t> bsz;
+					const size_t i0 = g * GRP - b0, i1 = std::min(nb, (g + 1) * GRP) - b0;
+					ob.assign(O + off[i0], O + off[i1]);
+					for (size_t i = i0; i < i1; ++i) bsz.push_back((uint32_t)(off[i + 1] - off[i]));
+					grp[g].bytes.swap(ob); grp[g].bsz.swap(bsz);
+					done[g].store(1, std::memory_order_release);
+				}
+			});
+			my_d += (long)((t2 - t1) * 1e6);
+		}
+		if (!O) dev_failed = 1;
+		ssg_host_free(O);
+		us_deflate += my_d; us_window += my_w;
+	};
 	auto producer = [&](int t) {
+		if (dev_gather) { producer_recs(t); return; }
 		if (ssg_set_device(t % n_devs) || ssg_set_lane(1 + (t / n_devs) % 7)) { dev_failed = 1; return; }
 		const int gth = std::max(1, threads / std::max(1, n_prod));
 		/* two slots: a helper thread gathers and checksums batch k + 1 on the host while this one has batch k deflated on the device (until round 6 a producer did one
@@ -503,9 +620,11 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	if (dbg() && !seg) fprintf(stderr, "[sambamba] sort: write: offsets and block cuts %.2f s, gather + deflate + write of %zu blocks %.2f s (record view for the index %.2f s, %d workers started in %.2f s; writer: waited %.2f s for blocks, wrote for %.2f s; "
 	                   "per worker: gather %.2f s, deflate %.2f s, held back by the writer's window %.2f s)\n", tw1 - tw0, nb, tw2 - tw1, tw_spawn0 - tw1, n_workers, tw_spawn - tw_spawn0, t_wr_wait, t_wr_io,
 	                   us_gather / 1e6 / std::max(1, n_workers + n_prod), us_deflate / 1e6 / std::max(1, n_workers + n_prod), us_window / 1e6 / std::max(1, n_workers + n_prod));
-	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; %s)%s\n", n_devs, n_prod,
+	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; %s)%s%s\n", n_devs, n_prod,
+	                                    dev_gather ? "`gather' = nothing, `deflate' = gather, deflate, CRC-32 and framing kernels + download: the payload is built in HBM" :
 	                                    dev_crc ? "`gather' = gather on the host, `deflate' = upload + kernels + download: CRC-32 on the device, framing too" : "`gather' = gather + CRC-32 on the host, `deflate' = upload + kernels + download, then framing on the host",
-	                                    host_slots ? (std::string("; ") + std::to_string(host_slots) + " of every " + std::to_string(slot_round) + " batches by the host's pool (zlib)").c_str() : "");
+	                                    host_slots ? (std::string("; ") + std::to_string(host_slots) + " of every " + std::to_string(slot_round) + " batches by the host's pool (zlib)").c_str() : "",
+	                                    dev_gather ? "; gather on the device" : "; gather on the host");
 	if (seg) seg->coff = coff;
 	if (seg && seg->ent_fd >= 0 && n) {   /* rank mode: what the index of the joined file needs of this stretch */
 		std::vector<uint8_t> eb(24 * n); size_t bk = 0;
@@ -786,6 +905,18 @@ static int cmd_sort(int argc, char **argv)
 	uint64_t budget = (uint64_t)(std::max(mem_gb, 0.25) * 0.6 * 1073741824.0);   /* record bytes per in-memory run; the rest is keys, locations, output blocks */
 	{ const char *e = getenv("SSG_SORT_CHUNK_BYTES"); if (e && atoll(e) > 0) budget = (uint64_t)atoll(e); }   /* the tests force the spill-and-merge path */
 	rec_store_t S; std::vector<std::string> spills; bam_hdr_t h;
+	/* SSG_SORT_DEVICE_GATHER=1 (off by default): the records go to the device as they arrive and the final write gathers them there (dev_gather_t).  Only the single
+	 * pipeline's final in-memory write at a compressing level, deflated and checksummed on the device; spilled runs, the merge and rank mode gather on the host. */
+	dev_gather_t dg;
+	{	const char *e = getenv("SSG_SORT_DEVICE_GATHER");
+		if (e && *e && strcmp(e, "0")) {
+			const char *const bdc = getenv("SSG_BGZF_DEVICE_CRC");
+			const char *const why = world > 1 ? "rank mode" : level == 0 ? "level 0: nothing is deflated" : !bgzf_device_wanted() ? "the blocks are not deflated on the device"
+			                      : bdc && !strcmp(bdc, "0") ? "SSG_BGZF_DEVICE_CRC=0: the host has no payload to checksum" : 0;
+			uint64_t cap = budget; { const char *m = getenv("SSG_SORT_DEVICE_POOL_MB"); if (m && atoll(m) > 0) cap = (uint64_t)atoll(m) << 20; }   /* HBM for the records: the run's record budget */
+			if (why) dev_gather_t::say_off(why); else dg.start(cap);
+		}
+	}
 	/* the device is first needed when the last record has arrived: bring the runtime up now, next to the input, not then */
 	std::thread warm([]() { const uint64_t k[2] = { 1, 0 }; uint32_t pm[2]; (void)ssg_sort_u64_perm(k, 2, pm); });
 	struct joiner_t { std::thread &t; ~joiner_t() { if (t.joinable()) t.join(); } } warm_join = { warm };
@@ -830,9 +961,10 @@ static int cmd_sort(int argc, char **argv)
 		}
 		runs.push_back(R); spills.push_back(R.path); S.clear();
 	};
-	auto spill = [&]() { spill_wait(); spill_store(S); };
+	static const char *const dg_spill = "the records exceed the memory budget: sorted runs are spilled and merged";
+	auto spill = [&]() { dg.stop(dg_spill); spill_wait(); spill_store(S); };
 	const bool spill_bg = fused && world == 1 && !(getenv("SSG_SORT_SPILL_BG") && atoi(getenv("SSG_SORT_SPILL_BG")) == 0);
-	auto spill_async = [&]() { spill_wait(); std::swap(S, S_bg); t_spill = std::thread([&]() { spill_store(S_bg); }); };
+	auto spill_async = [&]() { dg.stop(dg_spill); spill_wait(); std::swap(S, S_bg); t_spill = std::thread([&]() { spill_store(S_bg); }); };
 	struct spill_join_t { std::thread &t; ~spill_join_t() { if (t.joinable()) t.join(); } } spill_join = { t_spill };
 	const uint64_t budget_in = spill_bg ? std::max<uint64_t>(budget / 2, 1) : budget;
 	if (fused) {
@@ -872,6 +1004,7 @@ static int cmd_sort(int argc, char **argv)
 				});
 			}
 			{ const double t0 = wall(); if (!S.add_chunk(std::move(F->p), (size_t)F->fh.len, world > 1 ? ((uint64_t)rank + n_main * (uint64_t)world) << 28 : ~(uint64_t)0)) { bad = "sort: malformed record frame"; break; } t_index += wall() - t0; }
+			dg.push(S.chunk.back().p, S.chunk_len.back());
 			++n_main;
 			if (S.bytes >= budget_in || S.key.size() >= 0xfffffff0u) { if (spill_bg) spill_async(); else spill(); }
 		}
@@ -887,10 +1020,11 @@ static int cmd_sort(int argc, char **argv)
 		bi.raw.assign((const uint8_t*)first, (const uint8_t*)first + n_first);
 		if (!hdr_read(bi, h)) die("sort: not a BAM file");
 		change_so(h.text, "coordinate");
-		const size_t CH = (size_t)std::min<uint64_t>((uint64_t)64 << 20, std::max<uint64_t>(budget / 4, 65536));   /* the budget is checked once per chunk */
+		size_t CH = (size_t)std::min<uint64_t>((uint64_t)64 << 20, std::max<uint64_t>(budget / 4, 65536));   /* the budget is checked once per chunk */
+		{ const char *e = getenv("SSG_SORT_IN_CHUNK_BYTES"); if (e && atoll(e) > 0) CH = (size_t)atoll(e); }   /* tests: a small file in several chunks, without a spill */
 		fu_buf_t cur; size_t cap = CH, len = 0;
 		if (!cur.heap(CH)) die("sort: out of memory");
-		auto flush = [&]() { if (!len) return; if (!S.add_chunk(std::move(cur), len)) die("sort: malformed BAM record"); cap = CH; len = 0; if (!cur.heap(CH)) die("sort: out of memory"); if (S.bytes >= budget || S.key.size() >= 0xfffffff0u) spill(); };
+		auto flush = [&]() { if (!len) return; if (!S.add_chunk(std::move(cur), len)) die("sort: malformed BAM record"); dg.push(S.chunk.back().p, S.chunk_len.back()); cap = CH; len = 0; if (!cur.heap(CH)) die("sort: out of memory"); if (S.bytes >= budget || S.key.size() >= 0xfffffff0u) spill(); };
 		for (;;) {
 			uint32_t bs;
 			if (bi.get(&bs, 4) != 4) break;
@@ -904,6 +1038,7 @@ static int cmd_sort(int argc, char **argv)
 		}
 		flush();
 	}
+	ssg_recs_t *const recs = dg.finish();   /* (NULL unless every chunk is on the device) */
 	const double t_in = wall();
 	ssg_stamp("sambamba_sort", "input_done");
 	bool bai_note = false;
@@ -1017,7 +1152,7 @@ static int cmd_sort(int argc, char **argv)
 		std::vector<uint32_t> perm; gpu_perm(S, perm);
 		const double t_perm = wall();
 		const std::string bai = outp + ".bai";
-		write_sorted(S, perm, h, ofd, level, pool, getenv("SSG_SORT_NO_BAI") ? 0 : bai.c_str());
+		write_sorted(S, perm, h, ofd, level, pool, getenv("SSG_SORT_NO_BAI") ? 0 : bai.c_str(), 0, 0, 0, 0, recs);   /* (the store goes with the process: hipFree of gigabytes waits for the device) */
 		bai_note = !getenv("SSG_SORT_NO_BAI");
 		if (dbg()) fprintf(stderr, "[sambamba] sort: %zu records, %.2f GB: input %.2f s (from start), device sort of the keys %.2f s, gather + deflate (level %d, %d threads) + write %.2f s\n",
 		                   S.key.size(), (double)S.bytes / 1e9, t_in - t_start, t_perm - t_in, level < 0 ? 6 : level, pool, wall() - t_perm);
