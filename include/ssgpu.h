@@ -122,6 +122,19 @@ int ssg_align2_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
  * once by one lane running the textbook loops (out_lane); the two must be equal word for word. */
 int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *out_wave);
 
+/* Test entries of the paired-end decision stage (rows a9, a11): the stage on region lists given by the caller instead of stage 1's, through the kernels and
+ * the host code of the pipeline itself -- the form that takes a pair (lane in LDS, lane on global memory, wave) is chosen as ssg_mem_process_pairs chooses it.
+ * reg_off[2 n_pairs + 1]: read r's regions are regs[reg_off[r] .. reg_off[r + 1]) (read 1 and read 2 of a pair interleaved).  The lists are validated first
+ * (monotone offsets, at most 4096 regions a read, 0 <= rid < contigs, 0 <= qb < qe <= 310, 0 <= rb < re <= 2 l_pac, scores >= 0): SSG_EINVAL otherwise.
+ *   ssg_dbg_pestat      mem_pestat per batch: pes receives n_batches x 4 entries.
+ *   ssg_dbg_pair_final  mem_mark_primary_se, mem_pair and mem_sam_pe's decision with one insert-size model pes[4] for all pairs: regs_out receives the lists as
+ *                       the stage leaves them (sorted, marked), req_off[2 n_pairs + 1] and *req (malloc'd, release with ssg_free) the requests per read,
+ *                       req[].reg counted in the caller's layout.  SSG_EOVERFLOW as from the pipeline when a pair exceeds an on-device capacity. */
+int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                   const int32_t *pair_batch, int n_batches, ssg_pestat_t *pes);
+int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                       const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req);
+
 /* upstream mem_align1_core() (bwamem.c; rows a1-a8) for a batch of reads: SMEM -> SAL -> chain ->
  * filter -> extend -> sort/dedup/patch.  reg_off[n_reads+1] and regs (malloc'd by the library,
  * release with ssg_free) receive each read's mem_alnreg_t list in upstream order. */

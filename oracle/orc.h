@@ -134,6 +134,9 @@ int  orc_mem_mark_primary_se(const orc_opt_t *opt, int n, orc_alnreg_t *a, int64
 int  orc_mem_approx_mapq_se(const orc_opt_t *opt, const orc_alnreg_t *a);
 int  orc_mem_pair(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], const orc_alnreg_v a[2], int id, int *sub, int *n_sub, int z[2], int n_pri[2]);
 orc_aln_t orc_mem_reg2aln(const orc_opt_t *opt, const orc_idx_t *idx, int l_query, const uint8_t *query, const orc_alnreg_t *ar);
+typedef struct { int32_t kind, reg, owner, flag, mapq; } orc_pe_rec_t;
+int  orc_mem_pe_decide(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_alnreg_v a[2], int n_pri[2], int z[2], int q_se[2], int *extra_flag);
+void orc_mem_pe_records(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_alnreg_v a[2], orc_pe_rec_t *rec[2], int n_rec[2]);
 int  orc_mem_sam_pe(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_read_t s[2], orc_alnreg_v a[2], const char *rg_id);
 uint32_t *orc_gen_cigar2(const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins, int w_, int64_t l_pac, const uint8_t *pac,
                          int l_query, uint8_t *query, int64_t rb, int64_t re, int *score, int *n_cigar, int *NM);

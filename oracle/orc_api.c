@@ -21,6 +21,21 @@ static void flatten(const orc_alnreg_t *a, orc_flatreg_t *f)
 	f->frac_rep = a->frac_rep; f->hash = a->hash;
 }
 
+static void unflatten(const orc_flatreg_t *f, orc_alnreg_t *a)
+{
+	memset(a, 0, sizeof(*a));
+	a->rb = f->rb; a->re = f->re; a->qb = f->qb; a->qe = f->qe; a->rid = f->rid; a->score = f->score; a->truesc = f->truesc;
+	a->sub = f->sub; a->alt_sc = f->alt_sc; a->csub = f->csub; a->sub_n = f->sub_n; a->w = f->w; a->seedcov = f->seedcov;
+	a->secondary = f->secondary; a->secondary_all = f->secondary_all; a->seedlen0 = f->seedlen0; a->n_comp = f->n_comp;
+	a->frac_rep = f->frac_rep; a->hash = f->hash;
+}
+static orc_alnreg_v list_of(const orc_flatreg_t *f, int64_t n)
+{
+	orc_alnreg_v v = { (size_t)n, (size_t)n, malloc(sizeof(orc_alnreg_t) * (size_t)(n + 1)) };
+	for (int64_t k = 0; k < n; ++k) unflatten(&f[k], &v.a[k]);
+	return v;
+}
+
 orc_opt_t *orc_api_opt_new(void) { orc_opt_t *o = malloc(sizeof(orc_opt_t)); orc_opt_init(o); return o; }
 /* scoring of the stage-level checks (bwa mem -A -B -O -E): a, b, gap open / extend for deletions and insertions */
 void orc_api_opt_scores(orc_opt_t *o, int a, int b, int o_del, int e_del, int o_ins, int e_ins)
@@ -31,7 +46,44 @@ void orc_api_opt_chain(orc_opt_t *o, float drop_ratio, float mask_level, int min
 /* the seeding stage's knobs (bwa mem -k, -r, -c, -y and the compiled-in split_width), for the seeding reference's tests */
 void orc_api_opt_seed(orc_opt_t *o, int min_seed_len, float split_factor, int split_width, int max_occ, int64_t max_mem_intv)
 { o->min_seed_len = min_seed_len; o->split_factor = split_factor; o->split_width = split_width; o->max_occ = max_occ; o->max_mem_intv = (uint64_t)max_mem_intv; }
+/* the paired-end decision stage's knobs (bwa mem -M / -P through flag, -T, -U, -h and the compiled-in mapQ coefficients), for the pairing reference's tests */
+void orc_api_opt_pair(orc_opt_t *o, int flag, int max_XA_hits, float mapQ_coef_len, int mapQ_coef_fac, int T, int pen_unpaired)
+{ o->flag = flag; o->max_XA_hits = max_XA_hits; o->mapQ_coef_len = mapQ_coef_len; o->mapQ_coef_fac = mapQ_coef_fac; o->T = T; o->pen_unpaired = pen_unpaired; }
 void orc_api_free(void *p) { free(p); }
+
+/* the paired-end decision stage on region lists given by the caller (tests/test_pair_reference.py; the library's twins are ssg_dbg_pestat / ssg_dbg_pair_final):
+ * read r's regions are regs[reg_off[r] .. reg_off[r + 1]), read 1 and read 2 of a pair interleaved.
+ * orc_api_pestat: orc_mem_pestat over the pairs of each batch, n_batches x 4 models. */
+void orc_api_pestat(const orc_opt_t *opt, const orc_idx_t *idx, int n_pairs, const int64_t *reg_off, const orc_flatreg_t *regs, const int32_t *pair_batch, int n_batches, orc_pestat_t *pes)
+{
+	orc_alnreg_v *v = malloc(sizeof(orc_alnreg_v) * (size_t)(2 * n_pairs + 1));
+	for (int b = 0; b < n_batches; ++b) {
+		int n = 0;
+		for (int p = 0; p < n_pairs; ++p) if (pair_batch[p] == b) for (int i = 0; i < 2; ++i) v[n++] = list_of(regs + reg_off[2 * p + i], reg_off[2 * p + i + 1] - reg_off[2 * p + i]);
+		orc_mem_pestat(opt, idx->bns->l_pac, n, v, &pes[4 * b]);
+		for (int k = 0; k < n; ++k) free(v[k].a);
+	}
+	free(v);
+}
+/* orc_api_pair_final: orc_mem_mark_primary_se, orc_mem_pair and the decision of orc_mem_sam_pe (orc_mem_pe_records) for every pair, pair p with id id0 + p:
+ * regs_out the lists as the stage leaves them, req_off[2 n_pairs + 1] and req (room for 2 * regions + reads entries) the records, reg counted from regs[0]. */
+void orc_api_pair_final(const orc_opt_t *opt, const orc_idx_t *idx, int n_pairs, int64_t id0, const int64_t *reg_off, const orc_flatreg_t *regs, const orc_pestat_t pes[4],
+                        orc_flatreg_t *regs_out, int64_t *req_off, orc_pe_rec_t *req)
+{
+	int64_t nreq = 0;
+	for (int p = 0; p < n_pairs; ++p) {
+		orc_alnreg_v a[2]; orc_pe_rec_t *rec[2]; int n_rec[2];
+		for (int i = 0; i < 2; ++i) { a[i] = list_of(regs + reg_off[2 * p + i], reg_off[2 * p + i + 1] - reg_off[2 * p + i]); rec[i] = malloc(sizeof(orc_pe_rec_t) * (2 * a[i].n + 1)); }
+		orc_mem_pe_records(opt, idx, pes, (uint64_t)(id0 + p), a, rec, n_rec);
+		for (int i = 0; i < 2; ++i) {
+			req_off[2 * p + i] = nreq;
+			for (int k = 0; k < n_rec[i]; ++k) { req[nreq] = rec[i][k]; if (req[nreq].reg >= 0) req[nreq].reg += (int32_t)reg_off[2 * p + i]; ++nreq; }
+			for (size_t k = 0; k < a[i].n; ++k) flatten(&a[i].a[k], &regs_out[reg_off[2 * p + i] + k]);
+			free(a[i].a); free(rec[i]);
+		}
+	}
+	req_off[2 * n_pairs] = nreq;
+}
 
 /* mem_collect_intv for one read; returns the number of intervals (out may be smaller than needed) */
 int orc_api_collect_intv(const orc_opt_t *opt, const orc_idx_t *idx, int len, const uint8_t *seq, orc_intv_t *out, int cap)

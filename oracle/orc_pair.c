@@ -599,6 +599,7 @@ static void aln2sam(const orc_opt_t *opt, const orc_bns_t *bns, str_t *str, orc_
 	s_putc(str, '\n');
 }
 
+static inline int reg2sam_wanted(const orc_opt_t *opt, const orc_alnreg_t *p) { return p->score >= opt->T && p->secondary < 0; /* no -a */ }
 static void reg2sam(const orc_opt_t *opt, const orc_idx_t *idx, orc_read_t *s, orc_alnreg_v *a, int extra_flag, const orc_aln_t *m, const char *rg_id)
 {	/* upstream mem_reg2sam */
 	str_t str = {0,0,0};
@@ -608,8 +609,7 @@ static void reg2sam(const orc_opt_t *opt, const orc_idx_t *idx, orc_read_t *s, o
 	for (k = l = 0; k < (int)a->n; ++k) {
 		orc_alnreg_t *p = &a->a[k];
 		orc_aln_t q;
-		if (p->score < opt->T) continue;
-		if (p->secondary >= 0) continue; /* no -a */
+		if (!reg2sam_wanted(opt, p)) continue;
 		q = orc_mem_reg2aln(opt, idx, s->l_seq, s->seq, p);
 		q.XA = XA ? XA[k] : 0;
 		q.flag |= extra_flag;
@@ -633,34 +633,20 @@ static void reg2sam(const orc_opt_t *opt, const orc_idx_t *idx, orc_read_t *s, o
 
 #define raw_mapq(diff, a) ((int)(6.02 * (diff) / (a) + .499))
 
-int orc_mem_sam_pe(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_read_t s[2], orc_alnreg_v a[2], const char *rg_id)
-{	/* upstream mem_sam_pe */
-	int n = 0, i, j, z[2], o, subo, n_sub, extra_flag = 1, n_pri[2];
-	str_t str = {0,0,0};
-	orc_aln_t h[2];
-	memset(h, 0, sizeof(h));
-	if (!(opt->flag & ORC_F_NO_RESCUE)) {	/* mate rescue for the best hits */
-		orc_alnreg_v b[2] = {{0,0,0},{0,0,0}};
-		for (i = 0; i < 2; ++i)
-			for (j = 0; j < (int)a[i].n; ++j)
-				if (a[i].a[j].score >= a[i].a[0].score - opt->pen_unpaired) PUSH(b[i], orc_alnreg_t, a[i].a[j]);
-		for (i = 0; i < 2; ++i)
-			for (j = 0; j < (int)b[i].n && j < opt->max_matesw; ++j)
-				n += orc_mem_matesw(opt, idx, pes, &b[i].a[j], s[!i].l_seq, s[!i].seq, &a[!i]);
-		free(b[0].a); free(b[1].a);
-	}
-	n_pri[0] = orc_mem_mark_primary_se(opt, (int)a[0].n, a[0].a, id << 1 | 0);
-	n_pri[1] = orc_mem_mark_primary_se(opt, (int)a[1].n, a[1].a, id << 1 | 1);
-	if (opt->flag & ORC_F_NOPAIRING) goto no_pairing;
+/* mem_sam_pe between primary marking and SAM formatting: is the pair printed as a pair, and if so which regions (z), with which MAPQ (q_se) and flag bits;
+ * the lists' secondary_all are rewired to the chosen regions as upstream does before mem_gen_alt.  0: upstream's no_pairing branch takes over, nothing changed. */
+int orc_mem_pe_decide(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_alnreg_v a[2], int n_pri[2], int z[2], int q_se[2], int *extra_flag_)
+{
+	int i, j, o, subo, n_sub, extra_flag = *extra_flag_;
+	if (opt->flag & ORC_F_NOPAIRING) return 0;
 	if (n_pri[0] && n_pri[1] && (o = orc_mem_pair(opt, idx, pes, a, (int)id, &subo, &n_sub, z, n_pri)) > 0) {
-		int is_multi[2], q_pe, score_un, q_se[2];
-		char **XA[2];
+		int is_multi[2], q_pe, score_un;
 		for (i = 0; i < 2; ++i) {
 			for (j = 1; j < n_pri[i]; ++j)
 				if (a[i].a[j].secondary < 0 && a[i].a[j].score >= opt->T) break;
 			is_multi[i] = j < n_pri[i] ? 1 : 0;
 		}
-		if (is_multi[0] || is_multi[1]) goto no_pairing;
+		if (is_multi[0] || is_multi[1]) return 0;
 		score_un = a[0].a[0].score + a[1].a[0].score - opt->pen_unpaired;
 		subo = subo > score_un ? subo : score_un;
 		q_pe = raw_mapq(o - subo, opt->a);
@@ -692,6 +678,93 @@ int orc_mem_sam_pe(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_
 				a[i].a[z[i]].secondary_all = -1;
 			}
 		}
+		*extra_flag_ = extra_flag;
+		return 1;
+	}
+	return 0;
+}
+
+/* What mem_sam_pe prints for a pair whose lists are given (after mate rescue, before primary marking), without the alignments: per read the records
+ * (kind 0: a SAM line of region reg, -1 for an unmapped line; kind 1: an XA entry of region reg inside the line of region owner) with flag and MAPQ, SAM lines
+ * first.  The decision is orc_mem_pe_decide's, the choice of lines mem_reg2sam's, the XA candidates mem_gen_alt's (the lines that exist only).  Returns the
+ * number of records of read 0 and read 1 in n_rec; rec[i] must hold 2 * a[i].n + 1 entries. */
+void orc_mem_pe_records(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_alnreg_v a[2], orc_pe_rec_t *rec[2], int n_rec[2])
+{
+	int i, j, k, z[2], q_se[2], extra_flag = 1, n_pri[2];
+	n_rec[0] = n_rec[1] = 0;
+	n_pri[0] = orc_mem_mark_primary_se(opt, (int)a[0].n, a[0].a, id << 1 | 0);
+	n_pri[1] = orc_mem_mark_primary_se(opt, (int)a[1].n, a[1].a, id << 1 | 1);
+	if (orc_mem_pe_decide(opt, idx, pes, id, a, n_pri, z, q_se, &extra_flag)) {
+		for (i = 0; i < 2; ++i) { orc_pe_rec_t r = { 0, z[i], z[i], 0x40 << i | extra_flag, q_se[i] }; rec[i][n_rec[i]++] = r; }
+	} else {
+		int rid[2];
+		for (i = 0; i < 2; ++i) { /* the contig of the line mem_reg2aln would make of the top hit */
+			int which = -1, is_rev;
+			if (a[i].n) {
+				if (a[i].a[0].score >= opt->T) which = 0;
+				else if (n_pri[i] < (int)a[i].n && a[i].a[n_pri[i]].score >= opt->T) which = n_pri[i];
+			}
+			rid[i] = -1;
+			if (which >= 0) {
+				const orc_alnreg_t *ar = &a[i].a[which];
+				rid[i] = orc_bns_pos2rid(idx->bns, orc_bns_depos(idx->bns, ar->rb < idx->bns->l_pac ? ar->rb : ar->re - 1, &is_rev));
+			}
+		}
+		if (rid[0] == rid[1] && rid[0] >= 0) {
+			int64_t dist; int d;
+			d = infer_dir(idx->bns->l_pac, a[0].a[0].rb, a[1].a[0].rb, &dist);
+			if (!pes[d].failed && dist >= pes[d].low && dist <= pes[d].high) extra_flag |= 2;
+		}
+		for (i = 0; i < 2; ++i) { /* mem_reg2sam */
+			int l = 0, mapq0 = 0;
+			for (k = 0; k < (int)a[i].n; ++k) {
+				const orc_alnreg_t *p = &a[i].a[k];
+				orc_pe_rec_t r = { 0, k, k, (i ? 0x81 : 0x41) | extra_flag, 0 };
+				if (!reg2sam_wanted(opt, p)) continue;
+				r.mapq = p->secondary < 0 ? orc_mem_approx_mapq_se(opt, p) : 0;
+				if (l && p->secondary < 0) r.flag |= (opt->flag & ORC_F_NO_MULTI) ? 0x10000 : 0x800;
+				if (l && !p->is_alt && r.mapq > mapq0) r.mapq = mapq0;
+				if (!l) mapq0 = r.mapq;
+				rec[i][n_rec[i]++] = r;
+				++l;
+			}
+			if (l == 0) { orc_pe_rec_t r = { 0, -1, -1, (i ? 0x81 : 0x41) | extra_flag | 0x4, 0 }; rec[i][n_rec[i]++] = r; }
+		}
+	}
+	for (i = 0; i < 2; ++i) { /* mem_gen_alt, for the lines that exist */
+		int *cnt = calloc(a[i].n + 1, sizeof(int)), n_main = n_rec[i], r;
+		for (j = 0; j < (int)a[i].n; ++j) if ((r = get_pri_idx(opt->XA_drop_ratio, a[i].a, j)) >= 0) ++cnt[r];
+		for (j = 0; j < (int)a[i].n; ++j) {
+			if ((r = get_pri_idx(opt->XA_drop_ratio, a[i].a, j)) < 0) continue;
+			if (cnt[r] > opt->max_XA_hits_alt || cnt[r] > opt->max_XA_hits) continue;
+			for (k = 0; k < n_main; ++k) if (rec[i][k].reg == r) break;
+			if (k == n_main) continue;
+			{ orc_pe_rec_t x = { 1, j, r, 0, 0 }; rec[i][n_rec[i]++] = x; }
+		}
+		free(cnt);
+	}
+}
+
+int orc_mem_sam_pe(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_t pes[4], uint64_t id, orc_read_t s[2], orc_alnreg_v a[2], const char *rg_id)
+{	/* upstream mem_sam_pe */
+	int n = 0, i, j, z[2], q_se[2], extra_flag = 1, n_pri[2];
+	str_t str = {0,0,0};
+	orc_aln_t h[2];
+	memset(h, 0, sizeof(h));
+	if (!(opt->flag & ORC_F_NO_RESCUE)) {	/* mate rescue for the best hits */
+		orc_alnreg_v b[2] = {{0,0,0},{0,0,0}};
+		for (i = 0; i < 2; ++i)
+			for (j = 0; j < (int)a[i].n; ++j)
+				if (a[i].a[j].score >= a[i].a[0].score - opt->pen_unpaired) PUSH(b[i], orc_alnreg_t, a[i].a[j]);
+		for (i = 0; i < 2; ++i)
+			for (j = 0; j < (int)b[i].n && j < opt->max_matesw; ++j)
+				n += orc_mem_matesw(opt, idx, pes, &b[i].a[j], s[!i].l_seq, s[!i].seq, &a[!i]);
+		free(b[0].a); free(b[1].a);
+	}
+	n_pri[0] = orc_mem_mark_primary_se(opt, (int)a[0].n, a[0].a, id << 1 | 0);
+	n_pri[1] = orc_mem_mark_primary_se(opt, (int)a[1].n, a[1].a, id << 1 | 1);
+	if (orc_mem_pe_decide(opt, idx, pes, id, a, n_pri, z, q_se, &extra_flag)) {
+		char **XA[2];
 		for (i = 0; i < 2; ++i) XA[i] = gen_alt(opt, idx, &a[i], s[i].l_seq, s[i].seq);
 		for (i = 0; i < 2; ++i) {
 			h[i] = orc_mem_reg2aln(opt, idx, s[i].l_seq, s[i].seq, &a[i].a[z[i]]);
@@ -709,7 +782,7 @@ int orc_mem_sam_pe(const orc_opt_t *opt, const orc_idx_t *idx, const orc_pestat_
 		}
 		return n;
 	}
-no_pairing:
+	/* no pairing: */
 	for (i = 0; i < 2; ++i) {
 		int which = -1;
 		if (a[i].n) {

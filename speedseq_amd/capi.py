@@ -175,6 +175,31 @@ class Lib:
         self._chk(self.l.ssg_dbg_chain_sort(_ptr(keys), C.c_int(len(keys)), _ptr(o0), _ptr(o1)))
         return o0, o1
 
+    def dbg_pestat(self, idx, opt, reg_off, regs, pair_batch, n_batches):
+        """mem_pestat on given region lists (ssg_dbg_pestat): n_batches x 4 insert-size models"""
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        pair_batch = np.ascontiguousarray(pair_batch, dtype=np.int32)
+        pes = np.zeros(4 * n_batches, dtype=PESTAT_DT)
+        self._chk(self.l.ssg_dbg_pestat(idx, _ptr(opt), C.c_int((len(reg_off) - 1) // 2), _ptr(reg_off), _ptr(regs), _ptr(pair_batch), C.c_int(n_batches), _ptr(pes)))
+        return pes
+
+    def dbg_pair_final(self, idx, opt, id0, reg_off, regs, pes):
+        """primary marking, pairing, MAPQ and record selection on given region lists (ssg_dbg_pair_final): (regions as the stage leaves them, req_off, requests)"""
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DT)
+        assert len(pes) == 4 and len(regs) == reg_off[-1]
+        n = len(reg_off) - 1
+        out = np.zeros(len(regs), dtype=ALNREG_DT)
+        req_off = np.zeros(n + 1, dtype=np.int64)
+        req_p = C.c_void_p()
+        self._chk(self.l.ssg_dbg_pair_final(idx, _ptr(opt), C.c_int(n // 2), C.c_int64(id0), _ptr(reg_off), _ptr(regs), _ptr(pes), _ptr(out), _ptr(req_off), C.byref(req_p)))
+        nreq = int(req_off[n])
+        req = np.frombuffer((C.c_char * (nreq * ALNREQ_DT.itemsize)).from_address(req_p.value), dtype=ALNREQ_DT, count=nreq).copy() if nreq else np.zeros(0, ALNREQ_DT)
+        self.l.ssg_free(req_p)
+        return out, req_off, req
+
     def align1_batch(self, idx, opt, seq, off):
         n = len(off) - 1
         reg_off = np.zeros(n + 1, dtype=np.int64)

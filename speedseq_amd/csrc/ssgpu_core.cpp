@@ -1145,6 +1145,22 @@ static void host_pestat(const ssg_mem_opt_t *opt, const uint32_t *hist /* [4][SS
 	for (d = 0; d < 4; ++d) if (pes[d].failed == 0 && n[d] < max * 0.05) pes[d].failed = 1;
 }
 
+/* upstream mem_pestat for every batch of the call: candidate selection and the insert-size histograms on the device (ssg_k_pestat_hist), quartiles, mean, std
+ * and the fences on the host (host_pestat).  The pipeline (pe_core) and the test entry ssg_dbg_pestat both come through here. */
+static int run_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg,
+                      const int32_t *d_pb, int n_batches, ssg_pestat_t *pes /* n_batches x 4 */)
+{
+	const int block = 256;
+	dbuf<uint32_t> d_hist((size_t)n_batches * 4 * SSG_MAX_INS_HIST);
+	CHKA(d_hist); CHK(d_hist.zero());
+	SSG_LAUNCH(ssg_k_pestat_hist, (n_pairs + block - 1) / block, block, 0, idx->v, *opt, n_pairs, d_regoff, d_regs, d_nreg, d_pb, d_hist.p);
+	CHK(rt_sync());
+	std::vector<uint32_t> hh((size_t)n_batches * 4 * SSG_MAX_INS_HIST);
+	CHK(d_hist.down(hh.data(), hh.size()));
+	for (int b = 0; b < n_batches; ++b) host_pestat(opt, hh.data() + (size_t)b * 4 * SSG_MAX_INS_HIST, &pes[(size_t)b * 4]);
+	return 0;
+}
+
 /* the whole PE hot path on device-resident inputs; `keep` != NULL leaves the records in HBM
  * instead of downloading them into `res` */
 static thread_local unsigned int ssg_r2a_last[1 + SSG_R2D_CLASSES];   /* of this thread's last call: records left to the wave kernel, records per class of the lane DP */
@@ -1196,6 +1212,61 @@ static int run_reg2aln(const ssg_index *idx, const ssg_mem_opt_t *opt, int64_t n
 
 extern "C" void ssg_dbg_reg2aln_counts(unsigned int out[4]) { for (int k = 0; k < 1 + SSG_R2D_CLASSES; ++k) out[k] = ssg_r2a_last[k]; }
 
+/* mem_sam_pe after mate rescue, for all pairs: primary marking, pairing, MAPQ, record selection (k_pair.h, k_pairw.h), on the region slices reg_off (t2 slots in
+ * all) and request slices req_off that ssg_k_pair_caps sized; pair_key = the pairs' region counts, pair_order = the pairs heaviest first, err zeroed by the caller.
+ * Which kernel form takes which pair is decided here and nowhere else (SSG_PAIR_WAVE_MIN, SSG_PAIR_LDS); a pair beyond an on-device capacity ends the call with
+ * SSG_EOVERFLOW.  The pipeline (pe_core) and the test entry ssg_dbg_pair_final both come through here. */
+static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, int64_t t2, const int64_t *d_r2off, ssg_alnreg_t *d_regs2, const int32_t *d_nreg,
+                          const int32_t *d_pb, const ssg_pestat_t *d_pes, const int32_t *d_pkey, const int32_t *d_pw, int32_t *d_zbuf,
+                          const int64_t *d_reqoff, ssg_alnreq_t *d_req, int32_t *d_nreq, int32_t *d_perr, unsigned int *d_q)
+{
+	const int wpb = SSG_WAVES_PER_WG;
+	{	/* ---- primary marking, pairing, MAPQ, record selection ---- */
+		const int ucap = 1024;
+		long nthr = std::min<long>(((long)n_pairs + 63) / 64 * 64, (long)env_int("SSG_PF_THREADS", 131072));   /* 8 waves/CU at 2 waves/SIMD (249 VGPRs); 16 KB of candidate scratch per lane */
+		dbuf<ssg_pair64_t> d_v((size_t)t2 + 1), d_u((size_t)nthr * ucap);
+		CHKA(d_v); CHKA(d_u);
+		/* d_pw is heaviest first: pairs with long region lists get a wavefront each (k_pairw.h), the rest a lane each.  Above 16 regions (64 until r06T: the lane kernel on
+		 * global memory took 3.9 ms for the pairs of 7..63 regions, it takes 0.5 ms for those of 7..15, and the wave kernel 0.1 ms more: profiles/r06T_ktab_pairwave_sa_ab.json) */
+		unsigned int cc[5];
+		CHK(dev_class_counts(d_pkey, n_pairs, 0, 0, std::max(0, env_int("SSG_PAIR_WAVE_MIN", 16)), cc));   /* (below 0 the count would take in the padding lanes of its last wave) */
+		const int n_heavy = (int)cc[0];
+		const long nwg_h = n_heavy > 0 ? std::min<long>(((long)n_heavy + wpb - 1) / wpb, (long)env_int("SSG_PFW_WGS", 512)) : 0;
+		dbuf<ssg_pw_slab_t> d_slab((size_t)nwg_h * wpb + 1);
+		CHKA(d_slab); CHK(rt_memset(d_q, 0, sizeof(unsigned int)));
+		ssg_fork(1);
+		if (n_heavy > 0)
+			SSG_LAUNCH_ON(0, ssg_k_pair_final_wave, nwg_h, wpb * 64, 0, idx->v, *opt, n_heavy, id0, d_r2off, d_regs2, d_nreg, d_pb, d_pes, d_zbuf, d_v.p, d_slab.p,
+			              d_reqoff, d_req, d_nreq, d_perr, d_pw, d_q);
+		if (n_pairs > n_heavy) {
+			/* the pairs with a handful of regions (nearly all) with their state in LDS (k_pair.h ssg_k_pair_final_lds); what it lists, on global memory.  SSG_PAIR_LDS=0: all on global memory (A/B, tests) */
+			dbuf<int32_t> d_ptodo((size_t)n_pairs); dbuf<unsigned int> d_nptodo(1);
+			CHKA(d_ptodo); CHKA(d_nptodo); CHK(d_nptodo.zero());
+			const bool pf_lds = env_int("SSG_PAIR_LDS", 1) != 0;
+			if (pf_lds) SSG_LAUNCH(ssg_k_pair_final_lds, (n_pairs - n_heavy + 63) / 64, 64, 0, idx->v, *opt, n_pairs, id0, d_r2off, d_regs2, d_nreg, d_pb, d_pes,
+			                       d_reqoff, d_req, d_nreq, d_perr, d_pw, n_heavy, d_ptodo.p, d_nptodo.p);
+			SSG_LAUNCH(ssg_k_pair_final, nthr / 64, 64, 0, idx->v, *opt, n_pairs, id0, d_r2off, d_regs2, d_nreg, d_pb, d_pes, d_zbuf, d_v.p, d_u.p, ucap,
+			           d_reqoff, d_req, d_nreq, d_perr, d_pw, n_heavy, pf_lds ? (const int32_t*)d_ptodo.p : (const int32_t*)0, pf_lds ? (const unsigned int*)d_nptodo.p : (const unsigned int*)0);
+			ssg_join(1);
+			CHK(rt_sync());   /* (before the work lists of this scope go back to the arena) */
+		} else {
+			ssg_join(1);
+			CHK(rt_sync());
+		}
+	}
+	STAGE("pair_final");
+	{
+		unsigned int cc[5];
+		CHK(dev_class_counts(d_perr, n_pairs, 0, 0, 0, cc));
+		if (cc[4]) {
+			std::vector<int32_t> perr(n_pairs);
+			CHK(rt_d2h(perr.data(), d_perr, (size_t)n_pairs * sizeof(int32_t)));
+			for (int p = 0; p < n_pairs; ++p) if (perr[p]) { char b[128]; snprintf(b, sizeof(b), "pair %d exceeded an on-device capacity (code %d)", p, perr[p]); ssg_err_msg = b; return SSG_EOVERFLOW; }
+		}
+	}
+	return 0;
+}
+
 static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq_p, const int64_t *d_off_p, int max_len,
                    const int32_t *d_pb_p, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep)
 {
@@ -1210,15 +1281,7 @@ static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	/* ---- insert-size statistics ---- */
 	res->pes.resize((size_t)n_batches * 4);
 	if (pes0) { for (int b = 0; b < n_batches; ++b) memcpy(&res->pes[(size_t)b * 4], pes0, 4 * sizeof(ssg_pestat_t)); }
-	else {
-		dbuf<uint32_t> d_hist((size_t)n_batches * 4 * SSG_MAX_INS_HIST);
-		CHKA(d_hist); CHK(d_hist.zero());
-		SSG_LAUNCH(ssg_k_pestat_hist, (n_pairs + block - 1) / block, block, 0, idx->v, *opt, n_pairs, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_pb.p, d_hist.p);
-		CHK(rt_sync());
-		std::vector<uint32_t> hh((size_t)n_batches * 4 * SSG_MAX_INS_HIST);
-		CHK(d_hist.down(hh.data(), hh.size()));
-		for (int b = 0; b < n_batches; ++b) host_pestat(opt, hh.data() + (size_t)b * 4 * SSG_MAX_INS_HIST, &res->pes[(size_t)b * 4]);
-	}
+	else CHK(run_pestat(idx, opt, n_pairs, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_pb.p, n_batches, res->pes.data()));
 	STAGE("pestat");
 	dbuf<ssg_pestat_t> d_pes((size_t)n_batches * 4);
 	CHKA(d_pes); CHK(d_pes.up(res->pes.data(), res->pes.size()));
@@ -1289,49 +1352,7 @@ static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	STAGE("matesw");
 	dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
 	CHKA(d_req);
-	{	/* ---- primary marking, pairing, MAPQ, record selection ---- */
-		const int ucap = 1024;
-		long nthr = std::min<long>(((long)n_pairs + 63) / 64 * 64, (long)env_int("SSG_PF_THREADS", 131072));   /* 8 waves/CU at 2 waves/SIMD (249 VGPRs); 16 KB of candidate scratch per lane */
-		dbuf<ssg_pair64_t> d_v((size_t)t2 + 1), d_u((size_t)nthr * ucap);
-		CHKA(d_v); CHKA(d_u);
-		/* d_pw is heaviest first: pairs with long region lists get a wavefront each (k_pairw.h), the rest a lane each.  From 16 regions (64 until r06T: the lane kernel on
-		 * global memory took 3.9 ms for the pairs of 7..63 regions, it takes 0.5 ms for those of 7..15, and the wave kernel 0.1 ms more: profiles/r06T_ktab_pairwave_sa_ab.json) */
-		unsigned int cc[5];
-		CHK(dev_class_counts(d_pkey.p, n_pairs, 0, 0, env_int("SSG_PAIR_WAVE_MIN", 16), cc));
-		const int n_heavy = (int)cc[0];
-		const long nwg_h = n_heavy > 0 ? std::min<long>(((long)n_heavy + wpb - 1) / wpb, (long)env_int("SSG_PFW_WGS", 512)) : 0;
-		dbuf<ssg_pw_slab_t> d_slab((size_t)nwg_h * wpb + 1);
-		CHKA(d_slab); CHK(d_q.zero());
-		ssg_fork(1);
-		if (n_heavy > 0)
-			SSG_LAUNCH_ON(0, ssg_k_pair_final_wave, nwg_h, wpb * 64, 0, idx->v, *opt, n_heavy, id0, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_zbuf.p, d_v.p, d_slab.p,
-			              d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_pw.p, d_q.p);
-		if (n_pairs > n_heavy) {
-			/* the pairs with a handful of regions (nearly all) with their state in LDS (k_pair.h ssg_k_pair_final_lds); what it lists, on global memory.  SSG_PAIR_LDS=0: all on global memory (A/B, tests) */
-			dbuf<int32_t> d_ptodo((size_t)n_pairs); dbuf<unsigned int> d_nptodo(1);
-			CHKA(d_ptodo); CHKA(d_nptodo); CHK(d_nptodo.zero());
-			const bool pf_lds = env_int("SSG_PAIR_LDS", 1) != 0;
-			if (pf_lds) SSG_LAUNCH(ssg_k_pair_final_lds, (n_pairs - n_heavy + 63) / 64, 64, 0, idx->v, *opt, n_pairs, id0, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p,
-			                       d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_pw.p, n_heavy, d_ptodo.p, d_nptodo.p);
-			SSG_LAUNCH(ssg_k_pair_final, nthr / 64, 64, 0, idx->v, *opt, n_pairs, id0, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_zbuf.p, d_v.p, d_u.p, ucap,
-			           d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_pw.p, n_heavy, pf_lds ? (const int32_t*)d_ptodo.p : (const int32_t*)0, pf_lds ? (const unsigned int*)d_nptodo.p : (const unsigned int*)0);
-			ssg_join(1);
-			CHK(rt_sync());   /* (before the work lists of this scope go back to the arena) */
-		} else {
-			ssg_join(1);
-			CHK(rt_sync());
-		}
-	}
-	STAGE("pair_final");
-	{
-		unsigned int cc[5];
-		CHK(dev_class_counts(d_perr.p, n_pairs, 0, 0, 0, cc));
-		if (cc[4]) {
-			std::vector<int32_t> perr(n_pairs);
-			CHK(d_perr.down(perr.data(), n_pairs));
-			for (int p = 0; p < n_pairs; ++p) if (perr[p]) { char b[128]; snprintf(b, sizeof(b), "pair %d exceeded an on-device capacity (code %d)", p, perr[p]); ssg_err_msg = b; return SSG_EOVERFLOW; }
-		}
-	}
+	CHK(run_pair_final(idx, opt, n_pairs, id0, t2, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_pkey.p, d_pw.p, d_zbuf.p, d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
 	/* ---- compact the requests and generate CIGAR / NM / MD ---- */
 	dbuf<int64_t> d_coff(n_reads + 1);
 	CHKA(d_coff);
@@ -1360,6 +1381,104 @@ int ssg_pe_core(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_pairs, con
 	return pe_core(idx, opt, n_pairs, d_seq, d_off, max_len, d_pair_batch, n_batches, id0, pes0, res, keep);
 }
 int ssg_dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t *total) { return dev_exclusive_scan(d_in, d_out, n, total); }
+
+/* ---- test entries of the paired-end decision stage: region lists in, the stage's own results out (include/ssgpu.h) ---- */
+static int dbg_check_regs(const ssg_index_t *idx, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs, const char *who)
+{	/* the kernels index by what the lists say: nothing out of range may reach them */
+	static thread_local char msg[160];
+	const int n_reads = 2 * n_pairs;
+	const char *bad = 0; long at = -1;
+	if (n_pairs < 0 || n_pairs > (1 << 24)) { bad = "n_pairs out of range"; at = n_pairs; }
+	else if (reg_off[0] != 0) { bad = "reg_off[0] != 0"; at = 0; }
+	for (int r = 0; r < n_reads && !bad; ++r) {
+		if (reg_off[r + 1] < reg_off[r] || reg_off[r + 1] - reg_off[r] > 4096) { bad = "reg_off not monotone, or more than 4096 regions in a read: read"; at = r; }
+		else if (reg_off[r + 1] > (1LL << 28)) { bad = "too many regions in all: read"; at = r; }
+	}
+	for (int64_t k = 0; !bad && k < reg_off[n_reads]; ++k) {
+		const ssg_alnreg_t &e = regs[k];
+		if (e.rid < 0 || e.rid >= idx->v.n_ctg) bad = "rid out of range: region";
+		else if (!(0 <= e.qb && e.qb < e.qe && e.qe <= 310)) bad = "need 0 <= qb < qe <= 310: region";
+		else if (!(0 <= e.rb && e.rb < e.re && e.re <= 2 * idx->v.l_pac)) bad = "need 0 <= rb < re <= 2 l_pac: region";
+		else if (e.score < 0 || e.score > (1 << 20) || e.csub < 0 || e.csub > (1 << 20)) bad = "score / csub out of range: region";
+		else if (!(e.frac_rep >= 0 && e.frac_rep <= 1)) bad = "frac_rep outside [0, 1]: region";
+		if (bad) at = (long)k;
+	}
+	if (!bad) return 0;
+	snprintf(msg, sizeof(msg), "%s: %s %ld", who, bad, at);
+	ssg_err_msg = msg;
+	return SSG_EINVAL;
+}
+
+extern "C" {
+
+int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                   const int32_t *pair_batch, int n_batches, ssg_pestat_t *pes)
+{
+	CHK(need_device());
+	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pestat"));
+	if (n_batches < 1 || n_batches > 64) { ssg_err_msg = "ssg_dbg_pestat: 1 <= n_batches <= 64"; return SSG_EINVAL; }
+	for (int p = 0; p < n_pairs; ++p) if (pair_batch[p] < 0 || pair_batch[p] >= n_batches) { ssg_err_msg = "ssg_dbg_pestat: pair_batch out of range"; return SSG_EINVAL; }
+	const int n_reads = 2 * n_pairs;
+	const int64_t tot = reg_off[n_reads];
+	std::vector<int32_t> hn((size_t)n_reads + 1);
+	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
+	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1); dbuf<int32_t> d_n((size_t)n_reads + 1), d_pb((size_t)n_pairs + 1);
+	CHKA(d_off); CHKA(d_regs); CHKA(d_n); CHKA(d_pb);
+	CHK(d_off.up(reg_off, (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.up(pair_batch, (size_t)n_pairs));
+	return run_pestat(idx, opt, n_pairs, d_off.p, d_regs.p, d_n.p, d_pb.p, n_batches, pes);
+}
+
+int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                       const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req)
+{
+	CHK(need_device());
+	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pair_final"));
+	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].std > 0 && pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_pair_final: an orientation that has not failed needs std > 0 and 0 <= low <= high"; return SSG_EINVAL; }
+	const int n_reads = 2 * n_pairs, block = 256;
+	const int64_t tot = reg_off[n_reads];
+	*req = 0;
+	if (n_pairs == 0) { req_off[0] = 0; return SSG_OK; }
+	std::vector<int32_t> hn((size_t)n_reads);
+	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
+	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1); dbuf<int32_t> d_n((size_t)n_reads), d_pb((size_t)n_pairs); dbuf<ssg_pestat_t> d_pes(4);
+	CHKA(d_off); CHKA(d_regs); CHKA(d_n); CHKA(d_pb); CHKA(d_pes);
+	CHK(d_off.up(reg_off, (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pes.up(pes, 4));
+	/* slices, request capacities and the heaviest-first order exactly as pe_core makes them */
+	dbuf<int32_t> d_cap2(n_reads), d_capq(n_reads), d_pkey(n_pairs), d_pw(n_pairs);
+	dbuf<int64_t> d_r2off(n_reads + 1), d_reqoff(n_reads + 1);
+	CHKA(d_cap2); CHKA(d_capq); CHKA(d_pkey); CHKA(d_pw); CHKA(d_r2off); CHKA(d_reqoff);
+	SSG_LAUNCH(ssg_k_pair_caps, (n_reads + block - 1) / block, block, 0, n_reads, d_n.p, opt->max_matesw, d_cap2.p, d_capq.p, d_pkey.p);
+	int64_t t2 = 0, tq = 0;
+	CHK(dev_exclusive_scan(d_cap2.p, d_r2off.p, n_reads, &t2)); CHK(dev_exclusive_scan(d_capq.p, d_reqoff.p, n_reads, &tq));
+	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs));
+	dbuf<ssg_alnreg_t> d_regs2((size_t)t2 + 1); dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)t2 + 1), d_nreq(n_reads); dbuf<unsigned int> d_q(1); dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
+	CHKA(d_regs2); CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_q); CHKA(d_req);
+	CHK(d_perr.zero()); CHK(d_nreq.zero());
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_off.p, d_regs.p, d_n.p, d_r2off.p, d_regs2.p);
+	CHK(run_pair_final(idx, opt, n_pairs, id0, t2, d_r2off.p, d_regs2.p, d_n.p, d_pb.p, d_pes.p, d_pkey.p, d_pw.p, d_zbuf.p, d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
+	/* the regions back into the caller's layout, the requests compacted as pe_core compacts them */
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_r2off.p, d_regs2.p, d_n.p, d_off.p, d_regs.p);
+	dbuf<int64_t> d_coff(n_reads + 1);
+	CHKA(d_coff);
+	int64_t nreq = 0;
+	CHK(dev_exclusive_scan(d_nreq.p, d_coff.p, n_reads, &nreq));
+	dbuf<ssg_alnreq_t> d_creq((size_t)nreq + 1);
+	CHKA(d_creq);
+	SSG_LAUNCH(ssg_k_compact_req, (n_reads + block - 1) / block, block, 0, n_reads, d_reqoff.p, d_req.p, d_nreq.p, d_coff.p, d_creq.p);
+	CHK(rt_sync());
+	std::vector<int64_t> r2off((size_t)n_reads + 1);
+	CHK(d_r2off.down(r2off.data(), (size_t)n_reads + 1)); CHK(d_coff.down(req_off, (size_t)n_reads + 1)); CHK(d_regs.down(regs_out, (size_t)tot));
+	ssg_alnreq_t *out = (ssg_alnreq_t*)malloc(sizeof(ssg_alnreq_t) * (size_t)(nreq + 1));
+	if (!out) { ssg_err_msg = "host allocation failed: requests"; return SSG_ENOMEM; }
+	int rc = d_creq.down(out, (size_t)nreq);
+	if (rc) { free(out); return rc; }
+	for (int64_t k = 0; k < nreq; ++k) if (out[k].reg >= 0) out[k].reg = (int32_t)(out[k].reg - r2off[out[k].read] + reg_off[out[k].read]);   /* slice index -> the caller's index */
+	*req = out;
+	return SSG_OK;
+}
+
+} /* extern "C" */
+
 
 /* single-end reads (upstream mem_process_seqs without MEM_F_PE): stage 1 as for pairs, then every read on its own -- primary marking with
  * id = id0 + r (upstream's n_processed + i), the list of records (ssg_k_se_final), CIGAR / NM / MD.  No insert-size model, no mate rescue, no pairing. */

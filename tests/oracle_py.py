@@ -99,6 +99,29 @@ class Oracle:
                 return reg_off, out[:tot]
             cap = tot
 
+    def pestat(self, idx, reg_off, regs, pair_batch, n_batches, opt=None):
+        """orc_mem_pestat on given region lists, per batch: n_batches x 4 models (PESTAT_DT)"""
+        from speedseq_amd.capi import PESTAT_DT
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        pair_batch = np.ascontiguousarray(pair_batch, dtype=np.int32)
+        pes = np.zeros(4 * n_batches, dtype=PESTAT_DT)
+        self.l.orc_api_pestat(opt or self.opt, idx, C.c_int((len(reg_off) - 1) // 2), _ptr(reg_off), _ptr(regs), _ptr(pair_batch), C.c_int(n_batches), _ptr(pes))
+        return pes
+
+    def pair_final(self, idx, id0, reg_off, regs, pes, opt=None):
+        """primary marking, pairing and mem_sam_pe's decision on given region lists: (regions as the stage leaves them, req_off, records as
+        (kind, reg, owner, flag, mapq) rows)"""
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        pes = np.ascontiguousarray(pes)
+        n = len(reg_off) - 1
+        out = np.zeros(len(regs), dtype=ALNREG_DT)
+        req_off = np.zeros(n + 1, dtype=np.int64)
+        req = np.zeros((2 * len(regs) + n + 1, 5), dtype=np.int32)
+        self.l.orc_api_pair_final(opt or self.opt, idx, C.c_int(n // 2), C.c_int64(id0), _ptr(reg_off), _ptr(regs), _ptr(pes), _ptr(out), _ptr(req_off), _ptr(req))
+        return out, req_off, req[:req_off[n]]
+
     def chain_exposure(self, idx, seq, off, n_threads=8, opt=None, per_read=False):
         """every read through both containers of mem_chain (orc_mem.c: the position-sorted array the kernels restate, and klib's B-tree as upstream uses it):
         dict(differ, gt9_and_dup, gt9, dup, reads) [+ per-read flags]"""
