@@ -130,8 +130,19 @@ int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *o
  *   ssg_dbg_pair_final  mem_mark_primary_se, mem_pair and mem_sam_pe's decision with one insert-size model pes[4] for all pairs: regs_out receives the lists as
  *                       the stage leaves them (sorted, marked), req_off[2 n_pairs + 1] and *req (malloc'd, release with ssg_free) the requests per read,
  *                       req[].reg counted in the caller's layout.  SSG_EOVERFLOW as from the pipeline when a pair exceeds an on-device capacity. */
+/*   ssg_dbg_matesw      mem_matesw (mate rescue) for all pairs with one insert-size model pes[4]: seq / read_off[2 n_pairs + 1] are the reads (codes 0 .. 4), fixed[r] != 0
+ *                       says that read r's list is the output of mem_sort_dedup_patch already (NULL: none is).  The lists are laid out as the pipeline lays them out, each in
+ *                       a slice with head-room (headroom < 0: the pipeline's, else that many records): out_off[2 n_pairs + 1] the slices, *regs_out (malloc'd, release with
+ *                       ssg_free) their records, n_out[r] the length of read r's list after rescue, err[p] the stage's error code of pair p (0: none).  counts: [0] windows
+ *                       tried, [1] windows whose alignment came from a slot, [2] pairs decided by the kernel on keys, [3] listed pairs left to ssg_k_matesw, [4] listed
+ *                       pairs, [5] Smith-Waterman cells, [6] windows of the pairs left to ssg_k_matesw.
+ *   ssg_dbg_matesw_last the same counts of the calling thread's last rescue stage, whoever ran it (ssg_mem_process_pairs, ssg_hotpath_dev, ssg_dbg_matesw): with
+ *                       windows accumulated over the call (the counters of a pipeline call start at zero). */
 int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs,
                    const int32_t *pair_batch, int n_batches, ssg_pestat_t *pes);
+void ssg_dbg_matesw_last(uint64_t counts[8]);
+int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *read_off, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                   const uint8_t *fixed, const ssg_pestat_t pes[4], int headroom, int64_t *out_off, ssg_alnreg_t **regs_out, int32_t *n_out, int32_t *err, uint64_t counts[8]);
 int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
                        const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req);
 

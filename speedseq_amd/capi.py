@@ -200,6 +200,34 @@ class Lib:
         self.l.ssg_free(req_p)
         return out, req_off, req
 
+    def dbg_matesw(self, idx, opt, seq, read_off, reg_off, regs, pes, fixed=None, headroom=-1):
+        """mate rescue on given region lists (ssg_dbg_matesw): (per-read lists after rescue, per-pair error codes, counts: windows, windows from slots,
+        pairs decided on keys, pairs left to the record kernel, listed pairs, SW cells)"""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.int64)
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DT)
+        n = len(reg_off) - 1
+        assert len(pes) == 4 and len(regs) == reg_off[-1] and len(read_off) == n + 1 and len(seq) == read_off[-1]
+        fx = None if fixed is None else np.ascontiguousarray(fixed, dtype=np.uint8)
+        assert fx is None or len(fx) == n
+        out_off, n_out, err, counts = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(n // 2, dtype=np.int32), np.zeros(8, dtype=np.uint64)
+        out_p = C.c_void_p()
+        self._chk(self.l.ssg_dbg_matesw(idx, _ptr(opt), C.c_int(n // 2), _ptr(seq), _ptr(read_off), _ptr(reg_off), _ptr(regs), _ptr(fx) if fx is not None else None, _ptr(pes),
+                                        C.c_int(headroom), _ptr(out_off), C.byref(out_p), _ptr(n_out), _ptr(err), _ptr(counts)))
+        tot = int(out_off[n])
+        allr = np.frombuffer((C.c_char * (tot * ALNREG_DT.itemsize)).from_address(out_p.value), dtype=ALNREG_DT, count=tot).copy() if tot and out_p.value else np.zeros(0, ALNREG_DT)
+        self.l.ssg_free(out_p)
+        lists = [allr[int(out_off[r]):int(out_off[r]) + int(n_out[r])].copy() for r in range(n)]
+        return lists, err, counts
+
+    def dbg_matesw_last(self):
+        """the counts of ssg_dbg_matesw for the calling thread's last rescue stage (the pipeline's included)"""
+        counts = np.zeros(8, dtype=np.uint64)
+        self.l.ssg_dbg_matesw_last(_ptr(counts))
+        return counts
+
     def align1_batch(self, idx, opt, seq, off):
         n = len(off) - 1
         reg_off = np.zeros(n + 1, dtype=np.int64)

@@ -29,21 +29,10 @@
 #ifndef SSG_K_MSWLANE_H
 #define SSG_K_MSWLANE_H
 #include "k_sw.h"
-
-SSG_DEVFN int ssg_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)
-{	/* upstream mem_infer_dir */
-	int r1 = (b1 >= l_pac), r2 = (b2 >= l_pac);
-	int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
+#include "k_mswslot.h"   /* ssg_infer_dir, ssg_msjob_t, ssg_msres_t */
 
 #define SSG_ML_R 8            /* target rows per strip */
 #define SSG_ML_TMAX 8192      /* longest window given to the lane kernel */
-
-/* slot = side base + 4 * anchor + orientation.  p = 16 / 8: the padding unit of the query (KSW_XBYTE or not); xstart: KSW_XSTART */
-struct ssg_msjob_t { int64_t rb, qoff; int32_t tlen, qlen, qp, minsc, is_rev, p, xstart, _pad; };                 /* 48 bytes */
-struct ssg_msres_t { int64_t rb; int32_t tlen, state, score, te, qe, score2, te2, tb, qb, _pad; };   /* 48 bytes; state: 0 = not computed, 1 = forward pass, 2 = forward and reverse pass (tb, qb) */
 
 /* the lane kernel trusts no job record: a key that names no slot, or a record with impossible lengths, is skipped (the wave code does that
  * window then); -DSSG_ML_CHECK counts them in ssg_dbg_cyc[24 + code] */

@@ -63,13 +63,13 @@ static double ssg_stage_ms() { static thread_local std::chrono::steady_clock::ti
 #define STAGE(name) do { if (ssg_debug()) { int rc_ = rt_sync(); fprintf(stderr, "[ssgpu] stage %s done rc=%d  +%.1f ms\n", name, rc_, ssg_stage_ms()); fflush(stderr); if (rc_) return rc_; } } while (0)
 
 SSG_ABI_FP_DEFINE(core)
-extern "C" void ssg_abi_fp_index_build(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_seed(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_sam_format(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bam(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_coll(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf_frame(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_rec_gather(ssg_abi_fp_t*);
+extern "C" void ssg_abi_fp_index_build(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_seed(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_sam_format(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bam(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_coll(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf_frame(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_rec_gather(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_msw_replay(ssg_abi_fp_t*);
 extern "C" int ssg_abi_selfcheck(void)
 {	/* every translation unit of the library was compiled against the same shared declarations (ssg_index_int.h) */
 	static const char *const field[20] = { "sizeof(ssg_index_view_t)", "sizeof(ssg_mem_opt_t)", "sizeof(ssg_index)", "sizeof(ssg_intv_t)", "ssg_index_view_t.primary", "ssg_index_view_t.L2",
 		"ssg_index_view_t.l_pac", "ssg_index_view_t.sa_intv", "ssg_mem_opt_t.min_seed_len", "ssg_mem_opt_t.split_width", "ssg_mem_opt_t.max_mem_intv", "ssg_mem_opt_t.split_factor", "ssg_mem_opt_t.mat",
 		"ssg_index.bwt", "ssg_index.ktab", "ssg_index.bwt_words", "ssg_index.names", "sizeof(ssg_seed_t)", "sizeof(ssg_alnreg_t)", "sizeof(ssg_aln_t)" };
-	struct { const char *unit; void (*fn)(ssg_abi_fp_t*); } const units[] = { { "ssg_index_build", ssg_abi_fp_index_build }, { "ssg_seed", ssg_abi_fp_seed }, { "ssg_bgzf", ssg_abi_fp_bgzf }, { "sam_format", ssg_abi_fp_sam_format }, { "ssg_bam", ssg_abi_fp_bam }, { "ssg_coll", ssg_abi_fp_coll }, { "ssg_bgzf_frame", ssg_abi_fp_bgzf_frame }, { "ssg_rec_gather", ssg_abi_fp_rec_gather } };
+	struct { const char *unit; void (*fn)(ssg_abi_fp_t*); } const units[] = { { "ssg_index_build", ssg_abi_fp_index_build }, { "ssg_seed", ssg_abi_fp_seed }, { "ssg_bgzf", ssg_abi_fp_bgzf }, { "sam_format", ssg_abi_fp_sam_format }, { "ssg_bam", ssg_abi_fp_bam }, { "ssg_coll", ssg_abi_fp_coll }, { "ssg_bgzf_frame", ssg_abi_fp_bgzf_frame }, { "ssg_rec_gather", ssg_abi_fp_rec_gather }, { "ssg_msw_replay", ssg_abi_fp_msw_replay } };
 	ssg_abi_fp_t mine; ssg_abi_fp_core(&mine);
 	for (const auto &u : units) {
 		ssg_abi_fp_t o; u.fn(&o);
@@ -1267,6 +1267,90 @@ static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 	return 0;
 }
 
+/* upstream mem_matesw for all pairs, on the pairing-stage slices (d_r2off, head-room included) with n_reg updated in place: which pairs need it (ssg_k_matesw_need), their
+ * windows ahead of the decision (k_mswlane.h), the list logic (k_mswkeys.h, and ssg_k_matesw for what that kernel leaves).  d_cnt: SW cells, windows, windows taken from
+ * slots; d_perr: ssg_k_matesw's error codes.  The pipeline (pe_core) and the test entry ssg_dbg_matesw both come through here. */
+struct msw_stage_t { unsigned long long cells, windows, from_slots, left_windows; unsigned int listed, taken, left; };
+static thread_local msw_stage_t ssg_msw_last;   /* of this thread's last rescue stage (ssg_dbg_matesw_last) */
+static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq, const int64_t *d_off, int max_len, const int64_t *d_r2off, ssg_alnreg_t *d_regs2,
+                      int32_t *d_nreg, const int32_t *d_pb, const ssg_pestat_t *d_pes, const int32_t *d_pw, const uint8_t *d_fixed, int32_t *d_perr, unsigned long long *d_cnt,
+                      unsigned int *d_q, msw_stage_t *ms)
+{
+	const int n_reads = 2 * n_pairs, wpb = SSG_WAVES_PER_WG;
+	long nwg = std::min<long>(((long)n_pairs + wpb - 1) / wpb, 256 * SSG_SW_WAVES_PER_SIMD);
+	long nw = nwg * wpb;
+	dbuf<uint8_t> d_tglb((size_t)nw * SSG_TWIN_GLB); dbuf<unsigned long long> d_bglb((size_t)nw * SSG_MS_BCAP); dbuf<ssg_alnreg_t> d_bcopy((size_t)nw * (128 + SSG_SDP_BIG)); dbuf<ssg_sdp_big_t> d_sdpbig((size_t)nw);
+	CHKA(d_tglb); CHKA(d_bglb); CHKA(d_bcopy); CHKA(d_sdpbig);
+	dbuf<int32_t> d_mtodo((size_t)n_pairs); dbuf<unsigned int> d_nmtodo(1);
+	CHKA(d_mtodo); CHKA(d_nmtodo); CHK(d_nmtodo.zero());
+	SSG_LAUNCH(ssg_k_matesw_need, (n_pairs + 63) / 64, 64, 0, idx->v, *opt, n_pairs, d_r2off, d_regs2, d_nreg, d_pb, d_pes, d_pw, d_mtodo.p, d_nmtodo.p);
+	/* the windows' forward passes ahead of the decisions (k_mswlane.h): lanes per job; 0 = everything through the wave code */
+	dbuf<ssg_msres_t> d_jres; dbuf<int64_t> d_jbase;
+	const int ml_lanes = env_int("SSG_MSW_LANES", 4);
+	bool have_slots = false;
+	unsigned int n_listed = 0;
+	if (ml_lanes > 0) {
+		unsigned int n_todo = 0;
+		CHK(d_nmtodo.down(&n_todo, 1));
+		if (n_todo > 0 && n_todo < (1u << 30)) {
+			dbuf<int32_t> d_jcnt((size_t)2 * n_todo);
+			if (!d_jbase.alloc((size_t)2 * n_todo + 1)) { ssg_err_msg = "device allocation failed: mate rescue slots"; return SSG_ENOMEM; }
+			CHKA(d_jcnt);
+			SSG_LAUNCH(ssg_k_msw_count, (n_todo + 63) / 64, 64, 0, *opt, (int)n_todo, d_mtodo.p, d_r2off, d_regs2, d_nreg, d_jcnt.p);
+			int64_t nslot = 0;
+			STAGE("msw_count");
+			CHK(dev_exclusive_scan(d_jcnt.p, d_jbase.p, 2L * n_todo, &nslot));
+			STAGE("msw_scan");
+			if (nslot > 0 && nslot < (1LL << 31)) {
+				dbuf<ssg_msjob_t> d_jobs((size_t)nslot); dbuf<uint64_t> d_keys((size_t)nslot); dbuf<unsigned int> d_nj(2);   /* windows; the longest */
+				if (!d_jres.alloc((size_t)nslot)) { ssg_err_msg = "device allocation failed: mate rescue slots"; return SSG_ENOMEM; }
+				CHKA(d_jobs); CHKA(d_keys); CHKA(d_nj); CHK(d_nj.zero()); CHK(d_jres.zero());
+				SSG_LAUNCH(ssg_k_msw_emit, (nslot / 4 + 63) / 64, 64, 0, idx->v, *opt, (int)n_todo, (long)(nslot / 4), d_mtodo.p, d_jbase.p, d_off, d_r2off, d_regs2, d_nreg,
+				           d_pb, d_pes, d_jobs.p, d_keys.p, d_nj.p);
+				STAGE("msw_emit");
+				int64_t seq_bytes = 0;
+				CHK(rt_d2h(&seq_bytes, d_off + n_reads, 8));
+				unsigned int njt[2] = { 0, 0 };
+				CHK(d_nj.down(njt, 2));
+				const unsigned int nj = njt[0];
+				CHK(run_msw_lane(idx, opt, (long)nj, d_keys.p, d_jobs.p, d_seq, d_jres.p, (max_len + 15) / 16 * 16, (int)njt[1], ml_lanes, 0, (long)nslot, (long)seq_bytes));
+				have_slots = true; n_listed = n_todo;
+				if (ssg_debug()) fprintf(stderr, "[ssgpu] mate rescue: %u listed pairs, %lld slots, %u windows ahead of the decision\n", n_todo, (long long)nslot, nj);
+			}
+		}
+	}
+	/* the list logic of the listed pairs on compact keys (k_mswkeys.h) where every window has its slot; what that kernel gives up -- and everything with
+	 * SSG_MSW_KEYS=0 (A/B, tests) or without slots -- goes through ssg_k_matesw */
+	const bool keys = have_slots && n_listed > 0 && env_int("SSG_MSW_KEYS", 1) != 0;
+	dbuf<int32_t> d_left; dbuf<int64_t> d_lbase; dbuf<unsigned int> d_kcnt(SSG_MSW_NCNT), d_kq(1); dbuf<ssg_alnreg_t> d_ktmp; dbuf<uint8_t> d_kslab;
+	CHKA(d_kcnt); CHKA(d_kq); CHK(d_kcnt.zero());
+	if (keys) {
+		const long kw = ssg_msw_replay_waves(n_listed, env_int("SSG_MSW_KEYS_WGS", 768));   /* 52 KB of LDS a workgroup: three a CU */
+		size_t slab_bytes = 0; const size_t tmp_recs = ssg_msw_replay_scratch(kw, &slab_bytes);
+		if (!d_left.alloc((size_t)n_listed) || !d_lbase.alloc((size_t)2 * n_listed) || !d_ktmp.alloc(tmp_recs) || !d_kslab.alloc(slab_bytes)) { ssg_err_msg = "device allocation failed: mate rescue replay"; return SSG_ENOMEM; }
+		CHK(ssg_msw_replay(idx, opt, kw, d_mtodo.p, d_nmtodo.p, d_off, d_r2off, d_regs2, d_nreg, d_pb, d_pes, d_ktmp.p, d_kslab.p, d_kq.p, d_cnt, d_cnt + 1,
+		                   d_jres.p, d_jbase.p, d_fixed, (int)std::min<long>(SSG_TWIN_GLB, SSG_MS_BCAP), d_left.p, d_lbase.p, d_kcnt.p));
+	}
+	SSG_LAUNCH_W(max_len > 255, ssg_k_matesw, nwg, wpb * 64, 0, idx->v, *opt, n_pairs, d_seq, d_off, d_r2off, d_regs2, d_nreg, d_pb, d_pes,
+	           d_bcopy.p, d_tglb.p, d_bglb.p, d_perr, d_cnt, d_cnt + 1, keys ? (const int32_t*)d_left.p : (const int32_t*)d_mtodo.p, d_q, d_sdpbig.p, keys ? (const unsigned int*)d_kcnt.p : (const unsigned int*)d_nmtodo.p,
+	           have_slots ? (const ssg_msres_t*)d_jres.p : (const ssg_msres_t*)0, have_slots ? (keys ? (const int64_t*)d_lbase.p : (const int64_t*)d_jbase.p) : (const int64_t*)0, d_fixed);
+	CHK(rt_sync());
+	{	/* what the stage did: two small copies after the wait above */
+		unsigned long long c[3]; unsigned int k[SSG_MSW_NCNT];
+		CHK(rt_d2h(c, d_cnt, sizeof(c))); CHK(d_kcnt.down(k, SSG_MSW_NCNT));
+		if (!have_slots) CHK(d_nmtodo.down(&n_listed, 1));
+		if (ssg_debug()) {
+			fprintf(stderr, "[ssgpu] mate rescue: %llu windows aligned, %llu of them ahead of the decision\n", c[1], c[2]);
+			if (keys) fprintf(stderr, "[ssgpu] mate rescue replay on keys: %u of %u listed pairs decided, %u left over with %llu of %llu windows (window without a slot %u, no reverse pass %u, tie %u, head-room %u, list too long %u, error code %u)\n",
+			                  k[1], n_listed, k[0], c[1] - k[8], c[1], k[2], k[3], k[4], k[5], k[6], k[7]);
+		}
+		msw_stage_t &m = ssg_msw_last;
+		m.cells = c[0]; m.windows = c[1]; m.from_slots = c[2]; m.left_windows = keys ? c[1] - k[8] : c[1]; m.listed = n_listed; m.taken = keys ? k[1] : 0; m.left = keys ? k[0] : n_listed;
+		if (ms) *ms = m;
+	}
+	return 0;
+}
+
 static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq_p, const int64_t *d_off_p, int max_len,
                    const int32_t *d_pb_p, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep)
 {
@@ -1301,54 +1385,8 @@ static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	const int wpb = SSG_WAVES_PER_WG;
 	dbuf<unsigned int> d_q(1);
 	CHKA(d_q); CHK(d_q.zero());
-	if (!(opt->flag & SSG_F_NO_RESCUE)) {	/* ---- mate rescue (upstream mem_sam_pe: unless -S) ---- */
-		long nwg = std::min<long>(((long)n_pairs + wpb - 1) / wpb, 256 * SSG_SW_WAVES_PER_SIMD);
-		long nw = nwg * wpb;
-		dbuf<uint8_t> d_tglb((size_t)nw * SSG_TWIN_GLB); dbuf<unsigned long long> d_bglb((size_t)nw * SSG_MS_BCAP); dbuf<ssg_alnreg_t> d_bcopy((size_t)nw * (128 + SSG_SDP_BIG)); dbuf<ssg_sdp_big_t> d_sdpbig((size_t)nw);
-		CHKA(d_tglb); CHKA(d_bglb); CHKA(d_bcopy); CHKA(d_sdpbig);
-		dbuf<int32_t> d_mtodo((size_t)n_pairs); dbuf<unsigned int> d_nmtodo(1);
-		CHKA(d_mtodo); CHKA(d_nmtodo); CHK(d_nmtodo.zero());
-		SSG_LAUNCH(ssg_k_matesw_need, (n_pairs + 63) / 64, 64, 0, idx->v, *opt, n_pairs, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_pw.p, d_mtodo.p, d_nmtodo.p);
-		/* the windows' forward passes ahead of the decisions (k_mswlane.h): lanes per job; 0 = everything through the wave code */
-		dbuf<ssg_msres_t> d_jres; dbuf<int64_t> d_jbase;
-		const int ml_lanes = env_int("SSG_MSW_LANES", 4);
-		bool have_slots = false;
-		if (ml_lanes > 0) {
-			unsigned int n_todo = 0;
-			CHK(d_nmtodo.down(&n_todo, 1));
-			if (n_todo > 0 && n_todo < (1u << 30)) {
-				dbuf<int32_t> d_jcnt((size_t)2 * n_todo);
-				if (!d_jbase.alloc((size_t)2 * n_todo + 1)) { ssg_err_msg = "device allocation failed: mate rescue slots"; return SSG_ENOMEM; }
-				CHKA(d_jcnt);
-				SSG_LAUNCH(ssg_k_msw_count, (n_todo + 63) / 64, 64, 0, *opt, (int)n_todo, d_mtodo.p, d_r2off.p, d_regs2.p, a1.n_reg.p, d_jcnt.p);
-				int64_t nslot = 0;
-				STAGE("msw_count");
-				CHK(dev_exclusive_scan(d_jcnt.p, d_jbase.p, 2L * n_todo, &nslot));
-				STAGE("msw_scan");
-				if (nslot > 0 && nslot < (1LL << 31)) {
-					dbuf<ssg_msjob_t> d_jobs((size_t)nslot); dbuf<uint64_t> d_keys((size_t)nslot); dbuf<unsigned int> d_nj(2);   /* windows; the longest */
-					if (!d_jres.alloc((size_t)nslot)) { ssg_err_msg = "device allocation failed: mate rescue slots"; return SSG_ENOMEM; }
-					CHKA(d_jobs); CHKA(d_keys); CHKA(d_nj); CHK(d_nj.zero()); CHK(d_jres.zero());
-					SSG_LAUNCH(ssg_k_msw_emit, (nslot / 4 + 63) / 64, 64, 0, idx->v, *opt, (int)n_todo, (long)(nslot / 4), d_mtodo.p, d_jbase.p, d_off.p, d_r2off.p, d_regs2.p, a1.n_reg.p,
-					           d_pb.p, d_pes.p, d_jobs.p, d_keys.p, d_nj.p);
-					STAGE("msw_emit");
-					int64_t seq_bytes = 0;
-					CHK(rt_d2h(&seq_bytes, d_off.p + n_reads, 8));
-					unsigned int njt[2] = { 0, 0 };
-					CHK(d_nj.down(njt, 2));
-					const unsigned int nj = njt[0];
-					CHK(run_msw_lane(idx, opt, (long)nj, d_keys.p, d_jobs.p, d_seq.p, d_jres.p, (max_len + 15) / 16 * 16, (int)njt[1], ml_lanes, 0, (long)nslot, (long)seq_bytes));
-					have_slots = true;
-					if (ssg_debug()) fprintf(stderr, "[ssgpu] mate rescue: %u listed pairs, %lld slots, %u windows ahead of the decision\n", n_todo, (long long)nslot, nj);
-				}
-			}
-		}
-		SSG_LAUNCH_W(max_len > 255, ssg_k_matesw, nwg, wpb * 64, 0, idx->v, *opt, n_pairs, d_seq.p, d_off.p, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p,
-		           d_bcopy.p, d_tglb.p, d_bglb.p, d_perr.p, d_cnt.p, d_cnt.p + 1, d_mtodo.p, d_q.p, d_sdpbig.p, d_nmtodo.p,
-		           have_slots ? (const ssg_msres_t*)d_jres.p : (const ssg_msres_t*)0, have_slots ? (const int64_t*)d_jbase.p : (const int64_t*)0, (const uint8_t*)a1.sdp_fixed.p);
-		CHK(rt_sync());
-		if (ssg_debug()) { unsigned long long c[3]; CHK(d_cnt.down(c, 3)); fprintf(stderr, "[ssgpu] mate rescue: %llu windows aligned, %llu of them ahead of the decision\n", c[1], c[2]); }
-	}
+	if (!(opt->flag & SSG_F_NO_RESCUE))	/* ---- mate rescue (upstream mem_sam_pe: unless -S) ---- */
+		CHK(run_matesw(idx, opt, n_pairs, d_seq.p, d_off.p, max_len, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_pw.p, (const uint8_t*)a1.sdp_fixed.p, d_perr.p, d_cnt.p, d_q.p, 0));
 	STAGE("matesw");
 	dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
 	CHKA(d_req);
@@ -1474,6 +1512,59 @@ int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
 	if (rc) { free(out); return rc; }
 	for (int64_t k = 0; k < nreq; ++k) if (out[k].reg >= 0) out[k].reg = (int32_t)(out[k].reg - r2off[out[k].read] + reg_off[out[k].read]);   /* slice index -> the caller's index */
 	*req = out;
+	return SSG_OK;
+}
+
+void ssg_dbg_matesw_last(uint64_t counts[8])
+{
+	const msw_stage_t &m = ssg_msw_last;
+	memset(counts, 0, 8 * sizeof(uint64_t));
+	counts[0] = m.windows; counts[1] = m.from_slots; counts[2] = m.taken; counts[3] = m.left; counts[4] = m.listed; counts[5] = m.cells; counts[6] = m.left_windows;
+}
+
+int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *read_off, const int64_t *reg_off, const ssg_alnreg_t *regs,
+                   const uint8_t *fixed, const ssg_pestat_t pes[4], int headroom, int64_t *out_off, ssg_alnreg_t **regs_out, int32_t *n_out, int32_t *err, uint64_t counts[8])
+{
+	CHK(need_device());
+	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_matesw"));
+	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_matesw: an orientation that has not failed needs 0 <= low <= high"; return SSG_EINVAL; }
+	const int n_reads = 2 * n_pairs, block = 256;
+	*regs_out = 0; memset(counts, 0, 8 * sizeof(uint64_t));
+	if (n_pairs == 0) { out_off[0] = 0; return SSG_OK; }
+	int max_len = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (read_off[r + 1] <= read_off[r] || (r == 0 && read_off[0] != 0)) { ssg_err_msg = "ssg_dbg_matesw: read_off must start at 0 and increase"; return SSG_EINVAL; }
+		max_len = std::max<int>(max_len, (int)std::min<int64_t>(read_off[r + 1] - read_off[r], 1 << 20));
+	}
+	if (max_len > SSG_MAX_READ_LEN) { ssg_err_msg = "reads longer than " SSG_STR(SSG_MAX_READ_LEN) " bases are outside this build's scope"; return SSG_EINVAL; }
+	for (int64_t k = 0; k < read_off[n_reads]; ++k) if (seq[k] > 4) { ssg_err_msg = "ssg_dbg_matesw: bases are codes 0 .. 4"; return SSG_EINVAL; }
+	for (int r = 0; r < n_reads; ++r) for (int64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) if (regs[k].qe > (int)(read_off[r + 1] - read_off[r])) { ssg_err_msg = "ssg_dbg_matesw: a region ends beyond its read"; return SSG_EINVAL; }
+	/* the slices as ssg_k_pair_caps sizes them (own regions + 4 rescued hits per anchor of the mate + 4), or own regions + headroom */
+	std::vector<int32_t> hn((size_t)n_reads), hkey((size_t)n_pairs); std::vector<int64_t> r2off((size_t)n_reads + 1, 0); std::vector<uint8_t> hfix((size_t)n_reads, 0);
+	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
+	for (int r = 0; r < n_reads; ++r) { const int m = hn[r ^ 1]; r2off[r + 1] = r2off[r] + hn[r] + (headroom >= 0 ? headroom : 4 * std::min(m, opt->max_matesw) + 4); if (fixed) hfix[r] = fixed[r] ? 1 : 0; }
+	for (int p = 0; p < n_pairs; ++p) hkey[p] = hn[2 * p] + hn[2 * p + 1];
+	const int64_t tot = reg_off[n_reads], t2 = r2off[n_reads];
+	dbuf<uint8_t> d_seq((size_t)read_off[n_reads] + 1), d_fixed((size_t)n_reads); dbuf<int64_t> d_roff((size_t)n_reads + 1), d_off((size_t)n_reads + 1), d_r2off((size_t)n_reads + 1);
+	dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1), d_regs2((size_t)t2 + 1); dbuf<int32_t> d_n((size_t)n_reads), d_pb((size_t)n_pairs), d_pkey((size_t)n_pairs), d_pw((size_t)n_pairs), d_perr((size_t)n_pairs);
+	dbuf<ssg_pestat_t> d_pes(4); dbuf<unsigned long long> d_cnt(3); dbuf<unsigned int> d_q(1);
+	CHKA(d_seq); CHKA(d_fixed); CHKA(d_roff); CHKA(d_off); CHKA(d_r2off); CHKA(d_regs); CHKA(d_regs2); CHKA(d_n); CHKA(d_pb); CHKA(d_pkey); CHKA(d_pw); CHKA(d_perr); CHKA(d_pes); CHKA(d_cnt); CHKA(d_q);
+	CHK(d_seq.up(seq, (size_t)read_off[n_reads])); CHK(d_fixed.up(hfix.data(), (size_t)n_reads)); CHK(d_roff.up(read_off, (size_t)n_reads + 1)); CHK(d_off.up(reg_off, (size_t)n_reads + 1));
+	CHK(d_r2off.up(r2off.data(), (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_regs2.zero()); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pkey.up(hkey.data(), (size_t)n_pairs));
+	CHK(d_perr.zero()); CHK(d_pes.up(pes, 4)); CHK(d_cnt.zero()); CHK(d_q.zero());
+	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs));
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_off.p, d_regs.p, d_n.p, d_r2off.p, d_regs2.p);
+	msw_stage_t ms;
+	CHK(run_matesw(idx, opt, n_pairs, d_seq.p, d_roff.p, max_len, d_r2off.p, d_regs2.p, d_n.p, d_pb.p, d_pes.p, d_pw.p, d_fixed.p, d_perr.p, d_cnt.p, d_q.p, &ms));
+	ssg_alnreg_t *out = (ssg_alnreg_t*)malloc(sizeof(ssg_alnreg_t) * (size_t)(t2 + 1));
+	if (!out) { ssg_err_msg = "host allocation failed: regions"; return SSG_ENOMEM; }
+	int rc = d_regs2.down(out, (size_t)t2);
+	if (!rc) rc = d_n.down(n_out, (size_t)n_reads);
+	if (!rc) rc = d_perr.down(err, (size_t)n_pairs);
+	if (rc) { free(out); return rc; }
+	memcpy(out_off, r2off.data(), ((size_t)n_reads + 1) * sizeof(int64_t));
+	counts[0] = ms.windows; counts[1] = ms.from_slots; counts[2] = ms.taken; counts[3] = ms.left; counts[4] = ms.listed; counts[5] = ms.cells; counts[6] = ms.left_windows;
+	*regs_out = out;
 	return SSG_OK;
 }
 
