@@ -12,7 +12,7 @@ all: lib tools oracle emu synth
 lib: speedseq_amd/libssgpu.so
 # Every object's prerequisites come from the compiler (-MMD): no hand-kept header lists, so no object can be stale against a shared
 # declaration (round 3 shipped variant libraries linked from objects of different ages).
-HIPOBJS = $(CSRC)/ssgpu_core.o $(CSRC)/ssg_index_build.o $(CSRC)/ssg_seed.o $(CSRC)/ssg_bgzf.o $(CSRC)/ssg_bgzf_frame.o $(CSRC)/ssg_rec_gather.o $(CSRC)/ssg_msw_replay.o $(CSRC)/ssg_bam.o $(CSRC)/ssg_coll.o
+HIPOBJS = $(CSRC)/ssgpu_core.o $(CSRC)/ssg_index_build.o $(CSRC)/ssg_seed.o $(CSRC)/ssg_bgzf.o $(CSRC)/ssg_bgzf_frame.o $(CSRC)/ssg_bgzf_inflate.o $(CSRC)/ssg_rec_gather.o $(CSRC)/ssg_msw_replay.o $(CSRC)/ssg_bam.o $(CSRC)/ssg_coll.o
 $(HIPOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -x hip -c $< -o $@
 $(CSRC)/sam_format.o: $(CSRC)/sam_format.cpp
@@ -36,7 +36,10 @@ tools/synth/libsynthreads.so: tools/synth/synth_reads.cpp
 	$(HIPCC) --offload-arch=gfx950 -O3 -shared -fPIC $< -o $@
 
 # random 64-byte-line gather probe (the roofline denominator of the FM-index kernels; tools/profile_round.sh runs it)
-probe: tools/dbg/gather_probe tools/dbg/valu_probe tools/dbg/libm_probe
+probe: tools/dbg/gather_probe tools/dbg/valu_probe tools/dbg/libm_probe tools/dbg/inflate_probe
+# the BGZF reader's wall time with zlib and with the device inflate hook (tools/dbg/inflate_times.py)
+tools/dbg/inflate_probe: tools/dbg/inflate_probe.cpp $(HOSTHDRS) speedseq_amd/libssgpu.so
+	$(CXX) -O2 -std=c++17 tools/dbg/inflate_probe.cpp -o $@ -Lspeedseq_amd -lssgpu -lz -lpthread -Wl,-rpath,'$$ORIGIN/../../speedseq_amd'
 tools/dbg/libm_probe: tools/dbg/libm_probe.cpp
 	$(HIPCC) --offload-arch=gfx950 -O3 -ffp-contract=off $< -o $@
 tools/dbg/valu_probe: tools/dbg/valu_probe.cpp
@@ -70,9 +73,9 @@ tests/emu/fi_test: tools/dbg/fi_test.cpp $(HOST)/fast_inflate.h
 	$(CXX) -O2 -std=c++17 tools/dbg/fi_test.cpp -o $@ -lz
 tests/emu/fq_dump: tools/dbg/fq_dump.cpp $(HOST)/fastq.h $(HOST)/fast_inflate.h
 	$(CXX) -O2 -std=c++17 tools/dbg/fq_dump.cpp -o $@ -lz -lpthread
-tests/emu/libssgpu_emu.so: $(CSRC)/ssgpu_core.cpp $(CSRC)/ssg_index_build.cpp $(CSRC)/ssg_seed.cpp $(CSRC)/ssg_bgzf.cpp $(CSRC)/ssg_bgzf_frame.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_msw_replay.cpp $(CSRC)/ssg_bam.cpp $(CSRC)/ssg_coll.cpp $(CSRC)/sam_format.cpp tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
+tests/emu/libssgpu_emu.so: $(CSRC)/ssgpu_core.cpp $(CSRC)/ssg_index_build.cpp $(CSRC)/ssg_seed.cpp $(CSRC)/ssg_bgzf.cpp $(CSRC)/ssg_bgzf_frame.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_msw_replay.cpp $(CSRC)/ssg_bam.cpp $(CSRC)/ssg_coll.cpp $(CSRC)/sam_format.cpp tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
 	$(CXX) -O2 -g -std=c++17 -fPIC -ffp-contract=off -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
-		$(CSRC)/ssgpu_core.cpp $(CSRC)/ssg_index_build.cpp $(CSRC)/ssg_seed.cpp $(CSRC)/ssg_bgzf.cpp $(CSRC)/ssg_bgzf_frame.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_msw_replay.cpp $(CSRC)/ssg_bam.cpp $(CSRC)/ssg_coll.cpp $(CSRC)/sam_format.cpp tests/emu/emu.cpp -shared -o $@ -lpthread -lz
+		$(CSRC)/ssgpu_core.cpp $(CSRC)/ssg_index_build.cpp $(CSRC)/ssg_seed.cpp $(CSRC)/ssg_bgzf.cpp $(CSRC)/ssg_bgzf_frame.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_msw_replay.cpp $(CSRC)/ssg_bam.cpp $(CSRC)/ssg_coll.cpp $(CSRC)/sam_format.cpp tests/emu/emu.cpp -shared -o $@ -lpthread -lz
 tests/emu/bwa_emu: $(HOST)/bwa_main.cpp $(HOSTHDRS) tests/emu/libssgpu_emu.so
 	$(CXX) -O2 -std=c++17 $(HOST)/bwa_main.cpp -o $@ -Ltests/emu -lssgpu_emu -lz -lpthread -Wl,-rpath,'$$ORIGIN'
 tests/emu/samblaster_emu: $(HOST)/samblaster_main.cpp $(HOSTHDRS) tests/emu/libssgpu_emu.so
@@ -81,20 +84,28 @@ tests/emu/samblaster_emu: $(HOST)/samblaster_main.cpp $(HOSTHDRS) tests/emu/libs
 tests/emu/sambamba_emu: $(HOST)/sambamba_main.cpp $(HOSTHDRS) tests/emu/libssgpu_emu.so
 	$(CXX) -O2 -std=c++17 $(HOST)/sambamba_main.cpp -o $@ -Ltests/emu -lssgpu_emu -lz -lpthread -Wl,-rpath,'$$ORIGIN'
 
+# memory safety of the inflate kernel's error paths: the emulated kernel under AddressSanitizer and UndefinedBehaviorSanitizer, fed the malformed members of
+# tests/test_bgzf_inflate.py and 2000 seeded mutations (tools/dbg/inflate_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
+fuzz-inflate: tests/emu/inflate_fuzz
+	tests/emu/inflate_fuzz tests/golden/bgzf_inflate_malformed.bin
+tests/emu/inflate_fuzz: tools/dbg/inflate_fuzz.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
+		tools/dbg/inflate_fuzz.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp tests/emu/emu.cpp -o $@ -lpthread -lz
+
 clean:
-	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test $(CSRC)/*.o
+	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz $(CSRC)/*.o
 	$(MAKE) -C oracle clean
-.PHONY: all lib tools oracle emu clean variant tune
+.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate
 
 # A/B builds of the device library with other compile-time parameters (bench / tests: SSGPU_LIB=speedseq_amd/libssgpu_$(NAME).so); never the
 # default.  The units named in VUNITS (default: all) are compiled with VFLAGS into build/$(NAME)/; the others are the product build's
 # objects, which `lib` has just brought up to date against every header they include (-MMD), so no stale object can be linked.
 #   make variant NAME=x VFLAGS="-D..."                   all translation units
 #   make variant NAME=x VFLAGS="-D..." VUNITS=ssg_seed   only that unit (seconds)
-VUNITS ?= ssgpu_core ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_frame ssg_rec_gather ssg_msw_replay ssg_bam ssg_coll
+VUNITS ?= ssgpu_core ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_msw_replay ssg_bam ssg_coll
 variant: lib
 	mkdir -p build/$(NAME) && rm -f build/$(NAME)/*.o
-	for u in ssgpu_core ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_frame ssg_rec_gather ssg_msw_replay ssg_bam ssg_coll; do \
+	for u in ssgpu_core ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_msw_replay ssg_bam ssg_coll; do \
 	  case " $(VUNITS) " in *" $$u "*) $(HIPCC) $(HIPFLAGS) $(VFLAGS) -x hip -c $(CSRC)/$$u.cpp -o build/$(NAME)/$$u.o || exit 1;; \
 	  *) cp $(CSRC)/$$u.o build/$(NAME)/$$u.o;; esac; done
 	cp $(CSRC)/sam_format.o build/$(NAME)/sam_format.o

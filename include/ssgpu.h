@@ -339,6 +339,16 @@ uint64_t ssg_bgzf_bound(uint64_t payload_bytes, long n_blocks);
 /* CRC-32 (zlib's, the one of a BGZF member's trailer, bgzf.c:298-342) of n byte ranges data[cut[i] .. cut[i+1]) of any length, on the device; host buffers.
  * One wavefront per range: made for many ranges of BGZF-block size; a single range of many megabytes keeps one wavefront of the device busy. */
 int ssg_crc32_batch(const uint8_t *data, const uint64_t *cut, long n, uint32_t *crc);
+/* ssg_bgzf_inflate: the inverse of ssg_bgzf_compress (the reader in the reference: htslib bgzf.c, bgzf_read_block / check_header / inflate_block; the stream:
+ * RFC 1951, judged as zlib's inflate judges it).  members[moff[b] .. moff[b+1]) is one complete BGZF member -- header with the BC subfield, deflate stream of any
+ * block types, CRC-32, ISIZE; concatenated they are a BGZF file's body.  The host walks the headers: SSG_EINVAL, with the member's index in ssg_last_error(), for
+ * a member that is no gzip member with FEXTRA, has no BC subfield, a BSIZE + 1 other than its span, a span below 28 bytes or an ISIZE above 65536.  out_off[]
+ * becomes the prefix sum of the ISIZEs (out_off[0] = 0); SSG_EOVERFLOW when out_off[n_blocks] > out_cap (nothing is written behind out + out_cap);
+ * n_blocks <= 0: out_off[0] = 0 and nothing else.  The device inflates a wavefront per member to out[out_off[b] .. out_off[b+1]) and checksums the output.
+ * status (may be NULL): 0 good; 1 malformed stream; 2 the stream's output is not ISIZE bytes (shorter, or more to come); 3 CRC-32 mismatch.  Returns 0 when
+ * every member is good, SSG_EIO when one is not: status[] is complete then, the good members' output intact, a bad member's range unspecified (and only that
+ * range touched).  Bytes behind the final block's end are no error; an empty member (the end-of-file marker) is good and produces nothing.  Host buffers. */
+int ssg_bgzf_inflate(const uint8_t *members, const uint64_t *moff, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *status);
 /* ---- the records of a sort in HBM, and their sorted stream gathered there (row f1; stands for bgzf_write's copy of a record into the block buffer, htslib
  * bgzf.c) ----
  * A device mirror of the chunks `sambamba sort` holds its input in.  A record's location is (chunk << 40 | offset of its block_size word), the encoding the sort

@@ -430,6 +430,25 @@ def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None):
     return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
 
 
+def bgzf_inflate(lib, members, moff, want_status=True, out_cap=None):
+    """ssg_bgzf_inflate: the BGZF members members[moff[b] .. moff[b+1]) inflated and checksummed on the device.  Returns (rc, out, out_off, status):
+    rc 0 or SSG_EIO (-5: status[] says which members are bad; 1 malformed, 2 length, 3 CRC-32), member b's bytes out[out_off[b]:out_off[b+1]];
+    every other return code raises.  status is None unless wanted."""
+    members = _bytes_u8(members)
+    moff = np.ascontiguousarray(moff, dtype=np.uint64)
+    n = len(moff) - 1
+    if out_cap is None:
+        out_cap = sum(int.from_bytes(members[int(e) - 4:int(e)].tobytes(), "little") for e in moff[1:] if int(e) >= 4) if n > 0 else 0
+    out = np.zeros(max(int(out_cap), 1), dtype=np.uint8)
+    off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32) if want_status else None
+    rc = lib.l.ssg_bgzf_inflate(_ptr(members) if members.size else None, _ptr(moff), C.c_long(n), _ptr(out), C.c_uint64(int(out_cap)), _ptr(off),
+                                _ptr(status) if want_status else None)
+    if rc != -5:
+        lib._chk(rc)
+    return rc, out[:int(off[-1])], off, (status[:max(n, 0)] if want_status else None)
+
+
 class Recs:
     """A device-resident record store (ssg_recs_*): freed with the object or by close()."""
 

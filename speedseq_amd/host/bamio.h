@@ -128,6 +128,24 @@ struct bgzf_out_t {
 	void finish() { drain(true); io_write_all(fd, BGZF_EOF, 28); }
 };
 
+/* Optional batch inflate behind the reader (null: zlib on the pool's threads, as ever).  The signature and the return codes are
+ * ssg_bgzf_inflate's (include/ssgpu.h): 0, -5 when a member is bad (status[] says which), anything else when the call itself failed.
+ * sambamba_main.cpp installs it; bin/bamkit has no device library and keeps zlib. */
+typedef int (*bgzf_batch_inflate_fn)(const uint8_t *members, const uint64_t *moff, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *status);
+static bgzf_batch_inflate_fn bgzf_inflate_hook = 0;
+static bool bgzf_inflate_log = false;          /* one line per reader at its end */
+/* where the hook's output lands before it is cut into blocks: with these set, memory the installer's device copies into at bus speed (ssg_host_alloc) */
+static void *(*bgzf_hook_alloc)(size_t) = 0;
+static void (*bgzf_hook_free)(void*) = 0;
+/* a member whose stream is one final stored block holding all of ISIZE (the test next_batch makes before it sets up an inflate state) */
+static inline bool bgzf_member_is_stored(const uint8_t *h, size_t len)
+{
+	const size_t xlen = h[10] | (size_t)h[11] << 8;
+	uint32_t isz; memcpy(&isz, h + len - 4, 4);
+	const uint8_t *df = h + 12 + xlen; const size_t dn = len - 12 - xlen - 8;
+	return isz && dn == (size_t)isz + 5 && df[0] == 1 && (df[1] | (size_t)df[2] << 8) == isz && ((df[1] | (size_t)df[2] << 8) ^ 0xffffu) == (df[3] | (size_t)df[4] << 8);
+}
+
 /* BGZF reader: blocks are read sequentially and inflated by the pool in batches; exposes the payload as a byte stream and, for
  * the indexer, the virtual file offset bgzf_tell would report */
 struct bgzf_in_t {
@@ -135,7 +153,11 @@ struct bgzf_in_t {
 	std::vector<uint8_t> raw; size_t raw_pos;                  /* read-ahead of compressed bytes */
 	struct blk_t { uint64_t addr; std::vector<uint8_t> data; };
 	std::vector<blk_t> q; size_t qi, qo;                       /* current batch, block index, offset inside the block */
-	bgzf_in_t(int fd_, int threads_) : fd(fd_), threads(threads_), eof(false), caddr(0), raw_pos(0), qi(0), qo(0) {}
+	uint64_t n_dev, n_stored, n_host;                          /* members inflated through the hook, stored ones copied, inflated by zlib (counted with the hook or the log on) */
+	bgzf_in_t(int fd_, int threads_) : fd(fd_), threads(threads_), eof(false), caddr(0), raw_pos(0), qi(0), qo(0), n_dev(0), n_stored(0), n_host(0), hook_out(0), hook_out_cap(0), hook_out_free(0) {}
+	uint8_t *hook_out; size_t hook_out_cap; void (*hook_out_free)(void*);   /* the hook's output buffer: kept from batch to batch, grown when a batch needs more */
+	~bgzf_in_t() { if (hook_out) hook_out_free(hook_out); if (bgzf_inflate_log) fprintf(stderr, "[sambamba] inflate: %llu members on the device, %llu stored members copied, %llu on the host\n", (unsigned long long)n_dev, (unsigned long long)n_stored, (unsigned long long)n_host); }
+	bgzf_in_t(const bgzf_in_t&) = delete; bgzf_in_t &operator=(const bgzf_in_t&) = delete;
 	bool fill_raw(size_t need)
 	{
 		while (raw.size() - raw_pos < need && !eof) {
@@ -147,12 +169,49 @@ struct bgzf_in_t {
 		}
 		return raw.size() - raw_pos >= need;
 	}
+	/* the members of a batch that are neither empty nor stored, through the hook in one call: q[b] filled and via[b] = 1 for each.  A bad member ends
+	 * the program as the zlib path does; any other failure drops the hook for good, and zlib takes this batch and the rest. */
+	template <class SPANS> void hook_batch(const SPANS &sp, std::vector<uint8_t> &via)
+	{
+		std::vector<size_t> ix; std::vector<uint64_t> moff(1, 0); uint64_t out_bytes = 0;
+		for (size_t b = 0; b < sp.size(); ++b) {
+			const uint8_t *h = raw.data() + sp[b].off; uint32_t isz; memcpy(&isz, h + sp[b].len - 4, 4);
+			if (!isz || sp[b].len < 28 || bgzf_member_is_stored(h, sp[b].len)) continue;   /* (stored: copied on the host -- the `view -l 0' stream must not make a round trip over the bus) */
+			ix.push_back(b); moff.push_back(moff.back() + sp[b].len); out_bytes += isz;
+		}
+		if (ix.empty()) return;
+		const uint8_t *members = raw.data() + sp[ix[0]].off;
+		std::vector<uint8_t> pack;
+		if (sp[ix.back()].off + sp[ix.back()].len - sp[ix[0]].off != moff.back()) {   /* not one contiguous stretch of the read-ahead: pack them */
+			pack.resize((size_t)moff.back());
+			for (size_t k = 0; k < ix.size(); ++k) memcpy(pack.data() + moff[k], raw.data() + sp[ix[k]].off, sp[ix[k]].len);
+			members = pack.data();
+		}
+		if (out_bytes + 1 > hook_out_cap) {
+			if (hook_out) hook_out_free(hook_out);
+			hook_out_cap = (size_t)out_bytes + 1; hook_out_free = bgzf_hook_alloc && bgzf_hook_free ? bgzf_hook_free : free;
+			hook_out = (uint8_t*)(bgzf_hook_alloc && bgzf_hook_free ? bgzf_hook_alloc(hook_out_cap) : malloc(hook_out_cap));
+			if (!hook_out) { hook_out_cap = 0; fprintf(stderr, "[sambamba] no memory for the device inflate's output: zlib on the host from here on\n"); bgzf_inflate_hook = 0; return; }
+		}
+		uint8_t *const out = hook_out; std::vector<uint64_t> ooff(ix.size() + 1); std::vector<int32_t> st(ix.size(), 0);
+		const int rc = bgzf_inflate_hook(members, moff.data(), (long)ix.size(), out, out_bytes, ooff.data(), st.data());
+		if (rc == -5) {
+			size_t k = 0; while (k + 1 < ix.size() && !st[k]) ++k;
+			fprintf(stderr, "[sambamba] inflate failed: BGZF member at file offset %llu (device status %d)\n", (unsigned long long)sp[ix[k]].addr, (int)st[k]); exit(1);
+		}
+		if (rc != 0) { fprintf(stderr, "[sambamba] device inflate failed with code %d: zlib on the host from here on\n", rc); bgzf_inflate_hook = 0; return; }
+		parallel_for(threads, ix.size(), [&](size_t k0, size_t k1, int) {
+			for (size_t k = k0; k < k1; ++k) { const size_t b = ix[k]; q[b].addr = sp[b].addr; q[b].data.assign(out + ooff[k], out + ooff[k + 1]); via[b] = 1; }
+		});
+		n_dev += ix.size();
+	}
 	bool next_batch()
-	{	/* up to 512 blocks */
+	{	/* up to 512 blocks (4096 with the batch-inflate hook) */
 		struct span_t { size_t off, len; uint64_t addr; };
 		std::vector<span_t> sp;
 		if (raw_pos > ((size_t)8 << 20)) { raw.erase(raw.begin(), raw.begin() + raw_pos); raw_pos = 0; }   /* consumed bytes go here, between batches: the spans below are offsets into raw */
-		while (sp.size() < 512) {
+		const size_t batch_max = bgzf_inflate_hook ? 4096 : 512;
+		while (sp.size() < batch_max) {
 			if (!fill_raw(18)) break;
 			const uint8_t *h = raw.data() + raw_pos;
 			if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { fprintf(stderr, "[sambamba] not a BGZF block\n"); exit(1); }
@@ -167,8 +226,16 @@ struct bgzf_in_t {
 		}
 		if (sp.empty()) return false;
 		q.assign(sp.size(), blk_t());
+		std::vector<uint8_t> via;                              /* via[b] = 1: q[b] came through the hook */
+		if (bgzf_inflate_hook) { via.assign(sp.size(), 0); hook_batch(sp, via); }
+		if (bgzf_inflate_hook || bgzf_inflate_log)
+			for (size_t b = 0; b < sp.size(); ++b) {
+				const uint8_t *h = raw.data() + sp[b].off; uint32_t isz; memcpy(&isz, h + sp[b].len - 4, 4);
+				if (isz && !(b < via.size() && via[b])) { if (sp[b].len >= 28 && bgzf_member_is_stored(h, sp[b].len)) ++n_stored; else ++n_host; }
+			}
 		parallel_for(threads, sp.size(), [&](size_t b0, size_t b1, int) {
 			for (size_t b = b0; b < b1; ++b) {
+				if (b < via.size() && via[b]) continue;
 				const uint8_t *h = raw.data() + sp[b].off; const size_t xlen = h[10] | (size_t)h[11] << 8;
 				uint32_t isz; memcpy(&isz, h + sp[b].len - 4, 4);
 				q[b].addr = sp[b].addr; q[b].data.resize(isz);
@@ -178,7 +245,7 @@ struct bgzf_in_t {
 				} else if (isz) {
 					z_stream zs; memset(&zs, 0, sizeof(zs));
 					zs.next_in = (Bytef*)(h + 12 + xlen); zs.avail_in = (uInt)(sp[b].len - 12 - xlen - 8); zs.next_out = q[b].data.data(); zs.avail_out = isz;
-					if (inflateInit2(&zs, -15) != Z_OK || inflate(&zs, Z_FINISH) != Z_STREAM_END) { fprintf(stderr, "[sambamba] inflate failed\n"); exit(1); }
+					if (inflateInit2(&zs, -15) != Z_OK || inflate(&zs, Z_FINISH) != Z_STREAM_END) { fprintf(stderr, "[sambamba] inflate failed: BGZF member at file offset %llu\n", (unsigned long long)sp[b].addr); exit(1); }
 					inflateEnd(&zs);
 				}
 			}

@@ -3,6 +3,7 @@
  * sub-commands the reference's scripts issue:
  *   view -S -f bam [-l N] /dev/stdin          SAM text -> BAM on stdout               bin/speedseq:426,433,440,447
  *   view -H <in.bam>                          header text                             bin/speedseq:682,1032,1179
+ *   view [-h] <in.bam>                        SAM text (with -h: behind the header), the lines of bam2sam.h
  *   sort -t N -m XG --tmpdir=DIR -o out <in>  coordinate sort                         bin/speedseq:427,431,434,1950
  *   index <in.bam>                            <in.bam>.bai                            bin/speedseq:486-494
  *   merge -t N out.bam in1.bam in2.bam ...    merge of coordinate-sorted files        bin/speedseq:2002-2004
@@ -18,6 +19,7 @@
 #include "bamio.h"
 #include "fastq.h"   /* chan_t */
 #include "fused.h"
+#include "bam2sam.h"
 #include "xchg.h"
 #include "ranks.h"
 #include <atomic>
@@ -32,15 +34,25 @@ static int hw_threads() { unsigned n = std::thread::hardware_concurrency(); retu
 static void die(const std::string &m) { fprintf(stderr, "[sambamba] %s\n", m.c_str()); rk_mark_failed("sambamba"); exit(1); }   /* rank mode: the other ranks must not wait for this one */
 static int open_in(const char *p) { if (!strcmp(p, "/dev/stdin") || !strcmp(p, "-")) return 0; int fd = open(p, O_RDONLY); if (fd < 0) die(std::string("cannot open ") + p); return fd; }
 
+/* SSG_BGZF_INFLATE_DEVICE=1 and a visible device: every reader of this process inflates its batches through ssg_bgzf_inflate (bamio.h's hook; off by
+ * default).  SSG_BGZF_INFLATE_LOG=1: one line per reader at its end.  Called once, by the sub-command's thread, before its first reader is made (for
+ * `sort` in the worker process). */
+static void inflate_hook_setup()
+{
+	const char *const l = getenv("SSG_BGZF_INFLATE_LOG"); bgzf_inflate_log = l && atoi(l) != 0;
+	const char *const e = getenv("SSG_BGZF_INFLATE_DEVICE");
+	if (e && !strcmp(e, "1") && ssg_device_count() > 0) { bgzf_inflate_hook = ssg_bgzf_inflate; bgzf_hook_alloc = ssg_host_alloc; bgzf_hook_free = ssg_host_free; }
+}
+
 /* ---------------- view ---------------- */
 static int cmd_view(int argc, char **argv)
 {
-	int level = -1, threads = hw_threads(); bool hdr_only = false, sam_in = false; const char *in = 0, *fmt = "sam";
+	int level = -1, threads = hw_threads(); bool hdr_only = false, sam_in = false, with_hdr = false; const char *in = 0, *fmt = "sam";
 	for (int i = 0; i < argc; ++i) {
 		const char *a = argv[i];
 		if (!strcmp(a, "-S")) sam_in = true;
 		else if (!strcmp(a, "-H")) hdr_only = true;
-		else if (!strcmp(a, "-h")) ;
+		else if (!strcmp(a, "-h")) with_hdr = true;
 		else if (!strcmp(a, "-f") && i + 1 < argc) fmt = argv[++i];
 		else if (!strcmp(a, "-l") && i + 1 < argc) level = atoi(argv[++i]);
 		else if (!strcmp(a, "-t") && i + 1 < argc) threads = atoi(argv[++i]);
@@ -55,7 +67,24 @@ static int cmd_view(int argc, char **argv)
 		io_write_all(1, h.text.data(), h.text.size());
 		return 0;
 	}
-	if (!sam_in || strcmp(fmt, "bam")) die("view: only `-S -f bam` (SAM text to BAM) and `-H` are supported");
+	if (!sam_in && !strcmp(fmt, "sam")) {   /* a BAM file as SAM text (with -h: behind its header), the lines of bam2sam.h */
+		bgzf_in_t bi(fd, threads); bam_hdr_t h;
+		if (!hdr_read(bi, h)) die("view: not a BAM file");
+		std::string text; if (with_hdr) text = h.text;
+		std::vector<uint8_t> rec;
+		for (;;) {
+			uint32_t bs;
+			if (bi.get(&bs, 4) != 4) break;
+			if (bs < 32) die("view: malformed BAM record");
+			rec.resize(4 + (size_t)bs); memcpy(rec.data(), &bs, 4);
+			if (bi.get(rec.data() + 4, bs) != bs) die("view: truncated BAM");
+			if (!bam_record_to_sam(rec.data(), [&](int32_t t) -> const char* { return t < (int32_t)h.names.size() ? h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
+			if (text.size() > ((size_t)1 << 20)) { io_write_all(1, text.data(), text.size()); text.clear(); }
+		}
+		io_write_all(1, text.data(), text.size());
+		return 0;
+	}
+	if (!sam_in || strcmp(fmt, "bam")) die("view: only `-S -f bam` (SAM text to BAM), a BAM file as SAM text, and `-H` are supported");
 	/* fused stream (fused.h): the records already are BAM records; they pass through to `sambamba sort` untouched */
 	char first[8]; size_t n_first = 0;
 	while (n_first < 8) { ssize_t r = read(fd, first + n_first, 8 - n_first); if (r < 0) { if (errno == EINTR) continue; die("view: read error"); } if (r == 0) break; n_first += (size_t)r; }
@@ -1335,8 +1364,10 @@ int main(int argc, char **argv)
 #ifdef F_SETPIPE_SZ
 	(void)fcntl(0, F_SETPIPE_SZ, 1 << 20); (void)fcntl(1, F_SETPIPE_SZ, 1 << 20);   /* the reference's pipelines: fewer wake-ups per megabyte (fails harmlessly on files) */
 #endif
+	if (!strcmp(argv[1], "sort")) ssg_worker_begin();
+	inflate_hook_setup();
 	if (!strcmp(argv[1], "view")) return cmd_view(argc - 2, argv + 2);
-	if (!strcmp(argv[1], "sort")) { ssg_worker_begin(); ssg_stamp("sambamba_sort", "start"); const int rc = cmd_sort(argc - 2, argv + 2); ssg_stamp("sambamba_sort", "end"); ssg_worker_done(rc); return ssg_fast_exit(rc); }
+	if (!strcmp(argv[1], "sort")) { ssg_stamp("sambamba_sort", "start"); const int rc = cmd_sort(argc - 2, argv + 2); ssg_stamp("sambamba_sort", "end"); ssg_worker_done(rc); return ssg_fast_exit(rc); }
 	if (!strcmp(argv[1], "index")) { ssg_stamp("sambamba_index", "start"); const int rc = cmd_index(argc - 2, argv + 2); ssg_stamp("sambamba_index", "end"); return rc; }
 	if (!strcmp(argv[1], "flagstat")) return cmd_flagstat(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "merge")) return cmd_merge(argc - 2, argv + 2);

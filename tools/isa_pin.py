@@ -105,8 +105,12 @@ def main():
         return 0
     want = read_pins(golden)
     if "--write-new" in sys.argv:                                        # the kernels the pin does not know, into a file of their own
+        target = sys.argv[sys.argv.index("--write-new") + 1]
+        for extra in extras:                                             # (what another file of new kernels pins already stays there)
+            if os.path.abspath(extra) != os.path.abspath(target):
+                want.update(read_pins(extra))
         new = sorted(k for k in h if k not in want)
-        with open(sys.argv[sys.argv.index("--write-new") + 1], "w") as f:
+        with open(target, "w") as f:
             for k in new:
                 f.write("%s  %s\n" % (h[k], k))
         print("pinned %d new kernels" % len(new))
