@@ -163,7 +163,7 @@ SSG_DEVFN int ssg_sbfe6(uint32_t t, unsigned off) { return __builtin_amdgcn_sbfe
 #endif
 
 /* upstream ksw_extend2, one lane; Lc[j*64] is this lane's column j (query field already set); U = columns per trip of the cell loop */
-template <int U>
+template <int U, bool EQ>
 SSG_DEVFN ssg_ext_res_t ln_extend2(const ssg_mem_opt_t &opt, const ssg_index_view_t &ix, uint32_t *Lc, int qlen, int tlen, int64_t p0, int dir,
                                    int w, int end_bonus, int zdrop, int h0, unsigned long long *cells, unsigned int *tune_rowmax = 0, unsigned long long *tune_lane = 0)
 {
@@ -215,20 +215,21 @@ SSG_DEVFN ssg_ext_res_t ln_extend2(const ssg_mem_opt_t &opt, const ssg_index_vie
 		}
 		if (end > beg) {
 			ncell += (unsigned long long)(end - beg);
-			int mk = -1;                                 /* max over the row of (h << 9 | j): the largest h, at its last column (columns up to 320) */
-			auto cell = [&](const uint32_t wd, const int jj) -> uint32_t {
+			uint32_t mk = 0;                             /* max over the row of (h << 9 | j): the largest h, at its last column (columns up to 320); one max3 per column pair */
+			/* EQ (o_del + e_del == o_ins + e_ins, the instance the host chooses): one `M - (open + extend)' serves E and F.  The max3 are named (k_sw.h ssg_vmax3):
+			 * 83 VALU instructions a trip of four cells (87 without EQ), 91 where the compiler chose them */
+			auto cell = [&](const uint32_t wd, const int jj, uint32_t &key) -> uint32_t {
 				int M = SSG_XL_H(wd), e = SSG_XL_E(wd), h, t;
 				const int sc = ssg_sbfe6(T, SSG_XL_QS(wd));
 				M = M ? M + sc : 0;
-				h = M > e ? M : e;
-				h = h > f ? h : f;
-				{ const int k = h << 9 | jj; mk = mk > k ? mk : k; }
-				t = M - oe_del; t = t > 0 ? t : 0;
-				e -= e_del; e = e > t ? e : t;
+				h = ssg_vmax3(M, e, f);
+				key = (uint32_t)h << 9 | (uint32_t)jj;
+				t = M - oe_del;
+				e = ssg_vmax3z(e - e_del, t);
 				const uint32_t out = (wd & SSG_XL_QMASK) | ((uint32_t)e << 13) | (uint32_t)h1;
 				h1 = h;
-				t = M - oe_ins; t = t > 0 ? t : 0;
-				f -= e_ins; f = f > t ? f : t;
+				if (!EQ) t = M - oe_ins;
+				f = ssg_vmax3z(f - e_ins, t);
 				return out;
 			};
 			/* U columns per trip, the next U in flight meanwhile (the long class runs one wave per SIMD: nothing else hides LDS latency).  Whole trips carry no
@@ -238,11 +239,13 @@ SSG_DEVFN ssg_ext_res_t ln_extend2(const ssg_mem_opt_t &opt, const ssg_index_vie
 			for (j = beg; j + U <= end; j += U) {
 				uint32_t wn[U];
 				SSG_UNROLL for (int u = 0; u < U; ++u) wn[u] = Lc[(j + U + u) * 64];
-				SSG_UNROLL for (int u = 0; u < U; ++u) Lc[(j + u) * 64] = cell(wc[u], j + u);
+				uint32_t kk[U];
+				SSG_UNROLL for (int u = 0; u < U; ++u) Lc[(j + u) * 64] = cell(wc[u], j + u, kk[u]);
+				SSG_UNROLL for (int u = 0; u < U; u += 2) mk = ssg_umax3(mk, kk[u], kk[u + 1]);   /* one max3 per column pair */
 				SSG_UNROLL for (int u = 0; u < U; ++u) wc[u] = wn[u];
 			}
-			SSG_UNROLL for (int u = 0; u < U - 1; ++u) if (j + u < end) Lc[(j + u) * 64] = cell(wc[u], j + u);
-			mm = mk >> 9; mj = mk & 511;                 /* end > beg: at least one column */
+			SSG_UNROLL for (int u = 0; u < U - 1; ++u) if (j + u < end) { uint32_t k1; Lc[(j + u) * 64] = cell(wc[u], j + u, k1); mk = mk > k1 ? mk : k1; }
+			mm = (int)(mk >> 9); mj = (int)(mk & 511);                 /* end > beg: at least one column */
 			j = end;
 		} else j = beg;
 		Lc[end * 64] = (Lc[end * 64] & SSG_XL_QMASK) | (uint32_t)h1;
@@ -273,7 +276,7 @@ SSG_DEVFN ssg_ext_res_t ln_extend2(const ssg_mem_opt_t &opt, const ssg_index_vie
 /* side 0: left extensions (query and reference walked backwards from the seed); side 1: right extensions.
  * sorted[t] = (511 - side length) << 41 | (511 - expected rows) << 32 | job id; qcap+1 columns of LDS per lane. */
 /* one job of one side; L: the workgroup's (qcap + 2 U) x 64 words of LDS */
-template <int U>
+template <int U, bool EQ>
 SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt, const int side, const long job_first, const long n_jobs, const uint64_t *sorted,
                                 const ssg_xjob_t *jobs, const uint8_t *seq, const int64_t *read_off, ssg_xres_t *res_l, ssg_xres_t *res_r,
                                 unsigned long long *cells, uint32_t *L, const int qcap)
@@ -308,7 +311,7 @@ SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t 
 		for (int i = 0; i < SSG_XL_BAND_TRY; ++i) {
 			const int prev = score;
 			aw = opt.w << i;
-			x = ln_extend2<U>(opt, ix, Lc, qlen, tlen, jb.rbeg - 1, -1, aw, opt.pen_clip5, opt.zdrop, jb.len * opt.a, &nc SSG_XL_TUNE_ARGS(i));
+			x = ln_extend2<U, EQ>(opt, ix, Lc, qlen, tlen, jb.rbeg - 1, -1, aw, opt.pen_clip5, opt.zdrop, jb.len * opt.a, &nc SSG_XL_TUNE_ARGS(i));
 			score = x.score;
 			if (score == prev || x.max_off < (aw >> 1) + (aw >> 2)) break;
 		}
@@ -325,7 +328,7 @@ SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t 
 		for (int i = 0; i < SSG_XL_BAND_TRY; ++i) {
 			const int prev = score;
 			aw = opt.w << i;
-			x = ln_extend2<U>(opt, ix, Lc, qlen, tlen, jb.rbeg + jb.len, 1, aw, opt.pen_clip3, opt.zdrop, sc0, &nc SSG_XL_TUNE_ARGS(i));
+			x = ln_extend2<U, EQ>(opt, ix, Lc, qlen, tlen, jb.rbeg + jb.len, 1, aw, opt.pen_clip3, opt.zdrop, sc0, &nc SSG_XL_TUNE_ARGS(i));
 			score = x.score;
 			if (score == prev || x.max_off < (aw >> 1) + (aw >> 2)) break;
 		}
@@ -349,7 +352,7 @@ SSG_DEVFN void ssg_ext_lane_job(const ssg_index_view_t &ix, const ssg_mem_opt_t 
 /* The kernel, with as much LDS as the launch asks for ((qcap + 2 U) x 256 bytes: columns 0..qlen, and the 2U - 1 the cell loop may read ahead): the host cuts the
  * sorted job list into classes of 8 more columns each, so that a wave holds what its longest side needs -- 73..80 columns: 22 KB, seven waves a CU; 129..136: 37 KB,
  * four; a side of 100 of a 250-base read: 28 KB instead of the 68 KB of a fixed 256-column class (two waves a CU). */
-template <int U>
+template <int U, bool EQ>
 __global__ void __launch_bounds__(64) ssg_k_ext_lane_dyn(ssg_index_view_t ix, ssg_mem_opt_t opt, int side, long job_first, long n_jobs, const uint64_t *sorted,
                                const ssg_xjob_t *jobs, const uint8_t *seq, const int64_t *read_off, ssg_xres_t *res_l, ssg_xres_t *res_r,
                                unsigned long long *cells, int qcap)
@@ -360,7 +363,7 @@ __global__ void __launch_bounds__(64) ssg_k_ext_lane_dyn(ssg_index_view_t ix, ss
 	extern __shared__ uint32_t ssg_xl_lds[];
 	uint32_t *L = ssg_xl_lds;
 #endif
-	ssg_ext_lane_job<U>(ix, opt, side, job_first, n_jobs, sorted, jobs, seq, read_off, res_l, res_r, cells, L, qcap);
+	ssg_ext_lane_job<U, EQ>(ix, opt, side, job_first, n_jobs, sorted, jobs, seq, read_off, res_l, res_r, cells, L, qcap);
 }
 
 /* out[j] = number of keys whose side-length field (bits 41..49) is below t[j], in a list sorted ascending by it (= sides longer than 511 - t[j]): a binary search per threshold */

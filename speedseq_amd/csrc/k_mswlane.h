@@ -9,13 +9,23 @@
  *                     orientation that passes -> a job record in the anchor's slot, a sort key (padded query length, window length)
  *   ssg_k_msw_lane    the forward pass of ksw_align2 (oracle/orc_ksw.c local_sw: score, te, qe, b[] -> score2 / te2) for every job,
  *                     L LANES PER JOB (64 / L jobs per wavefront), the DP in strips of R = 8 target rows:
- *                       - a lane owns C = qp / L consecutive query columns; per column ONE LDS word holds the strip boundary
+ *                       - a lane owns C consecutive query columns; forward pass: C = qp / L, upstream's SSE-padded query length -- the pad
+ *                         columns (query code 5, score 0) are part of the result: column qlen + k hands H of the last query column of k + 1
+ *                         rows ago to the row maximum, and a b[] entry (score2 / te2) can come from nowhere else
+ *                         (tests/test_msw_lane_columns.py builds such windows).  The reverse pass keeps no b[] list, and a pad cell never
+ *                         exceeds every earlier row maximum, so it cannot set the running maximum, its row or its column: there
+ *                         C = roundup(longest query of the pass, 2 L) / L (152 columns for 150 bases at L = 4, not 160);
+ *                         per column ONE LDS word holds the strip boundary
  *                         (H of the row above the strip : 13 | E of the strip's first row : 13 | score-table offset of the query base : 5);
  *                         word (column * 64 + lane): bank = lane, conflict free.  One ds_read + one ds_write per EIGHT cells;
  *                       - the 8 rows of a strip run down a column in registers: H of the column to the left (the diagonal operand), F and the
- *                         row maximum per row, E handed down; 11 VALU per cell (bfe score, add, max3; shift-or + max for the row maximum and
- *                         its smallest column; 3 + 3 for E and F) against ~34 lane-operations per cell of the row-parallel wave form
- *                         (k_sw.h wv_local: 150 columns on 192 lane slots, two 6-step DPP scans per row);
+ *                         row maximum per row, E handed down; 9.5 VALU per cell where o_del + e_del == o_ins + e_ins (the instance EQ, chosen on
+ *                         the host: upstream's defaults), 10.5 otherwise: bfe score, add, max3 for H; H - (open + extend) once (EQ) or twice;
+ *                         subtract + max3 each for E and F; shift-or for the row key (H << 9 | 511 - column: the larger key of two equal scores
+ *                         is the smaller column) and ONE max3 per column pair that folds both keys into the row maximum.  With the unpacking
+ *                         and packing of the LDS words a trip of the column-pair loop (16 cells) is 170 VALU instructions (EQ; 186 otherwise;
+ *                         194 before the pair fold and the shared subtraction), against ~34 lane-operations per cell of the row-parallel
+ *                         wave form (k_sw.h wv_local: 150 columns on 192 lane slots, two 6-step DPP scans per row);
  *                       - lanes of a job are one strip apart (lane c works on strip s - c): the right edge of a strip (H, F, row maxima,
  *                         the diagonal) moves to the next lane by ONE wave_shr:1 DPP move per value and strip;
  *                       - target rows come straight from the 2-bit pac (3 byte loads per strip), no window copy in HBM.
@@ -49,7 +59,6 @@ SSG_DEVFN int ssg_sbfe5(uint32_t t, unsigned off) { return (int)(t << (27 - off)
 #else
 SSG_DEVFN int ssg_sbfe5(uint32_t t, unsigned off) { return __builtin_amdgcn_sbfe((int)t, off, 5u); }
 #endif
-SSG_DEVFN int ssg_max3(int a, int b, int c) { a = a > b ? a : b; return a > c ? a : c; }
 
 /* may this scoring / read go through the 13-bit cells and the 5-bit score table? */
 SSG_DEVFN bool ssg_ml_fits(const ssg_mem_opt_t &opt, int qlen)
@@ -95,7 +104,7 @@ template <bool REV> SSG_DEVFN uint32_t ssg_ml_rows8(const ssg_index_view_t &ix, 
  * (upstream appends at most every other row).
  * A chunk's jobs must share qp (the sort key's leading field); a job whose qp differs from the chunk's first is left (state 0).
  */
-template <int L, bool REV>
+template <int L, bool REV, bool EQ>
 __global__ void __launch_bounds__(64) ssg_k_msw_lane(ssg_index_view_t ix, ssg_mem_opt_t opt, long n_jobs, const uint64_t *sorted, const ssg_msjob_t *jobs,
                                const uint8_t *seq, ssg_msres_t *res, unsigned long long *bglb, unsigned int *queue, int ccap, int bcap, unsigned long long *cells, long n_slots, long seq_bytes)
 {
@@ -137,8 +146,9 @@ __global__ void __launch_bounds__(64) ssg_k_msw_lane(ssg_index_view_t ix, ssg_me
 		const int qp0 = wv_get(jb.qp, __ffsll(pm) - 1);
 		const bool have = pending && jb.qp == qp0;
 		pending = pending && !have;
-		const int C = qp0 / L;
-		if (C < 2 || C > ccap || C * L != qp0 || (C & 1)) continue;   /* wave-uniform; cannot happen with the host's launch parameters */
+		/* REV: the columns of the pass's longest query, an even number per lane (no b[] list: the pad columns cannot show, header comment) */
+		const int C = REV ? (wv_max(have ? jb.qlen : 0) + 2 * L - 1) / (2 * L) * 2 : qp0 / L;
+		if (C < 2 || C > ccap || (!REV && C * L != qp0) || (C & 1)) continue;   /* wave-uniform; cannot happen with the host's launch parameters */
 		const int tlen = have ? jb.tlen : 0;
 		const int nstrip = (wv_max(tlen) + R - 1) / R;
 		for (int cc = 0; cc < C + 2; ++cc) {       /* the lane's columns: query code -> table offset, H = E = 0 */
@@ -173,6 +183,7 @@ __global__ void __launch_bounds__(64) ssg_k_msw_lane(ssg_index_view_t ix, ssg_me
 				uint32_t w0 = Lc[0], w1 = Lc[64];
 				for (int cc = 0; cc < C; cc += 2) {
 					const uint32_t n0 = Lc[(cc + 2) * 64], n1 = Lc[(cc + 3) * 64];   /* next pair in flight (two spare columns behind the last) */
+					uint32_t k0[R];                                                       /* column cc's row keys: one max3 folds them and column cc + 1's into rm[] */
 					{	/* column cc: left neighbour in hA, result in hB */
 						const unsigned qs = SSG_ML_QS(w0);
 						int e = SSG_ML_E(w0), d = dg, h = 0;
@@ -180,15 +191,15 @@ __global__ void __launch_bounds__(64) ssg_k_msw_lane(ssg_index_view_t ix, ssg_me
 						SSG_UNROLL for (int r = 0; r < R; ++r) {
 							const int m = d + ssg_sbfe5(T[r], qs);
 							d = hA[r];
-							h = ssg_max3(m, e, f[r]);
+							h = ssg_vmax3(m, e, f[r]);
 							hB[r] = h;
-							{ const int k = h << 9 | tag; rm[r] = rm[r] > k ? rm[r] : k; }
-							e = ssg_max3(e - e_del, h - oe_del, 0);
-							f[r] = ssg_max3(f[r] - e_ins, h - oe_ins, 0);
+							k0[r] = (uint32_t)h << 9 | (uint32_t)tag;
+							const int g = h - oe_del;
+							e = ssg_max3(e - e_del, g, 0);
+							f[r] = ssg_max3(f[r] - e_ins, EQ ? g : h - oe_ins, 0);
 						}
 						Lc[cc * 64] = (uint32_t)h << 18 | (uint32_t)e << 5 | qs;
 					}
-					--tag;
 					{	/* column cc + 1: left neighbour in hB, result in hA */
 						const unsigned qs = SSG_ML_QS(w1);
 						int e = SSG_ML_E(w1), d = dg, h = 0;
@@ -196,15 +207,16 @@ __global__ void __launch_bounds__(64) ssg_k_msw_lane(ssg_index_view_t ix, ssg_me
 						SSG_UNROLL for (int r = 0; r < R; ++r) {
 							const int m = d + ssg_sbfe5(T[r], qs);
 							d = hB[r];
-							h = ssg_max3(m, e, f[r]);
+							h = ssg_vmax3(m, e, f[r]);
 							hA[r] = h;
-							{ const int k = h << 9 | tag; rm[r] = rm[r] > k ? rm[r] : k; }
-							e = ssg_max3(e - e_del, h - oe_del, 0);
-							f[r] = ssg_max3(f[r] - e_ins, h - oe_ins, 0);
+							rm[r] = (int)ssg_umax3((uint32_t)rm[r], k0[r], (uint32_t)h << 9 | (uint32_t)(tag - 1));
+							const int g = h - oe_del;
+							e = ssg_max3(e - e_del, g, 0);
+							f[r] = ssg_max3(f[r] - e_ins, EQ ? g : h - oe_ins, 0);
 						}
 						Lc[(cc + 1) * 64] = (uint32_t)h << 18 | (uint32_t)e << 5 | qs;
 					}
-					--tag;
+					tag -= 2;
 					w0 = n0; w1 = n1;
 				}
 				if (c == L - 1) {	/* the rows of this strip are complete: upstream's per-row bookkeeping, in row order */

@@ -35,6 +35,19 @@ SSG_DEVFN int sq_at(const ssg_seqv_t &s, int k) { return s.p[s.dir * k]; }
 /* upstream bwa_fill_scmat as arithmetic: t = target code 0..3(4), q = query code 0..4, 5 = pad column */
 SSG_DEVFN int ssg_sc(int a, int b, int t, int q) { return q > 4 ? 0 : (q > 3 || t > 3) ? -1 : (q == t ? a : -b); }
 
+/* max3 of the lane DP cells (k_mswlane.h, k_extlane.h).  ssg_vmax3 / ssg_vmax3z (third operand 0) NAME the instruction: E and F are never negative, and
+ * where a cell's H also feeds an unsigned expression (the row key H << 9 | column) or `H - (open + extend)' is shared by E and F, the compiler makes two
+ * instructions of what v_max3_i32 does in one (an unsigned second max; a clamped difference kept apart from the max). */
+SSG_DEVFN int ssg_max3(int a, int b, int c) { a = a > b ? a : b; return a > c ? a : c; }
+SSG_DEVFN uint32_t ssg_umax3(uint32_t a, uint32_t b, uint32_t c) { a = a > b ? a : b; return a > c ? a : c; }
+#ifdef SSG_EMU
+SSG_DEVFN int ssg_vmax3(int a, int b, int c) { return ssg_max3(a, b, c); }
+SSG_DEVFN int ssg_vmax3z(int a, int b) { return ssg_max3(a, b, 0); }
+#else
+SSG_DEVFN int ssg_vmax3(int a, int b, int c) { int h; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(h) : "v"(a), "v"(b), "v"(c)); return h; }
+SSG_DEVFN int ssg_vmax3z(int a, int b) { int h; asm("v_max3_i32 %0, %1, %2, 0" : "=v"(h) : "v"(a), "v"(b)); return h; }
+#endif
+
 /* uniform position of the first / last set lane of a ballot */
 SSG_DEVFN int ssg_first_lane(unsigned long long m) { return __ffsll(m) - 1; }
 SSG_DEVFN int ssg_last_lane(unsigned long long m) { return 63 - __clzll(m); }

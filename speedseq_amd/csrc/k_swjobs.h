@@ -23,7 +23,7 @@ __global__ void __launch_bounds__(256) ssg_k_align2_jobs(ssg_mem_opt_t opt, int 
  * job through the same ln_extend2 -- DP row in LDS words (13-bit h / e, 6-bit score table), target bases from a 2-bit pac.  A job's
  * target is `tlen' bases of the doubled coordinate system of the pac in `ix' from position toff in direction `dir' (+1 / -1), as the
  * product's left / right extensions read them; the query is qbuf[qoff .. qoff + qlen). */
-template <int QCAP>
+template <int QCAP, bool EQ>
 __global__ void __launch_bounds__(64) ssg_k_ext_lane_jobs(ssg_index_view_t ix, ssg_mem_opt_t opt, int n_jobs, const ssg_ext_job_t *jobs, const int64_t *tpos, int dir,
                                   const uint8_t *qbuf, ssg_ext_res_t *res, unsigned long long *cells)
 {
@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(64) ssg_k_ext_lane_jobs(ssg_index_view_t ix, s
 	for (int j = 0; j < jb.qlen; ++j) Lc[j * 64] = SSG_XL_QWORD(qbuf[jb.qoff + j]);
 	Lc[jb.qlen * 64] = 0;
 	unsigned long long nc = 0;
-	res[g] = ln_extend2<U>(opt, ix, Lc, jb.qlen, jb.tlen, tpos[g], dir, jb.w, jb.end_bonus, jb.zdrop, jb.h0, &nc);
+	res[g] = ln_extend2<U, EQ>(opt, ix, Lc, jb.qlen, jb.tlen, tpos[g], dir, jb.w, jb.end_bonus, jb.zdrop, jb.h0, &nc);
 	if (cells && nc) atomicAdd(cells, nc);
 }
 

@@ -436,10 +436,11 @@ int ssg_extend_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 	CHKA(dj); CHKA(dp); CHKA(dq); CHKA(dr); CHKA(dc);
 	CHK(dj.up(jobs, n_jobs)); CHK(dp.up(tpos, n_jobs)); CHK(dq.up(qbuf, qbytes)); CHK(dc.zero()); CHK(dr.zero());
 	const long nb = (n_jobs + 63) / 64;
-	if (qcap == 72) SSG_LAUNCH(ssg_k_ext_lane_jobs<72>, nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p);
-	else if (qcap == 136) SSG_LAUNCH(ssg_k_ext_lane_jobs<136>, nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p);
-	else if (qcap == 256) SSG_LAUNCH(ssg_k_ext_lane_jobs<256>, nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p);
-	else SSG_LAUNCH(ssg_k_ext_lane_jobs<320>, nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p);
+	const bool eq = opt->o_del + opt->e_del == opt->o_ins + opt->e_ins;   /* k_extlane.h: one `M - (open + extend)' per cell serves E and F */
+#define SSG_XJ_GO(QQ) do { if (eq) SSG_LAUNCH((ssg_k_ext_lane_jobs<QQ, true>), nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p); \
+                           else SSG_LAUNCH((ssg_k_ext_lane_jobs<QQ, false>), nb, 64, 0, idx->v, *opt, n_jobs, dj.p, dp.p, dir, dq.p, dr.p, dc.p); } while (0)
+	if (qcap == 72) SSG_XJ_GO(72); else if (qcap == 136) SSG_XJ_GO(136); else if (qcap == 256) SSG_XJ_GO(256); else SSG_XJ_GO(320);
+#undef SSG_XJ_GO
 	CHK(rt_sync());
 	CHK(dr.down(res, n_jobs));
 	if (cells) { unsigned long long c; CHK(dc.down(&c, 1)); *cells = c; }
@@ -502,10 +503,13 @@ static int run_msw_lane(const ssg_index_t *idx, const ssg_mem_opt_t *opt, long n
 	const int bcap = rev ? 1 : max_tlen / 2 + 2;
 	dbuf<unsigned long long> d_bl((size_t)grid * J * bcap);
 	CHKA(d_bl);
-#define SSG_ML_GO(LL, RR) SSG_LAUNCH((ssg_k_msw_lane<LL, RR>), grid, 64, lds, idx->v, *opt, nj, d_sorted.p, d_jobs, d_seq, d_res, d_bl.p, d_q.p, ccap, bcap, d_cells, n_slots, seq_bytes)
+	const bool eq = opt->o_del + opt->e_del == opt->o_ins + opt->e_ins;   /* then one `H - (open + extend)' per cell serves E and F (k_mswlane.h) */
+#define SSG_ML_GO3(LL, RR, EE) SSG_LAUNCH((ssg_k_msw_lane<LL, RR, EE>), grid, 64, lds, idx->v, *opt, nj, d_sorted.p, d_jobs, d_seq, d_res, d_bl.p, d_q.p, ccap, bcap, d_cells, n_slots, seq_bytes)
+#define SSG_ML_GO(LL, RR) do { if (eq) SSG_ML_GO3(LL, RR, true); else SSG_ML_GO3(LL, RR, false); } while (0)
 	if (rev) { if (lanes == 4) SSG_ML_GO(4, true); else if (lanes == 2) SSG_ML_GO(2, true); else SSG_ML_GO(1, true); }
 	else { if (lanes == 4) SSG_ML_GO(4, false); else if (lanes == 2) SSG_ML_GO(2, false); else SSG_ML_GO(1, false); }
 #undef SSG_ML_GO
+#undef SSG_ML_GO3
 	if (!rev) {	/* the reverse passes (KSW_XSTART) of the windows that call for one, the same way */
 		dbuf<uint64_t> d_rkeys((size_t)nj); dbuf<unsigned int> d_nr(2);
 		CHKA(d_rkeys); CHKA(d_nr); CHK(d_nr.zero());
@@ -1004,7 +1008,11 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 #ifndef SSG_EMU
 		if (max_len > 240) {   /* blocks above 64 KB */
 			static bool attr_set[SSG_MAX_DEV] = { false };
-			if (!attr_set[ssg_cur_dev]) { (void)hipFuncSetAttribute((const void*)ssg_k_ext_lane_dyn<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (320 + 8) * 256); attr_set[ssg_cur_dev] = true; }
+			if (!attr_set[ssg_cur_dev]) {
+				(void)hipFuncSetAttribute((const void*)ssg_k_ext_lane_dyn<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (320 + 8) * 256);
+				(void)hipFuncSetAttribute((const void*)ssg_k_ext_lane_dyn<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (320 + 8) * 256);
+				attr_set[ssg_cur_dev] = true;
+			}
 		}
 #endif
 		for (int side = 0; side < 2; ++side) {
@@ -1016,10 +1024,13 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 				/* (eight columns per trip instead of four -- twice the LDS loads in flight for the classes that run one wave a SIMD -- was measured slower on the MI355X:
 				 * 125.3 vs 119.4 ms at 2x150, 157.7 vs 151.3 at 2x250, profiles/r06f_ext_unroll_ab*.json: the cell loop waits for its own dependent VALU chain, not for LDS) */
 				const int c = caps[k], U = c > 72 ? 4 : 2; const size_t lds = (size_t)(c + 2 * U) * 256;
-#define SSG_XL_GO(LAUNCH, ...) do { if (U == 4) LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<4>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); \
-                                    else LAUNCH(__VA_ARGS__ ssg_k_ext_lane_dyn<2>, (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c); } while (0)
+				const bool xl_eq = opt->o_del + opt->e_del == opt->o_ins + opt->e_ins;   /* k_extlane.h: one `M - (open + extend)' per cell serves E and F */
+#define SSG_XL_GO1(LAUNCH, UU, EE, ...) LAUNCH(__VA_ARGS__ (ssg_k_ext_lane_dyn<UU, EE>), (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c)
+#define SSG_XL_GO(LAUNCH, ...) do { if (U == 4) { if (xl_eq) SSG_XL_GO1(LAUNCH, 4, true, __VA_ARGS__); else SSG_XL_GO1(LAUNCH, 4, false, __VA_ARGS__); } \
+                                    else { if (xl_eq) SSG_XL_GO1(LAUNCH, 2, true, __VA_ARGS__); else SSG_XL_GO1(LAUNCH, 2, false, __VA_ARGS__); } } while (0)
 				if (q % 3 == 0) SSG_XL_GO(SSG_LAUNCH); else if (q % 3 == 1) SSG_XL_GO(SSG_LAUNCH_ON, 0,); else SSG_XL_GO(SSG_LAUNCH_ON, 1,);
 #undef SSG_XL_GO
+#undef SSG_XL_GO1
 				++q;
 			}
 			ssg_join(2);

@@ -11,6 +11,9 @@ copied into tests/golden/ with the commit that ships those kernels.
 Kernels that a later change adds are pinned in a file of their own next to it (tests/golden/kernel_isa_<what>.sha256, written with --write-new
 once the suite is green on the GPU): the first file stays as it is, line for line, and every file is read.  A kernel may be pinned once;
 --write renews every file in place -- a kernel stays in the file that lists it, one that no file lists goes to kernel_isa.sha256.
+A change that rewrites a pinned kernel under another name (a template parameter more) leaves the old name without a kernel: --write-new also writes a line
+`retired  <name>' for every pinned kernel the library no longer has, and such a line takes the name out of the pin.  The kernels that replace it are new ones,
+pinned by that same file after their GPU run; a retired name that the library still has counts as new, so nothing escapes the alarm this way.
 usage: isa_pin.py [--write] [--write-new FILE] [--golden FILE] [--lib speedseq_amd/libssgpu.so]"""
 import glob
 import hashlib
@@ -23,6 +26,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_isa.sha256")
+RETIRED = "retired"
 
 
 def code_objects(lib):
@@ -92,7 +96,7 @@ def main():
     if "--write" in sys.argv:                                            # a kernel stays in the file that pins it; one no file knows goes to `golden'
         elsewhere = set()
         for extra in extras:
-            keep = sorted(k for k in read_pins(extra) if k in h and k not in elsewhere)
+            keep = sorted(k for k, v in read_pins(extra).items() if k in h and v != RETIRED and k not in elsewhere)
             elsewhere.update(keep)
             with open(extra, "w") as f:
                 for k in keep:
@@ -109,15 +113,21 @@ def main():
         for extra in extras:                                             # (what another file of new kernels pins already stays there)
             if os.path.abspath(extra) != os.path.abspath(target):
                 want.update(read_pins(extra))
-        new = sorted(k for k in h if k not in want)
+        new = sorted(k for k in h if k not in want or want[k] == RETIRED)
+        gone = sorted(k for k in want if k not in h and want[k] != RETIRED)
         with open(target, "w") as f:
             for k in new:
                 f.write("%s  %s\n" % (h[k], k))
-        print("pinned %d new kernels" % len(new))
+            for k in gone:
+                f.write("%s  %s\n" % (RETIRED, k))
+        print("pinned %d new kernels, retired %d" % (len(new), len(gone)))
         return 0
     if golden == GOLDEN:                                                 # ... and those files are part of the pin
         for extra in extras:
             more = read_pins(extra)
+            for k in [k for k in more if more[k] == RETIRED]:            # the name has no kernel any more: out of the pin (if the library has it after all, it is new)
+                want.pop(k, None)
+                del more[k]
             twice = sorted(k for k in more if k in want)
             if twice:
                 print("PINNED TWICE (%s)" % os.path.basename(extra), twice[0][:150])
