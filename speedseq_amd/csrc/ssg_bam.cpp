@@ -16,8 +16,6 @@
 #include "ssg_pe_int.h"
 
 SSG_ABI_FP_DEFINE(bam)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-#define CHKA(b) do { if (!(b).ok()) { ssg_err_msg = "device allocation failed: " #b; return SSG_ENOMEM; } } while (0)
 
 struct ssg_pe_bam {
 	int n_pairs = 0, n_batches = 0;

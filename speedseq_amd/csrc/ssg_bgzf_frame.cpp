@@ -11,7 +11,6 @@
 #include "ssg_index_int.h"
 
 SSG_ABI_FP_DEFINE(bgzf_frame)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 extern "C" {
 

@@ -12,7 +12,6 @@
 #include "../../include/ssgpu.h"
 #include "ssg_index_int.h"
 
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 static inline uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 

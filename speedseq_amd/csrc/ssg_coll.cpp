@@ -20,7 +20,6 @@
 #endif
 
 SSG_ABI_FP_DEFINE(coll)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 #ifndef SSG_EMU
 struct ssg_rccl_api {

@@ -15,8 +15,6 @@
 #include "../../include/ssgpu.h"
 #include "ssg_index_int.h"
 
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
 /* build-time arrays: straight from / back to the driver, never through the arena */
 template <class T> struct rbuf {
 	T *p; size_t n;
@@ -63,16 +61,16 @@ static int build_suffix_array(const uint8_t *d_T, int64_t n, uint64_t *d_SA)
 		uint64_t m = 0;
 		/* the bucket's suffixes in text order: per-workgroup counts straight from the text, their prefix sums, the scatter (k_index.h) */
 		SSG_LAUNCH(ssg_k_idx_bucket_count, n_wg, 256, 0, d_T, n, p, b, wg_cnt.p);
-		if ((rc = prim_exsum_u32_u64(wg_cnt.p, wg_off.p, n_wg))) break;
+		if ((rc = prim_exsum(wg_cnt.p, wg_off.p, n_wg + 1))) break;   /* n_wg + 1 items: wg_off[n_wg] = total (wg_cnt has the spare slot) */
 		if ((rc = rt_d2h(&m, wg_off.p + n_wg, 8))) break;
 		if (m == 0) continue;
 		rbuf<uint64_t> pos, key, ps, ks, grp; rbuf<int64_t> head, gh; rbuf<uint8_t> pend;
 		if (!pos.alloc(m) || !key.alloc(m) || !ps.alloc(m) || !ks.alloc(m) || !head.alloc(m) || !gh.alloc(m) || !pend.alloc(m)) { ssg_err_msg = "index construction: device allocation failed (bucket)"; rc = SSG_ENOMEM; break; }
 		SSG_LAUNCH(ssg_k_idx_bucket_scatter, n_wg, 256, 0, d_T, n, p, b, wg_off.p, pos.p);
 		SSG_LAUNCH(ssg_k_idx_key, nblk256((int64_t)m), 256, 0, d_T, pos.p, (int64_t)m, p, key.p);
-		if ((rc = prim_sort_pairs_u64(key.p, ks.p, pos.p, ps.p, (int64_t)m, 0, 64))) break;
+		if ((rc = prim_sort_pairs(key.p, ks.p, pos.p, ps.p, (int64_t)m, 0, 64)) || (rc = rt_sync())) break;
 		SSG_LAUNCH(ssg_k_idx_heads, nblk256((int64_t)m), 256, 0, ks.p, (int64_t)m, head.p);
-		if ((rc = prim_scan_max_i64(head.p, gh.p, (int64_t)m))) break;
+		if ((rc = prim_scan_max(head.p, gh.p, (int64_t)m)) || (rc = rt_sync())) break;
 		grp.p = key.take(); grp.n = m;   /* the unsorted keys are dead: reuse */
 		SSG_LAUNCH(ssg_k_idx_place, nblk256((int64_t)m), 256, 0, ps.p, gh.p, (int64_t)m, base, d_SA, rank.p, grp.p, pend.p);
 		uint64_t np = 0;
@@ -83,8 +81,8 @@ static int build_suffix_array(const uint8_t *d_T, int64_t n, uint64_t *d_SA)
 			chunks.push_back(c);
 			if (!c.pos || !c.grp) { ssg_err_msg = "index construction: device allocation failed (pending)"; rc = SSG_ENOMEM; break; }
 			uint64_t g1 = 0, g2 = 0;
-			if ((rc = prim_select_u64(ps.p, 0, pend.p, (int64_t)m, c.pos, &g1))) break;
-			if ((rc = prim_select_u64(grp.p, 0, pend.p, (int64_t)m, c.grp, &g2))) break;
+			if ((rc = prim_select(ps.p, pend.p, (int64_t)m, c.pos, &g1))) break;
+			if ((rc = prim_select(grp.p, pend.p, (int64_t)m, c.grp, &g2))) break;
 			n_pend += np;
 		}
 		if (idx_verbose()) fprintf(stderr, "[ssg index] bucket %u/%u: %llu suffixes, %llu not yet unique\n", b, n_bucket, (unsigned long long)m, (unsigned long long)np);
@@ -112,11 +110,11 @@ static int build_suffix_array(const uint8_t *d_T, int64_t n, uint64_t *d_SA)
 		rbuf<uint64_t> key2, iota, k2a, perma, grpa, grps, permb, poss, k2s, saidx, grpn; rbuf<int64_t> oh, ohs, nh, nhs; rbuf<uint8_t> pend;
 		RALLOC(key2, m); RALLOC(iota, m); RALLOC(k2a, m); RALLOC(perma, m);
 		SSG_LAUNCH(ssg_k_idx_key2, nblk256(m), 256, 0, P_pos.p, m, h, (uint64_t)n, rank.p, key2.p, iota.p);
-		CHK(prim_sort_pairs_u64(key2.p, k2a.p, iota.p, perma.p, m, 0, bits_n));
+		CHK(prim_sort_pairs(key2.p, k2a.p, iota.p, perma.p, m, 0, bits_n)); CHK(rt_sync());
 		iota.release(); k2a.release();
 		RALLOC(grpa, m); RALLOC(grps, m); RALLOC(permb, m);
 		SSG_LAUNCH(ssg_k_idx_gather, nblk256(m), 256, 0, perma.p, P_grp.p, m, grpa.p);
-		CHK(prim_sort_pairs_u64(grpa.p, grps.p, perma.p, permb.p, m, 0, bits_n));
+		CHK(prim_sort_pairs(grpa.p, grps.p, perma.p, permb.p, m, 0, bits_n)); CHK(rt_sync());
 		grpa.release(); perma.release();
 		RALLOC(poss, m); RALLOC(k2s, m);
 		SSG_LAUNCH(ssg_k_idx_gather, nblk256(m), 256, 0, permb.p, P_pos.p, m, poss.p);
@@ -125,11 +123,11 @@ static int build_suffix_array(const uint8_t *d_T, int64_t n, uint64_t *d_SA)
 		permb.release(); key2.release();
 		RALLOC(oh, m); RALLOC(ohs, m);
 		SSG_LAUNCH(ssg_k_idx_oldheads, nblk256(m), 256, 0, grps.p, m, oh.p);
-		CHK(prim_scan_max_i64(oh.p, ohs.p, m));
+		CHK(prim_scan_max(oh.p, ohs.p, m)); CHK(rt_sync());
 		oh.release();
 		RALLOC(saidx, m); RALLOC(nh, m); RALLOC(nhs, m);
 		SSG_LAUNCH(ssg_k_idx_newheads, nblk256(m), 256, 0, grps.p, k2s.p, ohs.p, m, saidx.p, nh.p);
-		CHK(prim_scan_max_i64(nh.p, nhs.p, m));
+		CHK(prim_scan_max(nh.p, nhs.p, m)); CHK(rt_sync());
 		nh.release(); ohs.release(); grps.release(); k2s.release();
 		RALLOC(grpn, m); RALLOC(pend, m);
 		SSG_LAUNCH(ssg_k_idx_replace, nblk256(m), 256, 0, poss.p, saidx.p, nhs.p, m, d_SA, rank.p, grpn.p, pend.p);
@@ -140,8 +138,8 @@ static int build_suffix_array(const uint8_t *d_T, int64_t n, uint64_t *d_SA)
 		if (np) {
 			uint64_t g1, g2;
 			RALLOC(npos, np); RALLOC(ngrp, np);
-			CHK(prim_select_u64(poss.p, 0, pend.p, m, npos.p, &g1));
-			CHK(prim_select_u64(grpn.p, 0, pend.p, m, ngrp.p, &g2));
+			CHK(prim_select(poss.p, pend.p, m, npos.p, &g1));
+			CHK(prim_select(grpn.p, pend.p, m, ngrp.p, &g2));
 		}
 		CHK(rt_sync());
 		P_pos.release(); P_grp.release();
@@ -199,7 +197,7 @@ static int build_from_fwd(const uint8_t *d_fwd, int64_t l_pac, ssg_index *ix)
 			RALLOC(row, nblk + 1);
 			CHK(rt_memset(row.p, 0, (nblk + 1) * 4));
 			CHK(rt_d2d(row.p, cnt.p + (size_t)c * nblk, nblk * 4));
-			CHK(prim_exsum_u32_u64(row.p, occ.p + (size_t)c * (nblk + 1), (int64_t)nblk));
+			CHK(prim_exsum(row.p, occ.p + (size_t)c * (nblk + 1), (int64_t)nblk + 1)); CHK(rt_sync());
 		}
 	}
 	SSG_LAUNCH(ssg_k_idx_bwt_write, nblk256((int64_t)nblk + 1), 256, 0, words.p, occ.p, (uint64_t)n, nblk, bwt.p);

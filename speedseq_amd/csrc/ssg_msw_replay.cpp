@@ -11,8 +11,6 @@
 #include "ssg_pe_int.h"
 
 SSG_ABI_FP_DEFINE(msw_replay)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-#define CHKA(b) do { if (!(b).ok()) { ssg_err_msg = "device allocation failed: " #b; return SSG_ENOMEM; } } while (0)
 static_assert(SSG_MSW_NCNT == SSG_MK_NCNT, "ssg_pe_int.h and k_mswkeys.h disagree about the counters");
 
 size_t ssg_msw_replay_scratch(long n_waves, size_t *slab_bytes)

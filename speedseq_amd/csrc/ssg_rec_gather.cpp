@@ -12,7 +12,6 @@
 #include "ssg_index_int.h"
 
 SSG_ABI_FP_DEFINE(rec_gather)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 /* the device mirror of the sort's record store (rec_store_t, sambamba_main.cpp): a chunk is a device allocation of its own, outside the arena -- gigabytes
  * that go back to the driver with the store -- with 16 bytes of slack behind it, so that a 16-byte load that starts inside a record stays inside */

@@ -12,6 +12,9 @@
 #include <string>
 
 extern thread_local std::string ssg_err_msg;
+/* return the first error; a device buffer (dbuf) that could not be allocated is SSG_ENOMEM (include/ssgpu.h, which the units that use CHKA include) */
+#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+#define CHKA(b) do { if (!(b).ok()) { ssg_err_msg = "device allocation failed: " #b; return SSG_ENOMEM; } } while (0)
 
 #ifdef SSG_EMU
 #include "emu.h"

@@ -10,7 +10,6 @@
 #include "ssg_index_int.h"
 
 SSG_ABI_FP_DEFINE(seed)
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; }
 /* rows (interval lists of one backward step) longer than this send a read to the wave-per-read kernel; only with an extension budget */
 static int budget_row(unsigned int max_ext) { return max_ext < 0x7fffffffu ? env_int("SSG_SMEM_MAX_ROW", 32) : 0x7fffffff; }

@@ -30,9 +30,7 @@
 #include "../../include/ssgpu.h"
 #include "ssg_index_int.h"
 #include "ssg_pe_int.h"
-#ifndef SSG_EMU
-#include <rocprim/rocprim.hpp>
-#endif
+#include "ssg_prim.h"
 
 thread_local std::string ssg_err_msg;
 thread_local int ssg_cur_dev = 0;
@@ -52,8 +50,6 @@ thread_local std::vector<ssg_prof_rec> ssg_prof_pending;
 #define SSG_STR_(x) #x
 #define SSG_STR(x) SSG_STR_(x)
 
-#define CHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-#define CHKA(b) do { if (!(b).ok()) { ssg_err_msg = "device allocation failed: " #b; return SSG_ENOMEM; } } while (0)
 
 /* the instance of a kernel templated on WIDE (k_sw.h): the one with the fifth register column only for a batch that has a read above 255 bases */
 #define SSG_LAUNCH_W(wide, kern, ...) do { if (wide) SSG_LAUNCH(kern<true>, __VA_ARGS__); else SSG_LAUNCH(kern<false>, __VA_ARGS__); } while (0)
@@ -80,12 +76,38 @@ extern "C" int ssg_abi_selfcheck(void)
 	}
 	return 0;
 }
-static int need_device()
+int ssg_need_device()
 {
 	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
 	return ssg_abi_selfcheck();
 }
-int ssg_need_device() { return need_device(); }
+
+/* ---- device-wide helpers over the shared primitives (ssg_prim.h); like them, none waits for the stream unless it says so ---- */
+/* exclusive prefix sum of n int32 counts into n + 1 int64 offsets, on the device; *total = out[n] (the download is the wait) */
+int ssg_dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t *total)
+{
+	if (n <= 0) { int64_t z = 0; CHK(rt_h2d(d_out, &z, 8)); *total = 0; return 0; }
+	CHK(prim_exsum(d_in, d_out, n));
+	SSG_LAUNCH(ssg_k_scan_tail, 1, 64, 0, d_in, d_out, n);
+	return rt_d2h(total, d_out + n, 8);
+}
+/* order[] = indices 0..n-1 by descending key (heaviest-first work lists; equal keys in index order), on the device */
+static int dev_order_desc(const int32_t *d_key, int32_t *d_order, long n)
+{
+	if (n <= 0) return 0;
+	dbuf<int32_t> iota(n), kout(n);
+	CHKA(iota); CHKA(kout);
+	SSG_LAUNCH(ssg_k_iota, (n + 255) / 256, 256, 0, iota.p, n);
+	return prim_sort_pairs_desc(d_key, kout.p, iota.p, d_order, n);
+}
+/* class counts of a device int32 array (ssg_k_class_counts) brought to the host */
+static int dev_class_counts(const int32_t *d_key, long n, int tA, int tB, int tC, unsigned int out[5])
+{
+	dbuf<unsigned int> d_c(8);
+	CHKA(d_c); CHK(d_c.zero());
+	if (n > 0) SSG_LAUNCH(ssg_k_class_counts, (n + 255) / 256, 256, 0, d_key, n, tA, tB, tC, d_c.p);
+	return d_c.down(out, 5);
+}
 
 extern "C" {
 
@@ -138,7 +160,7 @@ int ssg_index_from_arrays(const uint32_t *bwt, uint64_t bwt_words, uint64_t prim
                           const uint64_t *sa, uint64_t n_sa, int sa_intv, const uint8_t *pac, int64_t l_pac,
                           int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, ssg_index_t **out)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	ssg_index *ix = new ssg_index();
 	size_t pac_bytes = (size_t)(l_pac / 4 + 1);
 	ix->bwt_words = bwt_words;
@@ -211,7 +233,7 @@ static int stream_files_to_device(const std::vector<load_item_t> &items, int n_t
 int ssg_index_load(const char *prefix, ssg_index_t **out) { return ssg_index_load2(prefix, 0, out); }
 int ssg_index_densify(ssg_index_t *ix)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (!ix) { ssg_err_msg = "ssg_index_densify: no index"; return SSG_EINVAL; }
 	return densify_sa(ix);
 }
@@ -219,13 +241,13 @@ int ssg_index_densify(ssg_index_t *ix)
  * a sparser copy is not cheaper to make (measured: 1.0 s to every 16th row as to every 4th), only smaller. */
 int ssg_index_densify_to(ssg_index_t *ix, int intv)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (!ix || intv <= 0) { ssg_err_msg = "ssg_index_densify_to: bad arguments"; return SSG_EINVAL; }
 	return densify_sa(ix, intv);
 }
 int ssg_index_load2(const char *prefix, int defer_dense_sa, ssg_index_t **out)
 {	/* on-disk layout: SURVEY.md Appendix A (verified against the bundled example index) */
-	CHK(need_device());
+	CHK(ssg_need_device());
 	const auto t_begin = std::chrono::steady_clock::now();
 	std::string p(prefix);
 	FILE *fp = fopen((p + ".ann").c_str(), "r");
@@ -301,7 +323,7 @@ void ssg_index_destroy(ssg_index_t *ix)
 int ssg_index_from_device(const uint32_t *d_bwt, uint64_t primary, const uint64_t L2[5], const uint64_t *d_sa, int sa_intv,
                           const uint8_t *d_pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, ssg_index_t **out)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	ssg_index *ix = new ssg_index();
 	ix->bwt = 0; ix->sa = 0; ix->pac = 0; /* borrowed: not freed by ssg_index_destroy */
 	ix->ctg_off = (int64_t*)rt_malloc(n_ctg * 8); ix->ctg_len = (int32_t*)rt_malloc(n_ctg * 4);
@@ -404,7 +426,7 @@ int ssg_index_n_ctg(const ssg_index_t *ix) { return ix->v.n_ctg; }
 int ssg_extend_batch(const ssg_mem_opt_t *opt, int n_jobs, const ssg_ext_job_t *jobs, const uint8_t *qbuf, size_t qbytes,
                      const uint8_t *tbuf, size_t tbytes, ssg_ext_res_t *res, uint64_t *cells)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_jobs <= 0) return 0;
 	for (int i = 0; i < n_jobs; ++i) if (jobs[i].qlen > 318 || jobs[i].qlen < 0 || jobs[i].h0 <= 0) { ssg_err_msg = "ssg_extend_batch: qlen must be <= 318 and h0 > 0"; return SSG_EINVAL; }
 	dbuf<ssg_ext_job_t> dj(n_jobs); dbuf<uint8_t> dq(qbytes + 1), dt(tbytes + 1); dbuf<ssg_ext_res_t> dr(n_jobs); dbuf<unsigned long long> dc(1);
@@ -421,7 +443,7 @@ int ssg_extend_batch(const ssg_mem_opt_t *opt, int n_jobs, const ssg_ext_job_t *
 int ssg_extend_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_jobs, const ssg_ext_job_t *jobs, const int64_t *tpos, int dir,
                           const uint8_t *qbuf, size_t qbytes, int qcap, ssg_ext_res_t *res, uint64_t *cells)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_jobs <= 0) return 0;
 	if (qcap != 72 && qcap != 136 && qcap != 256 && qcap != 320) { ssg_err_msg = "ssg_extend_lane_batch: qcap is 72, 136, 256 or 320"; return SSG_EINVAL; }
 	if (dir != 1 && dir != -1) { ssg_err_msg = "ssg_extend_lane_batch: dir is +1 or -1"; return SSG_EINVAL; }
@@ -450,7 +472,7 @@ int ssg_extend_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 int ssg_align2_batch(const ssg_mem_opt_t *opt, int n_jobs, const ssg_sw_job_t *jobs, const uint8_t *qbuf, size_t qbytes,
                      const uint8_t *tbuf, size_t tbytes, ssg_kswr_t *res)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_jobs <= 0) return 0;
 	int max_t = 1;
 	for (int i = 0; i < n_jobs; ++i) { if (jobs[i].qlen > 320 || jobs[i].qlen < 1) { ssg_err_msg = "ssg_align2_batch: 1 <= qlen <= 320"; return SSG_EINVAL; } max_t = std::max(max_t, jobs[i].tlen); }
@@ -463,7 +485,6 @@ int ssg_align2_batch(const ssg_mem_opt_t *opt, int n_jobs, const ssg_sw_job_t *j
 	return dr.down(res, n_jobs);
 }
 
-static int sort_keys_u64(uint64_t *k_in, uint64_t *k_out, long n, int begin_bit, int end_bit);
 /* The forward passes of nj mate-rescue windows (k_mswlane.h): d_keys[nj] = qp << 48 | tlen << 32 | slot (unsorted; sorted here so that a
  * wavefront's jobs share the padded query length and have similar window lengths), results into d_res[slot].  lanes = 1, 2 or 4 per job;
  * max_qp / max_tlen = the largest padded query length / window length among the jobs (LDS columns per lane = max_qp / lanes;
@@ -477,7 +498,7 @@ static int run_msw_lane(const ssg_index_t *idx, const ssg_mem_opt_t *opt, long n
 	CHKA(d_sorted); CHKA(d_q); CHK(d_q.zero());
 	/* bits [32, 58): padded query length (<= 256 at bit 48) over window length (< 2^16).  NOT [32, 64): the radix sort of ROCm 7.2 (met through hipCUB, the same code underneath) returns
 	 * a list that is not even a permutation of its input for that range of 64-bit keys (tools/dbg/sort_probe.cpp) */
-	CHK(sort_keys_u64(d_keys, d_sorted.p, nj, 32, 58));
+	CHK(prim_sort_keys(d_keys, d_sorted.p, nj, 32, 58));
 	STAGE("msw_sort");
 	if (ssg_debug() >= 2) {	/* diagnostic: the sorted list is a permutation of the keys, in order, and every key names a plausible job */
 		std::vector<uint64_t> hk((size_t)nj), hs((size_t)nj);
@@ -529,7 +550,7 @@ static int run_msw_lane(const ssg_index_t *idx, const ssg_mem_opt_t *opt, long n
  * upstream's introsort (out_lane); the two must be equal word for word */
 int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *out_wave)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n < 0 || n > 5120) { ssg_err_msg = "ssg_dbg_chain_sort: 0 <= n <= 5120"; return SSG_EINVAL; }
 	dbuf<int64_t> d_in((size_t)n + 1), d_o0((size_t)n + 1), d_o1((size_t)n + 1);
 	CHKA(d_in); CHKA(d_o0); CHKA(d_o1);
@@ -544,7 +565,7 @@ int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *o
 int ssg_align2_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_jobs, const ssg_sw_job_t *jobs, const int64_t *tpos,
                           const uint8_t *qbuf, size_t qbytes, int lanes, ssg_kswr_t *res, int32_t *from_lane)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_jobs <= 0) return 0;
 	int max_t = 1, max_qp = 16;
 	std::vector<ssg_msjob_t> hj((size_t)n_jobs); std::vector<uint64_t> hk;
@@ -577,7 +598,7 @@ int ssg_align2_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 int ssg_global_batch(const ssg_mem_opt_t *opt, int n_jobs, const ssg_glb_job_t *jobs, const uint8_t *qbuf, size_t qbytes,
                      const uint8_t *tbuf, size_t tbytes, int32_t *score, int32_t *n_cigar, uint32_t *cigar, int cap)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_jobs <= 0) return 0;
 	long zmax = 1;
 	for (int i = 0; i < n_jobs; ++i) {
@@ -601,8 +622,6 @@ struct seed_stage_t {
 
 /* runs the SMEM kernel for all reads (cap0 per read), then re-runs overflowing reads with a
  * private large capacity and copies their lists back; on return every n_intv[r] >= 0. */
-static int dev_class_counts(const int32_t *d_key, long n, int tA, int tB, int tC, unsigned int out[5]);
-static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n);
 /* upstream's ks_introsort(mem_intv) of every read's list (k_seed.h): a lane per read ranks the lists of up to 24 intervals, a wave per read the longer ones */
 static int launch_smem_sort(int n_reads, ssg_intv_t *d_intv, const int32_t *d_n, int cap)
 {
@@ -667,7 +686,7 @@ static int run_smem(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_read
 int ssg_smem_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
                    int cap, ssg_intv_t *out_intv, int32_t *out_n)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_reads <= 0) return 0;
 	int max_len = 0; for (int r = 0; r < n_reads; ++r) max_len = std::max<int>(max_len, (int)(off[r+1] - off[r]));
 	dbuf<uint8_t> d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_off(n_reads + 1); dbuf<ssg_intv_t> d_intv((size_t)n_reads * cap); dbuf<int32_t> d_n(n_reads);
@@ -676,109 +695,6 @@ int ssg_smem_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads
 	CHK(run_smem(idx, opt, n_reads, d_seq.p, d_off.p, max_len, cap, d_intv.p, d_n.p));
 	CHK(d_intv.down(out_intv, (size_t)n_reads * cap));
 	return d_n.down(out_n, n_reads);
-}
-
-/* permutation of 0..n-1 by descending key (counting sort on the clipped key; stable) */
-static void order_desc(const std::vector<int32_t> &key, std::vector<int32_t> &order)
-{
-	const int K = 1 << 16;
-	std::vector<int64_t> cnt(K + 1, 0);
-	for (int32_t k : key) ++cnt[K - 1 - std::min(std::max(k, 0), K - 1)];
-	int64_t s = 0;
-	for (int i = 0; i < K; ++i) { int64_t c = cnt[i]; cnt[i] = s; s += c; }
-	order.resize(key.size());
-	for (size_t i = 0; i < key.size(); ++i) order[cnt[K - 1 - std::min(std::max(key[i], 0), K - 1)]++] = (int32_t)i;
-}
-
-/* radix sort of 64-bit keys on bits [begin_bit, end_bit) (stable) */
-static int sort_keys_u64(uint64_t *k_in, uint64_t *k_out, long n, int begin_bit, int end_bit)
-{
-	if (n <= 0) return 0;
-#ifdef SSG_EMU
-	const uint64_t mask = (end_bit >= 64 ? ~0ull : (1ull << end_bit) - 1) & ~((1ull << begin_bit) - 1);
-	std::vector<uint64_t> v(k_in, k_in + n);
-	std::stable_sort(v.begin(), v.end(), [&](uint64_t a, uint64_t b) { return (a & mask) < (b & mask); });
-	memcpy(k_out, v.data(), (size_t)n * 8);
-	return 0;
-#else
-	size_t tmp_bytes = 0;
-	if (rocprim::radix_sort_keys(nullptr, tmp_bytes, k_in, k_out, (size_t)n, (unsigned)begin_bit, (unsigned)end_bit) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_keys (size query) failed"; return SSG_EHIP; }
-	dbuf<uint8_t> tmp(tmp_bytes);
-	CHKA(tmp);
-	if (rocprim::radix_sort_keys(tmp.p, tmp_bytes, k_in, k_out, (size_t)n, (unsigned)begin_bit, (unsigned)end_bit, ssg_stream) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_keys failed"; return SSG_EHIP; }
-	return 0;
-#endif
-}
-
-/* exclusive prefix sum of n int32 counts into n+1 int64 offsets, on the device; *total = out[n] */
-struct ssg_to_i64 { SSG_DEVMEM int64_t operator()(int32_t v) const { return (int64_t)v; } };
-static int dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t *total)
-{
-	if (n <= 0) { int64_t z = 0; CHK(rt_h2d(d_out, &z, 8)); *total = 0; return 0; }
-#ifdef SSG_EMU
-	int64_t t = 0; for (long i = 0; i < n; ++i) { d_out[i] = t; t += d_in[i]; } d_out[n] = t; *total = t;
-	return 0;
-#else
-	rocprim::transform_iterator<const int32_t*, ssg_to_i64, int64_t> it(d_in, ssg_to_i64());
-	size_t tmp_bytes = 0;
-	if (rocprim::exclusive_scan(nullptr, tmp_bytes, it, d_out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>()) != hipSuccess) { ssg_err_msg = "rocprim exclusive_scan (size query) failed"; return SSG_EHIP; }
-	dbuf<uint8_t> tmp(tmp_bytes + 16);
-	CHKA(tmp);
-	if (rocprim::exclusive_scan(tmp.p, tmp_bytes, it, d_out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), ssg_stream) != hipSuccess) { ssg_err_msg = "rocprim exclusive_scan failed"; return SSG_EHIP; }
-	SSG_LAUNCH(ssg_k_scan_tail, 1, 64, 0, d_in, d_out, n);
-	return rt_d2h(total, d_out + n, 8);
-#endif
-}
-
-/* out[i] = max(in[0..i]) */
-#ifndef SSG_EMU
-struct ssg_max_i32 { __device__ int32_t operator()(const int32_t &a, const int32_t &b) const { return a > b ? a : b; } };
-#endif
-static int dev_scan_max_i32(const int32_t *d_in, int32_t *d_out, long n)
-{
-	if (n <= 0) return 0;
-#ifdef SSG_EMU
-	int32_t m = d_in[0]; for (long i = 0; i < n; ++i) { m = d_in[i] > m ? d_in[i] : m; d_out[i] = m; }
-	return 0;
-#else
-	size_t tmp_bytes = 0;
-	if (rocprim::inclusive_scan(nullptr, tmp_bytes, d_in, d_out, (size_t)n, ssg_max_i32()) != hipSuccess) { ssg_err_msg = "rocprim inclusive_scan (size query) failed"; return SSG_EHIP; }
-	dbuf<uint8_t> tmp(tmp_bytes + 16);
-	CHKA(tmp);
-	if (rocprim::inclusive_scan(tmp.p, tmp_bytes, d_in, d_out, (size_t)n, ssg_max_i32(), ssg_stream) != hipSuccess) { ssg_err_msg = "rocprim inclusive_scan failed"; return SSG_EHIP; }
-	return 0;
-#endif
-}
-
-/* order[] = indices 0..n-1 by descending key (heaviest-first work lists), on the device */
-static int dev_order_desc(const int32_t *d_key, int32_t *d_order, long n)
-{
-	if (n <= 0) return 0;
-#ifdef SSG_EMU
-	std::vector<int32_t> key(d_key, d_key + n), ord;
-	order_desc(key, ord);
-	memcpy(d_order, ord.data(), (size_t)n * 4);
-	return 0;
-#else
-	dbuf<int32_t> iota(n), kout(n);
-	CHKA(iota); CHKA(kout);
-	SSG_LAUNCH(ssg_k_iota, (n + 255) / 256, 256, 0, iota.p, n);
-	size_t tmp_bytes = 0;
-	if (rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, d_key, kout.p, iota.p, d_order, (size_t)n, 0u, 32u) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_pairs_desc (size query) failed"; return SSG_EHIP; }
-	dbuf<uint8_t> tmp(tmp_bytes + 16);
-	CHKA(tmp);
-	if (rocprim::radix_sort_pairs_desc(tmp.p, tmp_bytes, d_key, kout.p, iota.p, d_order, (size_t)n, 0u, 32u, ssg_stream) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_pairs_desc failed"; return SSG_EHIP; }
-	return rt_sync();   /* the temporaries are released on return */
-#endif
-}
-
-/* class counts of a device int32 array (ssg_k_class_counts) brought to the host */
-static int dev_class_counts(const int32_t *d_key, long n, int tA, int tB, int tC, unsigned int out[5])
-{
-	dbuf<unsigned int> d_c(8);
-	CHKA(d_c); CHK(d_c.zero());
-	if (n > 0) SSG_LAUNCH(ssg_k_class_counts, (n + 255) / 256, 256, 0, d_key, n, tA, tB, tC, d_c.p);
-	return d_c.down(out, 5);
 }
 
 /* ------------------------------- mem_align1_core for a batch ------------------------------- */
@@ -801,18 +717,19 @@ static int run_locate(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	SSG_LAUNCH(ssg_k_sal_count, (n_reads + block - 1) / block, block, 0, *opt, n_reads, d_intv, d_nintv, cap, d_nseed, d_pre.p);
 	CHK(rt_sync());
 	STAGE("sal_count");
-	CHK(dev_exclusive_scan(d_nseed, seed_off, n_reads, tot));
+	CHK(ssg_dev_exclusive_scan(d_nseed, seed_off, n_reads, tot));
 	const long g = (long)*tot;
 	if (!seeds.alloc((size_t)g + 1) || !srid.alloc((size_t)g + 1) || !mark.alloc((size_t)g + 1) || !read_of.alloc((size_t)g + 1)) { ssg_err_msg = "device allocation failed: seeds"; return SSG_ENOMEM; }
 	if (g > 0) {
 		CHK(rt_memset(mark.p, 0, (size_t)g * 4));
 		SSG_LAUNCH(ssg_k_sal_mark, (n_reads + block - 1) / block, block, 0, n_reads, (const int64_t*)seed_off, mark.p);
-		CHK(dev_scan_max_i32(mark.p, read_of.p, g));
+		CHK(prim_scan_max(mark.p, read_of.p, g));
 	}
 	SSG_LAUNCH(ssg_k_sal, (g + block - 1) / block, block, 0, idx->v, *opt, n_reads, d_intv, d_nintv, cap, (const int64_t*)seed_off, seeds.p, srid.p, (const int32_t*)d_pre.p, (const int32_t*)read_of.p);
 	return 0;   /* d_pre (1.5 GB per million pairs) back to the lane's arena: whatever takes it next is queued behind the kernel above */
 }
 
+static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n);   /* (defined behind the pairing stage: see there) */
 static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len,
                       align1_dev_t &o, uint64_t stats[8])
 {
@@ -855,7 +772,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	/* heaviest-first work order (seed count): the per-read cost of chaining / extension is heavy-tailed */
 	dbuf<int32_t> d_work(n_reads); dbuf<unsigned int> d_queue(8);
 	CHKA(d_work); CHKA(d_queue);
-	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(d_queue.zero());
+	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());
 	if (ssg_debug() >= 2) { /* tuning: seeds-per-read histogram (power-of-two bins) */
 		std::vector<int32_t> hns(n_reads);
 		CHK(d_nseed.down(hns.data(), n_reads));
@@ -917,13 +834,13 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 			if (!d_hoff.alloc((size_t)n_heavy + 1)) { ssg_err_msg = "device allocation failed: d_hoff"; return SSG_ENOMEM; }
 			SSG_LAUNCH(ssg_k_chw_count, (n_heavy + 255) / 256, 256, 0, n_heavy, d_work.p, o.seed_off.p, d_hns.p);
 			int64_t n_hs = 0;
-			CHK(dev_exclusive_scan(d_hns.p, d_hoff.p, n_heavy, &n_hs));
+			CHK(ssg_dev_exclusive_scan(d_hns.p, d_hoff.p, n_heavy, &n_hs));
 			if (n_hs >= (1LL << 32)) { ssg_err_msg = "more than 2^32 seeds in repeat-heavy reads of one call"; return SSG_EOVERFLOW; }
 			dbuf<uint64_t> d_hk((size_t)n_hs + 1), d_hks((size_t)n_hs + 1); dbuf<uint32_t> d_hv((size_t)n_hs + 1), d_hvs((size_t)n_hs + 1);
 			CHKA(d_hk); CHKA(d_hks); CHKA(d_hv); CHKA(d_hvs);
 			if (!d_hrank.alloc((size_t)n_hs + 1)) { ssg_err_msg = "device allocation failed: d_hrank"; return SSG_ENOMEM; }
 			SSG_LAUNCH(ssg_k_chw_keys, n_heavy, 64, 0, n_heavy, d_work.p, o.seed_off.p, d_seeds.p, d_hoff.p, d_hk.p, d_hv.p);
-			CHK(sort_pairs_u64(d_hk.p, d_hks.p, d_hv.p, d_hvs.p, (long)n_hs));
+			CHK(sort_pairs_u64(d_hk.p, d_hks.p, d_hv.p, d_hvs.p, (long)n_hs)); CHK(rt_sync());
 			SSG_LAUNCH(ssg_k_chw_ranks, (n_hs + 255) / 256, 256, 0, (long)n_hs, d_hks.p, d_hvs.p, d_hoff.p, d_hrank.p);
 			CHK(rt_sync());
 		}
@@ -976,7 +893,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	dbuf<int64_t> d_choff((size_t)n_reads + 1);
 	CHKA(d_choff);
 	int64_t n_jobs64 = 0;
-	CHK(dev_exclusive_scan(d_nchain.p, d_choff.p, n_reads, &n_jobs64));
+	CHK(ssg_dev_exclusive_scan(d_nchain.p, d_choff.p, n_reads, &n_jobs64));
 	if (n_jobs64 >= (int64_t)1 << 31) { ssg_err_msg = "more than 2^31 chains in one call"; return SSG_EOVERFLOW; }
 	const long n_jobs = (long)n_jobs64;
 	dbuf<ssg_xjob_t> d_xjobs((size_t)n_jobs + 1); dbuf<ssg_xres_t> d_xl((size_t)n_jobs + 1), d_xr((size_t)n_jobs + 1);
@@ -989,7 +906,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
 		SSG_LAUNCH(ssg_k_ext_prep, (n_jobs + 255) / 256, 256, 0, idx->v, *opt, n_reads, n_jobs, d_off, o.seed_off.p, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p,
 		           d_choff.p, d_seq, (int)SSG_TWIN_GLB, d_xjobs.p, d_kl.p, d_kr.p);
-		CHK(sort_keys_u64(d_kl.p, d_sl.p, n_jobs, 32, 50)); CHK(sort_keys_u64(d_kr.p, d_sr.p, n_jobs, 32, 50));   /* 9 + 9 bits: 511 - side length, 511 - expected rows */
+		CHK(prim_sort_keys(d_kl.p, d_sl.p, n_jobs, 32, 50)); CHK(prim_sort_keys(d_kr.p, d_sr.p, n_jobs, 32, 50));   /* 9 + 9 bits: 511 - side length, 511 - expected rows */
 		if (ssg_debug()) fprintf(stderr, "[ssgpu] ext jobs %ld\n", n_jobs);
 		/* Classes of 8 more columns each, a launch per class with the LDS its longest side needs (k_extlane.h ssg_k_ext_lane_dyn): the list is sorted longest side first, the
 		 * class boundaries are binary searches; a side's classes go round three queues (no tail of one launch before the next starts, and a CU holds a mix of block sizes),
@@ -1062,7 +979,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
                     int64_t *seed_off, ssg_seed_t **seeds, int32_t **rids)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	*seeds = 0; *rids = 0;
 	if (n_reads <= 0) { if (seed_off) seed_off[0] = 0; return 0; }
 	int max_len = 0; for (int r = 0; r < n_reads; ++r) max_len = std::max<int>(max_len, (int)(off[r+1] - off[r]));
@@ -1093,7 +1010,7 @@ int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_read
 int ssg_align1_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
                      int64_t *reg_off, ssg_alnreg_t **regs, uint64_t stats[8])
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	*regs = 0;
 	if (n_reads <= 0) { if (reg_off) reg_off[0] = 0; return 0; }
 	int max_len = 0; for (int r = 0; r < n_reads; ++r) max_len = std::max<int>(max_len, (int)(off[r+1] - off[r]));
@@ -1157,7 +1074,7 @@ static void host_pestat(const ssg_mem_opt_t *opt, const uint32_t *hist /* [4][SS
 }
 
 /* upstream mem_pestat for every batch of the call: candidate selection and the insert-size histograms on the device (ssg_k_pestat_hist), quartiles, mean, std
- * and the fences on the host (host_pestat).  The pipeline (pe_core) and the test entry ssg_dbg_pestat both come through here. */
+ * and the fences on the host (host_pestat).  The pipeline (ssg_pe_core) and the test entry ssg_dbg_pestat both come through here. */
 static int run_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg,
                       const int32_t *d_pb, int n_batches, ssg_pestat_t *pes /* n_batches x 4 */)
 {
@@ -1226,7 +1143,7 @@ extern "C" void ssg_dbg_reg2aln_counts(unsigned int out[4]) { for (int k = 0; k 
 /* mem_sam_pe after mate rescue, for all pairs: primary marking, pairing, MAPQ, record selection (k_pair.h, k_pairw.h), on the region slices reg_off (t2 slots in
  * all) and request slices req_off that ssg_k_pair_caps sized; pair_key = the pairs' region counts, pair_order = the pairs heaviest first, err zeroed by the caller.
  * Which kernel form takes which pair is decided here and nowhere else (SSG_PAIR_WAVE_MIN, SSG_PAIR_LDS); a pair beyond an on-device capacity ends the call with
- * SSG_EOVERFLOW.  The pipeline (pe_core) and the test entry ssg_dbg_pair_final both come through here. */
+ * SSG_EOVERFLOW.  The pipeline (ssg_pe_core) and the test entry ssg_dbg_pair_final both come through here. */
 static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, int64_t t2, const int64_t *d_r2off, ssg_alnreg_t *d_regs2, const int32_t *d_nreg,
                           const int32_t *d_pb, const ssg_pestat_t *d_pes, const int32_t *d_pkey, const int32_t *d_pw, int32_t *d_zbuf,
                           const int64_t *d_reqoff, ssg_alnreq_t *d_req, int32_t *d_nreq, int32_t *d_perr, unsigned int *d_q)
@@ -1280,7 +1197,7 @@ static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 
 /* upstream mem_matesw for all pairs, on the pairing-stage slices (d_r2off, head-room included) with n_reg updated in place: which pairs need it (ssg_k_matesw_need), their
  * windows ahead of the decision (k_mswlane.h), the list logic (k_mswkeys.h, and ssg_k_matesw for what that kernel leaves).  d_cnt: SW cells, windows, windows taken from
- * slots; d_perr: ssg_k_matesw's error codes.  The pipeline (pe_core) and the test entry ssg_dbg_matesw both come through here. */
+ * slots; d_perr: ssg_k_matesw's error codes.  The pipeline (ssg_pe_core) and the test entry ssg_dbg_matesw both come through here. */
 struct msw_stage_t { unsigned long long cells, windows, from_slots, left_windows; unsigned int listed, taken, left; };
 static thread_local msw_stage_t ssg_msw_last;   /* of this thread's last rescue stage (ssg_dbg_matesw_last) */
 static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq, const int64_t *d_off, int max_len, const int64_t *d_r2off, ssg_alnreg_t *d_regs2,
@@ -1310,7 +1227,7 @@ static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pa
 			SSG_LAUNCH(ssg_k_msw_count, (n_todo + 63) / 64, 64, 0, *opt, (int)n_todo, d_mtodo.p, d_r2off, d_regs2, d_nreg, d_jcnt.p);
 			int64_t nslot = 0;
 			STAGE("msw_count");
-			CHK(dev_exclusive_scan(d_jcnt.p, d_jbase.p, 2L * n_todo, &nslot));
+			CHK(ssg_dev_exclusive_scan(d_jcnt.p, d_jbase.p, 2L * n_todo, &nslot));
 			STAGE("msw_scan");
 			if (nslot > 0 && nslot < (1LL << 31)) {
 				dbuf<ssg_msjob_t> d_jobs((size_t)nslot); dbuf<uint64_t> d_keys((size_t)nslot); dbuf<unsigned int> d_nj(2);   /* windows; the longest */
@@ -1362,74 +1279,92 @@ static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pa
 	return 0;
 }
 
-static int pe_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq_p, const int64_t *d_off_p, int max_len,
-                   const int32_t *d_pb_p, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep)
+/* The pairing stage's slices, for the pipeline (ssg_pe_core) and the test entry ssg_dbg_pair_final alike: per read a region slice with head-room for rescued
+ * hits (d_r2off, t2 slots in all) and a request slice (d_reqoff, tq slots), as ssg_k_pair_caps sizes them (d_cap2, d_capq); d_pkey = the pairs' region counts,
+ * d_pw = the pairs heaviest first (key: candidate regions of both ends); d_regs2 = the regions (d_regoff, d_regs, d_nreg) copied into their slices. */
+struct pair_slices_t {
+	dbuf<int32_t> d_cap2, d_capq, d_pkey, d_pw; dbuf<int64_t> d_r2off, d_reqoff; dbuf<ssg_alnreg_t> d_regs2; int64_t t2, tq;
+};
+static int make_pair_slices(int n_reads, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg, int max_matesw, pair_slices_t &s)
 {
-	const int n_reads = 2 * n_pairs;
-	struct { const uint8_t *p; } d_seq = { d_seq_p };
-	struct { const int64_t *p; } d_off = { d_off_p };
-	struct { const int32_t *p; } d_pb = { d_pb_p };
-	res->n_reads = n_reads; res->n_batches = n_batches; memset(res->stats, 0, sizeof(res->stats));
-	align1_dev_t a1;
-	CHK(run_align1(idx, opt, n_reads, d_seq.p, d_off.p, max_len, a1, res->stats));
+	const int n_pairs = n_reads / 2, block = 256;
+	if (!s.d_cap2.alloc(n_reads) || !s.d_capq.alloc(n_reads) || !s.d_pkey.alloc(n_pairs) || !s.d_pw.alloc(n_pairs) || !s.d_r2off.alloc(n_reads + 1) || !s.d_reqoff.alloc(n_reads + 1)) {
+		ssg_err_msg = "device allocation failed: pairing-stage slices"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_pair_caps, (n_reads + block - 1) / block, block, 0, n_reads, d_nreg, max_matesw, s.d_cap2.p, s.d_capq.p, s.d_pkey.p);
+	CHK(ssg_dev_exclusive_scan(s.d_cap2.p, s.d_r2off.p, n_reads, &s.t2)); CHK(ssg_dev_exclusive_scan(s.d_capq.p, s.d_reqoff.p, n_reads, &s.tq));
+	CHK(dev_order_desc(s.d_pkey.p, s.d_pw.p, n_pairs)); CHK(rt_sync());
+	if (!s.d_regs2.alloc((size_t)s.t2 + 1)) { ssg_err_msg = "device allocation failed: pairing-stage regions"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_regoff, d_regs, d_nreg, s.d_r2off.p, s.d_regs2.p);
+	return 0;
+}
+
+/* The request tail of ssg_pe_core, se_core and ssg_dbg_pair_final: the requests that the final stage left in the reads' slices (d_reqoff, d_req, d_nreq) compacted into
+ * t.req, the reads' offsets (n_reads + 1) in t.req_off and, where the caller wants them on the host at once, in h_off.  With `a`, on through CIGAR / NM / MD of every
+ * request (run_reg2aln, on the regions a->d_regs) into t.alns, and a->stats[2 .. 4] = what a->d_cnt counted (rescue SW cells, rescues) and the number of records. */
+struct reg2aln_in_t { const ssg_index_t *idx; const ssg_mem_opt_t *opt; const ssg_alnreg_t *d_regs; const uint8_t *d_seq; const int64_t *d_off; int max_len; unsigned long long *d_cnt; uint64_t *stats; };
+static int run_req_tail(int n_reads, const int64_t *d_reqoff, const ssg_alnreq_t *d_req, const int32_t *d_nreq, int64_t *h_off, const reg2aln_in_t *a, pe_dev_t &t)
+{
 	const int block = 256;
-	/* ---- insert-size statistics ---- */
-	res->pes.resize((size_t)n_batches * 4);
-	if (pes0) { for (int b = 0; b < n_batches; ++b) memcpy(&res->pes[(size_t)b * 4], pes0, 4 * sizeof(ssg_pestat_t)); }
-	else CHK(run_pestat(idx, opt, n_pairs, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_pb.p, n_batches, res->pes.data()));
-	STAGE("pestat");
-	dbuf<ssg_pestat_t> d_pes((size_t)n_batches * 4);
-	CHKA(d_pes); CHK(d_pes.up(res->pes.data(), res->pes.size()));
-	/* ---- pairing-stage region slices with head-room for rescued hits ---- */
-	dbuf<int32_t> d_cap2(n_reads), d_capq(n_reads), d_pkey(n_pairs), d_pw(n_pairs);
-	dbuf<int64_t> d_r2off(n_reads + 1), d_reqoff(n_reads + 1);
-	CHKA(d_cap2); CHKA(d_capq); CHKA(d_pkey); CHKA(d_pw); CHKA(d_r2off); CHKA(d_reqoff);
-	SSG_LAUNCH(ssg_k_pair_caps, (n_reads + block - 1) / block, block, 0, n_reads, a1.n_reg.p, opt->max_matesw, d_cap2.p, d_capq.p, d_pkey.p);
-	int64_t t2 = 0, tq = 0;
-	CHK(dev_exclusive_scan(d_cap2.p, d_r2off.p, n_reads, &t2)); CHK(dev_exclusive_scan(d_capq.p, d_reqoff.p, n_reads, &tq));
-	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs));   /* heaviest-first pair order for the pairing-stage kernels (key: candidate regions of both ends) */
-	dbuf<ssg_alnreg_t> d_regs2((size_t)t2 + 1); dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)t2 + 1), d_nreq(n_reads), d_gerr(1);
-	dbuf<unsigned long long> d_cnt(3);   /* SW cells, mate rescues, rescues whose forward pass was computed ahead of the decision */
-	CHKA(d_regs2); CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_cnt); CHKA(d_gerr);
-	CHK(d_perr.zero()); CHK(d_cnt.zero()); CHK(d_gerr.zero());
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_r2off.p, d_regs2.p);
-	const int wpb = SSG_WAVES_PER_WG;
-	dbuf<unsigned int> d_q(1);
-	CHKA(d_q); CHK(d_q.zero());
-	if (!(opt->flag & SSG_F_NO_RESCUE))	/* ---- mate rescue (upstream mem_sam_pe: unless -S) ---- */
-		CHK(run_matesw(idx, opt, n_pairs, d_seq.p, d_off.p, max_len, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_pw.p, (const uint8_t*)a1.sdp_fixed.p, d_perr.p, d_cnt.p, d_q.p, 0));
-	STAGE("matesw");
-	dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
-	CHKA(d_req);
-	CHK(run_pair_final(idx, opt, n_pairs, id0, t2, d_r2off.p, d_regs2.p, a1.n_reg.p, d_pb.p, d_pes.p, d_pkey.p, d_pw.p, d_zbuf.p, d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
-	/* ---- compact the requests and generate CIGAR / NM / MD ---- */
-	dbuf<int64_t> d_coff(n_reads + 1);
-	CHKA(d_coff);
-	int64_t nreq = 0;
-	CHK(dev_exclusive_scan(d_nreq.p, d_coff.p, n_reads, &nreq));
-	if (!keep) { res->req_off.resize(n_reads + 1); CHK(d_coff.down(res->req_off.data(), (size_t)n_reads + 1)); }
-	dbuf<ssg_alnreq_t> d_creq((size_t)nreq + 1); dbuf<ssg_aln_t> d_alns((size_t)nreq + 1);
-	CHKA(d_creq); CHKA(d_alns);
-	SSG_LAUNCH(ssg_k_compact_req, (n_reads + block - 1) / block, block, 0, n_reads, d_reqoff.p, d_req.p, d_nreq.p, d_coff.p, d_creq.p);
-	CHK(run_reg2aln(idx, opt, nreq, d_creq.p, d_regs2.p, d_seq.p, d_off.p, d_alns.p, d_gerr.p, d_cnt.p, max_len));
+	if (!t.req_off.alloc((size_t)n_reads + 1)) { ssg_err_msg = "device allocation failed: request offsets"; return SSG_ENOMEM; }
+	CHK(ssg_dev_exclusive_scan(d_nreq, t.req_off.p, n_reads, &t.n_req));
+	if (h_off) CHK(t.req_off.down(h_off, (size_t)n_reads + 1));
+	if (!t.req.alloc((size_t)t.n_req + 1) || (a && !t.alns.alloc((size_t)t.n_req + 1))) { ssg_err_msg = "device allocation failed: compacted requests"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_compact_req, (n_reads + block - 1) / block, block, 0, n_reads, d_reqoff, d_req, d_nreq, t.req_off.p, t.req.p);
+	if (!a) return 0;
+	dbuf<int32_t> d_gerr(1);
+	CHKA(d_gerr); CHK(d_gerr.zero());
+	CHK(run_reg2aln(a->idx, a->opt, t.n_req, t.req.p, a->d_regs, a->d_seq, a->d_off, t.alns.p, d_gerr.p, a->d_cnt, a->max_len));
 	STAGE("reg2aln");
 	{ int32_t ge; CHK(d_gerr.down(&ge, 1)); if (ge) { char b[96]; snprintf(b, sizeof(b), "CIGAR generation exceeded an on-device capacity (code %d)", ge); ssg_err_msg = b; return SSG_EOVERFLOW; } }
-	{ unsigned long long c[2]; CHK(d_cnt.down(c, 2)); res->stats[2] = c[0]; res->stats[3] = c[1]; res->stats[4] = (uint64_t)nreq; }
-	if (keep) { keep->req.swap(d_creq); keep->alns.swap(d_alns); keep->req_off.swap(d_coff); keep->n_req = nreq; }
-	else {
-		if (!res->req.resize((size_t)nreq) || !res->alns.resize((size_t)nreq)) { ssg_err_msg = "host allocation failed: result records"; return SSG_ENOMEM; }
-		CHK(d_creq.down(res->req.data(), (size_t)nreq)); CHK(d_alns.down(res->alns.data(), (size_t)nreq));
-		STAGE("download");
-	}
+	{ unsigned long long c[2]; CHK(rt_d2h(c, a->d_cnt, sizeof(c))); a->stats[2] = c[0]; a->stats[3] = c[1]; a->stats[4] = (uint64_t)t.n_req; }
+	return 0;
+}
+/* ... and the records into the host result */
+static int download_records(const pe_dev_t &t, ssg_pe_result *res)
+{
+	const size_t nreq = (size_t)t.n_req;
+	if (!res->req.resize(nreq) || !res->alns.resize(nreq)) { ssg_err_msg = "host allocation failed: result records"; return SSG_ENOMEM; }
+	CHK(t.req.down(res->req.data(), nreq)); CHK(t.alns.down(res->alns.data(), nreq));
+	STAGE("download");
 	return 0;
 }
 
 int ssg_pe_core(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq, const int64_t *d_off, int max_len,
-                const int32_t *d_pair_batch, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep)
+                const int32_t *d_pb, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result *res, pe_dev_t *keep)
 {
-	return pe_core(idx, opt, n_pairs, d_seq, d_off, max_len, d_pair_batch, n_batches, id0, pes0, res, keep);
+	const int n_reads = 2 * n_pairs;
+	res->n_reads = n_reads; res->n_batches = n_batches; memset(res->stats, 0, sizeof(res->stats));
+	align1_dev_t a1;
+	CHK(run_align1(idx, opt, n_reads, d_seq, d_off, max_len, a1, res->stats));
+	/* ---- insert-size statistics ---- */
+	res->pes.resize((size_t)n_batches * 4);
+	if (pes0) { for (int b = 0; b < n_batches; ++b) memcpy(&res->pes[(size_t)b * 4], pes0, 4 * sizeof(ssg_pestat_t)); }
+	else CHK(run_pestat(idx, opt, n_pairs, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_pb, n_batches, res->pes.data()));
+	STAGE("pestat");
+	dbuf<ssg_pestat_t> d_pes((size_t)n_batches * 4);
+	CHKA(d_pes); CHK(d_pes.up(res->pes.data(), res->pes.size()));
+	/* ---- pairing-stage region slices with head-room for rescued hits ---- */
+	pair_slices_t s;
+	CHK(make_pair_slices(n_reads, a1.seed_off.p, a1.regs.p, a1.n_reg.p, opt->max_matesw, s));
+	dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)s.t2 + 1), d_nreq(n_reads);
+	dbuf<unsigned long long> d_cnt(3);   /* SW cells, mate rescues, rescues whose forward pass was computed ahead of the decision */
+	dbuf<unsigned int> d_q(1);
+	CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_cnt); CHKA(d_q);
+	CHK(d_perr.zero()); CHK(d_cnt.zero()); CHK(d_q.zero());
+	if (!(opt->flag & SSG_F_NO_RESCUE))	/* ---- mate rescue (upstream mem_sam_pe: unless -S) ---- */
+		CHK(run_matesw(idx, opt, n_pairs, d_seq, d_off, max_len, s.d_r2off.p, s.d_regs2.p, a1.n_reg.p, d_pb, d_pes.p, s.d_pw.p, (const uint8_t*)a1.sdp_fixed.p, d_perr.p, d_cnt.p, d_q.p, 0));
+	STAGE("matesw");
+	dbuf<ssg_alnreq_t> d_req((size_t)s.tq + 1);
+	CHKA(d_req);
+	CHK(run_pair_final(idx, opt, n_pairs, id0, s.t2, s.d_r2off.p, s.d_regs2.p, a1.n_reg.p, d_pb, d_pes.p, s.d_pkey.p, s.d_pw.p, d_zbuf.p, s.d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
+	/* ---- compact the requests and generate CIGAR / NM / MD ---- */
+	pe_dev_t here; pe_dev_t &t = keep ? *keep : here;
+	if (!keep) res->req_off.resize((size_t)n_reads + 1);
+	const reg2aln_in_t r2a = { idx, opt, s.d_regs2.p, d_seq, d_off, max_len, d_cnt.p, res->stats };
+	CHK(run_req_tail(n_reads, s.d_reqoff.p, d_req.p, d_nreq.p, keep ? (int64_t*)0 : res->req_off.data(), &r2a, t));
+	return keep ? 0 : download_records(t, res);
 }
-int ssg_dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t *total) { return dev_exclusive_scan(d_in, d_out, n, total); }
+
 
 /* ---- test entries of the paired-end decision stage: region lists in, the stage's own results out (include/ssgpu.h) ---- */
 static int dbg_check_regs(const ssg_index_t *idx, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs, const char *who)
@@ -1463,7 +1398,7 @@ extern "C" {
 int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs,
                    const int32_t *pair_batch, int n_batches, ssg_pestat_t *pes)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pestat"));
 	if (n_batches < 1 || n_batches > 64) { ssg_err_msg = "ssg_dbg_pestat: 1 <= n_batches <= 64"; return SSG_EINVAL; }
 	for (int p = 0; p < n_pairs; ++p) if (pair_batch[p] < 0 || pair_batch[p] >= n_batches) { ssg_err_msg = "ssg_dbg_pestat: pair_batch out of range"; return SSG_EINVAL; }
@@ -1480,7 +1415,7 @@ int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
                        const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pair_final"));
 	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].std > 0 && pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_pair_final: an orientation that has not failed needs std > 0 and 0 <= low <= high"; return SSG_EINVAL; }
 	const int n_reads = 2 * n_pairs, block = 256;
@@ -1492,34 +1427,24 @@ int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
 	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1); dbuf<int32_t> d_n((size_t)n_reads), d_pb((size_t)n_pairs); dbuf<ssg_pestat_t> d_pes(4);
 	CHKA(d_off); CHKA(d_regs); CHKA(d_n); CHKA(d_pb); CHKA(d_pes);
 	CHK(d_off.up(reg_off, (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pes.up(pes, 4));
-	/* slices, request capacities and the heaviest-first order exactly as pe_core makes them */
-	dbuf<int32_t> d_cap2(n_reads), d_capq(n_reads), d_pkey(n_pairs), d_pw(n_pairs);
-	dbuf<int64_t> d_r2off(n_reads + 1), d_reqoff(n_reads + 1);
-	CHKA(d_cap2); CHKA(d_capq); CHKA(d_pkey); CHKA(d_pw); CHKA(d_r2off); CHKA(d_reqoff);
-	SSG_LAUNCH(ssg_k_pair_caps, (n_reads + block - 1) / block, block, 0, n_reads, d_n.p, opt->max_matesw, d_cap2.p, d_capq.p, d_pkey.p);
-	int64_t t2 = 0, tq = 0;
-	CHK(dev_exclusive_scan(d_cap2.p, d_r2off.p, n_reads, &t2)); CHK(dev_exclusive_scan(d_capq.p, d_reqoff.p, n_reads, &tq));
-	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs));
-	dbuf<ssg_alnreg_t> d_regs2((size_t)t2 + 1); dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)t2 + 1), d_nreq(n_reads); dbuf<unsigned int> d_q(1); dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
-	CHKA(d_regs2); CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_q); CHKA(d_req);
+	/* slices, request capacities and the heaviest-first order: the pipeline's own (make_pair_slices) */
+	pair_slices_t s;
+	CHK(make_pair_slices(n_reads, d_off.p, d_regs.p, d_n.p, opt->max_matesw, s));
+	dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)s.t2 + 1), d_nreq(n_reads); dbuf<unsigned int> d_q(1); dbuf<ssg_alnreq_t> d_req((size_t)s.tq + 1);
+	CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_q); CHKA(d_req);
 	CHK(d_perr.zero()); CHK(d_nreq.zero());
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_off.p, d_regs.p, d_n.p, d_r2off.p, d_regs2.p);
-	CHK(run_pair_final(idx, opt, n_pairs, id0, t2, d_r2off.p, d_regs2.p, d_n.p, d_pb.p, d_pes.p, d_pkey.p, d_pw.p, d_zbuf.p, d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
-	/* the regions back into the caller's layout, the requests compacted as pe_core compacts them */
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_r2off.p, d_regs2.p, d_n.p, d_off.p, d_regs.p);
-	dbuf<int64_t> d_coff(n_reads + 1);
-	CHKA(d_coff);
-	int64_t nreq = 0;
-	CHK(dev_exclusive_scan(d_nreq.p, d_coff.p, n_reads, &nreq));
-	dbuf<ssg_alnreq_t> d_creq((size_t)nreq + 1);
-	CHKA(d_creq);
-	SSG_LAUNCH(ssg_k_compact_req, (n_reads + block - 1) / block, block, 0, n_reads, d_reqoff.p, d_req.p, d_nreq.p, d_coff.p, d_creq.p);
+	CHK(run_pair_final(idx, opt, n_pairs, id0, s.t2, s.d_r2off.p, s.d_regs2.p, d_n.p, d_pb.p, d_pes.p, s.d_pkey.p, s.d_pw.p, d_zbuf.p, s.d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
+	/* the regions back into the caller's layout, the requests compacted by the pipeline's own tail (without its CIGAR step) */
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, s.d_r2off.p, s.d_regs2.p, d_n.p, d_off.p, d_regs.p);
+	pe_dev_t t;
+	CHK(run_req_tail(n_reads, s.d_reqoff.p, d_req.p, d_nreq.p, 0, 0, t));
 	CHK(rt_sync());
+	const int64_t nreq = t.n_req;
 	std::vector<int64_t> r2off((size_t)n_reads + 1);
-	CHK(d_r2off.down(r2off.data(), (size_t)n_reads + 1)); CHK(d_coff.down(req_off, (size_t)n_reads + 1)); CHK(d_regs.down(regs_out, (size_t)tot));
+	CHK(s.d_r2off.down(r2off.data(), (size_t)n_reads + 1)); CHK(t.req_off.down(req_off, (size_t)n_reads + 1)); CHK(d_regs.down(regs_out, (size_t)tot));
 	ssg_alnreq_t *out = (ssg_alnreq_t*)malloc(sizeof(ssg_alnreq_t) * (size_t)(nreq + 1));
 	if (!out) { ssg_err_msg = "host allocation failed: requests"; return SSG_ENOMEM; }
-	int rc = d_creq.down(out, (size_t)nreq);
+	int rc = t.req.down(out, (size_t)nreq);
 	if (rc) { free(out); return rc; }
 	for (int64_t k = 0; k < nreq; ++k) if (out[k].reg >= 0) out[k].reg = (int32_t)(out[k].reg - r2off[out[k].read] + reg_off[out[k].read]);   /* slice index -> the caller's index */
 	*req = out;
@@ -1536,7 +1461,7 @@ void ssg_dbg_matesw_last(uint64_t counts[8])
 int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *read_off, const int64_t *reg_off, const ssg_alnreg_t *regs,
                    const uint8_t *fixed, const ssg_pestat_t pes[4], int headroom, int64_t *out_off, ssg_alnreg_t **regs_out, int32_t *n_out, int32_t *err, uint64_t counts[8])
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_matesw"));
 	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_matesw: an orientation that has not failed needs 0 <= low <= high"; return SSG_EINVAL; }
 	const int n_reads = 2 * n_pairs, block = 256;
@@ -1563,7 +1488,7 @@ int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	CHK(d_seq.up(seq, (size_t)read_off[n_reads])); CHK(d_fixed.up(hfix.data(), (size_t)n_reads)); CHK(d_roff.up(read_off, (size_t)n_reads + 1)); CHK(d_off.up(reg_off, (size_t)n_reads + 1));
 	CHK(d_r2off.up(r2off.data(), (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_regs2.zero()); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pkey.up(hkey.data(), (size_t)n_pairs));
 	CHK(d_perr.zero()); CHK(d_pes.up(pes, 4)); CHK(d_cnt.zero()); CHK(d_q.zero());
-	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs));
+	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs)); CHK(rt_sync());
 	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_off.p, d_regs.p, d_n.p, d_r2off.p, d_regs2.p);
 	msw_stage_t ms;
 	CHK(run_matesw(idx, opt, n_pairs, d_seq.p, d_roff.p, max_len, d_r2off.p, d_regs2.p, d_n.p, d_pb.p, d_pes.p, d_pw.p, d_fixed.p, d_perr.p, d_cnt.p, d_q.p, &ms));
@@ -1589,51 +1514,29 @@ static int se_core(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads
 	res->n_reads = n_reads; res->n_batches = 0; res->se = 1; memset(res->stats, 0, sizeof(res->stats));
 	align1_dev_t a1;
 	CHK(run_align1(idx, opt, n_reads, d_seq, d_off, max_len, a1, res->stats));
-	const int block = 256, wpb = SSG_WAVES_PER_WG;
-	dbuf<int32_t> d_capq(n_reads), d_nreq(n_reads), d_zbuf((size_t)a1.tot_seeds + 1), d_ibuf((size_t)a1.tot_seeds + 1), d_gerr(1);
-	dbuf<int64_t> d_reqoff(n_reads + 1), d_coff(n_reads + 1); dbuf<unsigned long long> d_cnt(2);
-	CHKA(d_capq); CHKA(d_nreq); CHKA(d_zbuf); CHKA(d_ibuf); CHKA(d_gerr); CHKA(d_reqoff); CHKA(d_coff); CHKA(d_cnt);
-	CHK(d_gerr.zero()); CHK(d_cnt.zero());
+	const int block = 256;
+	dbuf<int32_t> d_capq(n_reads), d_nreq(n_reads), d_zbuf((size_t)a1.tot_seeds + 1), d_ibuf((size_t)a1.tot_seeds + 1);
+	dbuf<int64_t> d_reqoff(n_reads + 1); dbuf<unsigned long long> d_cnt(2);
+	CHKA(d_capq); CHKA(d_nreq); CHKA(d_zbuf); CHKA(d_ibuf); CHKA(d_reqoff); CHKA(d_cnt);
+	CHK(d_cnt.zero());
 	SSG_LAUNCH(ssg_k_se_caps, (n_reads + block - 1) / block, block, 0, n_reads, a1.n_reg.p, d_capq.p);
 	int64_t tq = 0;
-	CHK(dev_exclusive_scan(d_capq.p, d_reqoff.p, n_reads, &tq));
+	CHK(ssg_dev_exclusive_scan(d_capq.p, d_reqoff.p, n_reads, &tq));
 	dbuf<ssg_alnreq_t> d_req((size_t)tq + 1);
 	CHKA(d_req);
 	SSG_LAUNCH(ssg_k_se_final, (n_reads + 63) / 64, 64, 0, *opt, n_reads, id0, a1.seed_off.p, a1.regs.p, a1.n_reg.p, d_zbuf.p, d_ibuf.p, d_reqoff.p, d_req.p, d_nreq.p);
 	STAGE("se_final");
-	int64_t nreq = 0;
-	CHK(dev_exclusive_scan(d_nreq.p, d_coff.p, n_reads, &nreq));
-	res->req_off.resize((size_t)n_reads + 1); CHK(d_coff.down(res->req_off.data(), (size_t)n_reads + 1));
-	dbuf<ssg_alnreq_t> d_creq((size_t)nreq + 1); dbuf<ssg_aln_t> d_alns((size_t)nreq + 1);
-	CHKA(d_creq); CHKA(d_alns);
-	SSG_LAUNCH(ssg_k_compact_req, (n_reads + block - 1) / block, block, 0, n_reads, d_reqoff.p, d_req.p, d_nreq.p, d_coff.p, d_creq.p);
-	CHK(run_reg2aln(idx, opt, nreq, d_creq.p, a1.regs.p, d_seq, d_off, d_alns.p, d_gerr.p, d_cnt.p, max_len));
-	STAGE("reg2aln");
-	{ int32_t ge; CHK(d_gerr.down(&ge, 1)); if (ge) { char b[96]; snprintf(b, sizeof(b), "CIGAR generation exceeded an on-device capacity (code %d)", ge); ssg_err_msg = b; return SSG_EOVERFLOW; } }
-	{ unsigned long long c[2]; CHK(d_cnt.down(c, 2)); res->stats[2] = c[0]; res->stats[3] = c[1]; res->stats[4] = (uint64_t)nreq; }
-	if (!res->req.resize((size_t)nreq) || !res->alns.resize((size_t)nreq)) { ssg_err_msg = "host allocation failed: result records"; return SSG_ENOMEM; }
-	CHK(d_creq.down(res->req.data(), (size_t)nreq)); CHK(d_alns.down(res->alns.data(), (size_t)nreq));
-	STAGE("download");
-	return 0;
+	pe_dev_t t;
+	res->req_off.resize((size_t)n_reads + 1);
+	const reg2aln_in_t r2a = { idx, opt, a1.regs.p, d_seq, d_off, max_len, d_cnt.p, res->stats };
+	CHK(run_req_tail(n_reads, d_reqoff.p, d_req.p, d_nreq.p, res->req_off.data(), &r2a, t));
+	return download_records(t, res);
 }
 
-/* stable sort of (hash, ordinal) by hash: hipCUB radix sort on the GPU */
-static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n)
-{
-#ifdef SSG_EMU
-	std::vector<uint32_t> idx(n); for (long i = 0; i < n; ++i) idx[i] = (uint32_t)i;
-	std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return k_in[a] < k_in[b]; });
-	for (long i = 0; i < n; ++i) { k_out[i] = k_in[idx[i]]; v_out[i] = v_in[idx[i]]; }
-	return 0;
-#else
-	size_t tmp_bytes = 0;
-	if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, 64u) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_pairs (size query) failed"; return SSG_EHIP; }
-	dbuf<uint8_t> tmp(tmp_bytes);
-	CHKA(tmp);
-	if (rocprim::radix_sort_pairs(tmp.p, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, 64u, ssg_stream) != hipSuccess) { ssg_err_msg = "rocprim radix_sort_pairs failed"; return SSG_EHIP; }
-	return rt_sync();
-#endif
-}
+/* stable sort of (hash, ordinal) by hash; like the primitive, it does not wait.  It is a function of its own, defined behind the pairing stage and declared ahead of
+ * run_align1, for the unit's device code: this is where rocPRIM's kernels for u64 / u32 pairs are instantiated, after ssg_k_matesw, as in the build whose kernels were
+ * checked on the GPU (tools/isa_pin.py hashes a kernel with the padding up to the symbol that follows it; as the last one of the unit ssg_k_matesw<false> has none). */
+static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n) { return prim_sort_pairs(k_in, k_out, v_in, v_out, n, 0, 64); }
 
 /* ---- the persistent duplicate set (k_sbl.h): open-addressing table in HBM ---- */
 struct ssg_sbl_state {
@@ -1665,7 +1568,7 @@ static int dedup_core(ssg_sbl_state *st, long n_pairs, const ssg_sbl_end_t *d_en
 	CHKA(d_h); CHKA(d_hs); CHKA(d_o); CHKA(d_os);
 	if (st) { if (!d_fresh.alloc(n_pairs)) { ssg_err_msg = "device allocation failed: fresh flags"; return SSG_ENOMEM; } CHK(sbl_table_reserve(st, (uint64_t)n_pairs)); }
 	SSG_LAUNCH(ssg_k_sig, (n_pairs + block - 1) / block, block, 0, n_pairs, d_ends, d_sig_out, d_h.p, d_o.p);
-	CHK(sort_pairs_u64(d_h.p, d_hs.p, d_o.p, d_os.p, n_pairs));
+	CHK(sort_pairs_u64(d_h.p, d_hs.p, d_o.p, d_os.p, n_pairs)); CHK(rt_sync());
 	SSG_LAUNCH(ssg_k_sbl_markdup, (n_pairs + block - 1) / block, block, 0, n_pairs, d_hs.p, d_os.p, d_sig_out,
 	           st ? st->th : (const uint64_t*)0, st ? st->ts : (const ssg_sig_t*)0, st ? st->slots - 1 : 0, d_dup, st ? d_fresh.p : (uint8_t*)0);
 	if (st) {
@@ -1699,9 +1602,9 @@ static int sigdup_core(long n, const ssg_sig_t *d_sig, const uint64_t *d_ordinal
 	CHKA(d_k); CHKA(d_ks); CHKA(d_h); CHKA(d_hs); CHKA(d_v); CHKA(d_perm); CHKA(d_o); CHKA(d_os); CHKA(d_so); CHKA(d_do);
 	CHK(rt_d2d(d_k.p, d_ordinal, (size_t)n * 8));
 	SSG_LAUNCH(ssg_k_iota_u32, (n + block - 1) / block, block, 0, d_v.p, n);
-	CHK(sort_pairs_u64(d_k.p, d_ks.p, d_v.p, d_perm.p, n));
+	CHK(sort_pairs_u64(d_k.p, d_ks.p, d_v.p, d_perm.p, n)); CHK(rt_sync());
 	SSG_LAUNCH(ssg_k_sigdup_gather, (n + block - 1) / block, block, 0, n, d_perm.p, d_sig, d_so.p, d_h.p, d_o.p);
-	CHK(sort_pairs_u64(d_h.p, d_hs.p, d_o.p, d_os.p, n));
+	CHK(sort_pairs_u64(d_h.p, d_hs.p, d_o.p, d_os.p, n)); CHK(rt_sync());
 	SSG_LAUNCH(ssg_k_sbl_markdup, (n + block - 1) / block, block, 0, n, d_hs.p, d_os.p, d_so.p, (const uint64_t*)0, (const ssg_sig_t*)0, (uint64_t)0, d_do.p, (uint8_t*)0);
 	SSG_LAUNCH(ssg_k_sigdup_scatter, (n + block - 1) / block, block, 0, n, d_perm.p, d_do.p, d_dup);
 	return rt_sync();
@@ -1734,7 +1637,7 @@ int ssg_mem_process_pairs(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 }
 int ssg_mem_process_reads(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off, int64_t id0, ssg_pe_result_t **out)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	*out = 0;
 	if (n_reads <= 0) { ssg_err_msg = "ssg_mem_process_reads: empty input"; return SSG_EINVAL; }
 	int max_len = 0; for (int r = 0; r < n_reads; ++r) max_len = std::max<int>(max_len, (int)(off[r+1] - off[r]));
@@ -1754,7 +1657,7 @@ int ssg_mem_process_reads(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
  * (2*n_pairs entries: read1, read2 primaries); dup[p] = 1 when an earlier pair has the same signature */
 int ssg_sbl_markdup(long n_pairs, const ssg_sbl_end_t *ends, uint8_t *dup)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_pairs <= 0) return 0;
 	if (n_pairs >= (1L << 31)) { ssg_err_msg = "ssg_sbl_markdup: more than 2^31 pairs per call"; return SSG_EINVAL; }
 	dbuf<ssg_sbl_end_t> d_ends(2 * n_pairs); dbuf<uint8_t> d_dup(n_pairs);
@@ -1771,7 +1674,7 @@ void ssg_sbl_state_free(ssg_sbl_state_t *s) { delete s; }
 
 int ssg_sbl_markdup_stream(ssg_sbl_state_t *st, long n_pairs, const ssg_sbl_end_t *ends, uint8_t *dup)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_pairs <= 0) return 0;
 	if (n_pairs >= (1L << 31)) { ssg_err_msg = "ssg_sbl_markdup_stream: more than 2^31 pairs per call"; return SSG_EINVAL; }
 	dbuf<ssg_sbl_end_t> d_ends(2 * n_pairs); dbuf<uint8_t> d_dup(n_pairs);
@@ -1785,7 +1688,7 @@ int ssg_sbl_markdup_stream(ssg_sbl_state_t *st, long n_pairs, const ssg_sbl_end_
  * ssg_hotpath_dev_ex wrote them on the sending ranks (all ones = never a duplicate), d_ordinal the global input ordinal of each pair */
 int ssg_markdup_sig_dev(long n, const uint64_t *d_sig, const int64_t *d_ordinal, uint8_t *d_dup)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n <= 0) return 0;
 	if (n >= (1L << 32)) { ssg_err_msg = "ssg_markdup_sig_dev: more than 2^32 signatures per call"; return SSG_EINVAL; }
 	return sigdup_core(n, (const ssg_sig_t*)d_sig, (const uint64_t*)d_ordinal, d_dup);
@@ -1795,7 +1698,7 @@ int ssg_markdup_sig_dev(long n, const uint64_t *d_sig, const int64_t *d_ordinal,
  * The coordinate sort of BAM records (samtools bam_sort.c:1607-1614 key, stable) is this call on the record keys (row f1). */
 int ssg_sort_u64_perm(const uint64_t *keys, int64_t n, uint32_t *perm)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n <= 0) return 0;
 	if (n >= (1LL << 32)) { ssg_err_msg = "ssg_sort_u64_perm: more than 2^32 keys per call"; return SSG_EINVAL; }
 	dbuf<uint64_t> d_k(n), d_ks(n); dbuf<uint32_t> d_v(n), d_vs(n);
@@ -1803,7 +1706,7 @@ int ssg_sort_u64_perm(const uint64_t *keys, int64_t n, uint32_t *perm)
 	CHK(d_k.up(keys, n));
 	SSG_LAUNCH(ssg_k_iota_u32, (n + 255) / 256, 256, 0, d_v.p, (long)n);
 	CHK(sort_pairs_u64(d_k.p, d_ks.p, d_v.p, d_vs.p, n));
-	return d_vs.down(perm, n);
+	return d_vs.down(perm, n);   /* (the download is the wait) */
 }
 
 void ssg_sbl_opt_init(ssg_sbl_opt_t *o)
@@ -1815,7 +1718,7 @@ void ssg_sbl_opt_init(ssg_sbl_opt_t *o)
 int ssg_sbl_process(ssg_sbl_state_t *st, const ssg_sbl_opt_t *o, long n_blocks, const int64_t *blk_off, const ssg_sbl_line_t *lines,
                     uint8_t *line_bits, int64_t *mate_line)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_blocks <= 0) return 0;
 	if (n_blocks >= (1L << 31)) { ssg_err_msg = "ssg_sbl_process: more than 2^31 blocks per call"; return SSG_EINVAL; }
 	const int64_t n_lines = blk_off[n_blocks];
@@ -1832,7 +1735,7 @@ int ssg_sbl_process(ssg_sbl_state_t *st, const ssg_sbl_opt_t *o, long n_blocks, 
  * input order), its verdicts come back, and the lines are classified with them.  Same kernels as ssg_sbl_process, same results. */
 int ssg_sbl_ends(long n_blocks, const int64_t *blk_off, const ssg_sbl_line_t *lines, ssg_sbl_end_t *ends)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_blocks <= 0) return 0;
 	if (n_blocks >= (1L << 31)) { ssg_err_msg = "ssg_sbl_ends: more than 2^31 blocks per call"; return SSG_EINVAL; }
 	const int64_t n_lines = blk_off[n_blocks]; const int block = 256;
@@ -1844,7 +1747,7 @@ int ssg_sbl_ends(long n_blocks, const int64_t *blk_off, const ssg_sbl_line_t *li
 }
 int ssg_sbl_classify(const ssg_sbl_opt_t *o, long n_blocks, const int64_t *blk_off, const ssg_sbl_line_t *lines, const uint8_t *dup, uint8_t *line_bits, int64_t *mate_line)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_blocks <= 0) return 0;
 	if (n_blocks >= (1L << 31)) { ssg_err_msg = "ssg_sbl_classify: more than 2^31 blocks per call"; return SSG_EINVAL; }
 	if (o->max_split_count > SSG_SBL_MAX_SPLIT) { ssg_err_msg = "samblaster: --maxSplitCount above 16 is not supported"; return SSG_EINVAL; }
@@ -1874,7 +1777,7 @@ static int records_lines(struct ssg_dev_records *R)
 	CHKA(d_nl);
 	if (!R->line_off.alloc(n_pairs + 1)) { ssg_err_msg = "device allocation failed: line offsets"; return SSG_ENOMEM; }
 	SSG_LAUNCH(ssg_k_sbl_count_lines, (n_pairs + block - 1) / block, block, 0, n_pairs, R->keep.req_off.p, R->keep.req.p, d_nl.p);
-	CHK(dev_exclusive_scan(d_nl.p, R->line_off.p, n_pairs, &R->n_lines));
+	CHK(ssg_dev_exclusive_scan(d_nl.p, R->line_off.p, n_pairs, &R->n_lines));
 	const size_t nl = (size_t)R->n_lines + 1;
 	if (!R->lines.alloc(nl) || !R->line_req.alloc(nl) || !R->prim.alloc(2 * n_pairs) || !R->mate.alloc(nl) || !R->bits.alloc(nl) || !R->ends.alloc(2 * n_pairs) || !R->dup.alloc(n_pairs)) {
 		ssg_err_msg = "device allocation failed: samblaster lines"; return SSG_ENOMEM; }
@@ -1885,7 +1788,7 @@ static int records_lines(struct ssg_dev_records *R)
 static int process_pairs_host(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *off,
                               const int32_t *pair_batch, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result_t **out)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	*out = 0;
 	const int n_reads = 2 * n_pairs;
 	if (n_pairs <= 0 || n_batches <= 0) { ssg_err_msg = "ssg_mem_process_pairs: empty input"; return SSG_EINVAL; }
@@ -1898,7 +1801,7 @@ static int process_pairs_host(const ssg_index_t *idx, const ssg_mem_opt_t *opt, 
 	CHK(d_seq.up(seq, off[n_reads])); CHK(d_off.up(off, n_reads + 1)); CHK(d_pb.up(pair_batch, n_pairs));
 	STAGE("upload");
 	std::unique_ptr<ssg_pe_result> res(new ssg_pe_result());
-	CHK(pe_core(idx, opt, n_pairs, d_seq.p, d_off.p, max_len, d_pb.p, n_batches, id0, pes0, res.get(), 0));
+	CHK(ssg_pe_core(idx, opt, n_pairs, d_seq.p, d_off.p, max_len, d_pb.p, n_batches, id0, pes0, res.get(), 0));
 	ssg_prof_flush();
 	*out = res.release();
 	return 0;
@@ -1927,13 +1830,13 @@ int ssg_hotpath_dev_ex(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
                        const int32_t *d_pair_batch, int n_batches, int64_t id0, const ssg_sbl_opt_t *sbl, int local_dedup,
                        uint64_t summary[16], uint8_t *dup_host, uint64_t *d_sig_out, ssg_dev_records_t **keep_out)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (keep_out) *keep_out = 0;
 	if (n_pairs <= 0 || max_len > SSG_MAX_READ_LEN) { ssg_err_msg = "ssg_hotpath_dev: bad arguments"; return SSG_EINVAL; }
 	ssg_sbl_opt_t so; if (sbl) so = *sbl; else { ssg_sbl_opt_init(&so); so.exclude_dups = 1; so.add_mate_tags = 1; }   /* the reference's command line */
 	ssg_pe_result res; std::unique_ptr<ssg_dev_records> R(new ssg_dev_records());
 	R->n_pairs = n_pairs;
-	CHK(pe_core(idx, opt, n_pairs, d_seq, d_off, max_len, d_pair_batch, n_batches, id0, 0, &res, &R->keep));
+	CHK(ssg_pe_core(idx, opt, n_pairs, d_seq, d_off, max_len, d_pair_batch, n_batches, id0, 0, &res, &R->keep));
 	CHK(records_lines(R.get()));
 	memset(summary, 0, 16 * sizeof(uint64_t));
 	if (local_dedup || d_sig_out) {
@@ -1973,7 +1876,7 @@ int ssg_dev_records_export(const ssg_dev_records_t *R, uint64_t *d_keys, void *d
  * record by record with upstream's `bwa mem | samblaster` output (bench.py's parity gate on the timed call, tests) */
 int ssg_dev_records_download(const ssg_dev_records_t *R, ssg_pe_result_t **out, uint8_t *line_bits, int64_t *mate_line)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	*out = 0;
 	std::unique_ptr<ssg_pe_result> res(new ssg_pe_result());
 	const int n_reads = (int)(2 * R->n_pairs); const size_t nreq = (size_t)R->keep.n_req;
@@ -2020,7 +1923,7 @@ int32_t ssg_index_len(const ssg_index_t *ix, int i) { return i >= 0 && i < (int)
 void ssg_pe_result_free(ssg_pe_result_t *r) { delete r; }
 int ssg_pe_reserve(int n_pairs, int n_calls)
 {
-	CHK(need_device());
+	CHK(ssg_need_device());
 	if (n_pairs <= 0 || n_calls <= 0 || n_calls > 8) { ssg_err_msg = "ssg_pe_reserve: bad arguments"; return SSG_EINVAL; }
 	const size_t nrec = (size_t)n_pairs * 2 + (size_t)n_pairs / 4;      /* records per pair: 2 + supplementary / XA entries */
 	std::vector<void*> a, b;
