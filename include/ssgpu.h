@@ -122,6 +122,29 @@ int ssg_align2_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
  * once by one lane running the textbook loops (out_lane); the two must be equal word for word. */
 int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *out_wave);
 
+/* Test entry of the chaining stage (rows a4-a5: upstream mem_chain with test_and_merge, mem_chain_weight, mem_chain_flt, frac_rep): the stage on seeds and
+ * intervals given by the caller instead of the seeding stage's, through the one host function stage 1 of the pipeline runs -- the class split by seed count, every
+ * kernel form under the SSG_CHAIN_* switches, the second pass on klib's B-tree.  The kernels read l_pac and n_ctg of the index and nothing else, so no index is needed.
+ *   read_len[n_reads]; read r's seeds are seeds[seed_off[r] .. seed_off[r + 1]) in upstream's visiting order (rbeg, qbeg, len are read; score and next are ignored)
+ *   with their contigs rids[] (< 0: a seed upstream drops); its intervals intv[intv_off[r] .. intv_off[r + 1]) (info and x2 are read), the source of frac_rep.
+ * Validated first, SSG_EINVAL otherwise: 1 <= l_pac < 2^33, n_ctg >= 1, offsets from 0 and monotone, 1 <= read_len <= 310, 0 <= qbeg, 1 <= len, qbeg + len <= read_len,
+ * 0 <= rbeg, rbeg + len <= 2 l_pac, rid < n_ctg, intervals sorted by start with 0 <= start < end <= read_len.
+ * Out: chain_off[n_reads + 1]; *chains (malloc'd, ssg_free) the chains that survive the filter, in the stage's final order: pos, rid, n, w, kept, frac_rep as the
+ * kernels leave them, first_seed = where the chain's n seed indices begin in *chain_seeds (malloc'd, ssg_free; indices count from the read's first seed), the other
+ * fields 0; form[r] (may be NULL) = the kernel form that took read r, SSG_CHAIN_FORM_TREE added when the read was chained again on the tree. */
+#define SSG_CHAIN_FORM_LANE     0   /* ssg_k_chain: one lane per read on global memory */
+#define SSG_CHAIN_FORM_LDS16    1   /* ssg_k_chain_lds<16 | 32 | 64> */
+#define SSG_CHAIN_FORM_LDS32    2
+#define SSG_CHAIN_FORM_LDS64    3
+#define SSG_CHAIN_FORM_WAVE256  4   /* ssg_k_chain_wave<256 | 512 | 1024 | 2048 | 5120> */
+#define SSG_CHAIN_FORM_WAVE512  5
+#define SSG_CHAIN_FORM_WAVE1024 6
+#define SSG_CHAIN_FORM_WAVE2048 7
+#define SSG_CHAIN_FORM_WAVE5120 8
+#define SSG_CHAIN_FORM_TREE  0x10
+int ssg_dbg_chain(const ssg_mem_opt_t *opt, int64_t l_pac, int n_ctg, int n_reads, const int32_t *read_len, const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *rids,
+                  const int64_t *intv_off, const ssg_intv_t *intv, int64_t *chain_off, ssg_chain_t **chains, int32_t **chain_seeds, int32_t *form);
+
 /* Test entries of the paired-end decision stage (rows a9, a11): the stage on region lists given by the caller instead of stage 1's, through the kernels and
  * the host code of the pipeline itself -- the form that takes a pair (lane in LDS, lane on global memory, wave) is chosen as ssg_mem_process_pairs chooses it.
  * reg_off[2 n_pairs + 1]: read r's regions are regs[reg_off[r] .. reg_off[r + 1]) (read 1 and read 2 of a pair interleaved).  The lists are validated first

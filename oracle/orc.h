@@ -115,6 +115,11 @@ orc_chain_v orc_mem_chain(const orc_opt_t *opt, const orc_idx_t *idx, int len, c
 void orc_set_chain_container(int kbtree);
 int  orc_chain_exposure(const orc_opt_t *opt, const orc_idx_t *idx, int len, const uint8_t *seq, int *n_chains, int *dup);
 int  orc_mem_chain_flt(const orc_opt_t *opt, int n_chn, orc_chain_t *a);
+/* the pieces of the two above that orc_api_chain runs on seeds and intervals given by a test: mem_chain's loop over a seed list (rids[i] < 0: dropped), its frac_rep,
+ * and mem_chain_flt up to the removal of the chains it marked kept = 0 (returns the number of chains left by min_chain_weight, sorted by weight) */
+orc_chain_v orc_chain_seeds(const orc_opt_t *opt, int64_t l_pac, int64_t n_seeds, const orc_seed_t *seeds, const int *rids);
+float orc_frac_rep(const orc_opt_t *opt, int len, int n_intv, const orc_intv_t *intv);
+int  orc_mem_chain_flt_mark(const orc_opt_t *opt, int n_chn, orc_chain_t *a);
 void orc_mem_chain2aln(const orc_opt_t *opt, const orc_idx_t *idx, int l_query, const uint8_t *query, const orc_chain_t *c, orc_alnreg_v *av);
 int  orc_mem_sort_dedup_patch(const orc_opt_t *opt, const orc_idx_t *idx, uint8_t *query, int n, orc_alnreg_t *a);
 orc_alnreg_v orc_mem_align1_core(const orc_opt_t *opt, const orc_idx_t *idx, int l_seq, uint8_t *seq /* nt4 codes */);

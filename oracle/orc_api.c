@@ -49,7 +49,43 @@ void orc_api_opt_seed(orc_opt_t *o, int min_seed_len, float split_factor, int sp
 /* the paired-end decision stage's knobs (bwa mem -M / -P through flag, -T, -U, -h and the compiled-in mapQ coefficients), for the pairing reference's tests */
 void orc_api_opt_pair(orc_opt_t *o, int flag, int max_XA_hits, float mapQ_coef_len, int mapQ_coef_fac, int T, int pen_unpaired)
 { o->flag = flag; o->max_XA_hits = max_XA_hits; o->mapQ_coef_len = mapQ_coef_len; o->mapQ_coef_fac = mapQ_coef_fac; o->T = T; o->pen_unpaired = pen_unpaired; }
+/* the chaining stage's remaining knobs (bwa mem -w, -k, -c), for the chaining reference's tests */
+void orc_api_opt_chain2(orc_opt_t *o, int w, int min_seed_len, int max_occ) { o->w = w; o->min_seed_len = min_seed_len; o->max_occ = max_occ; }
 void orc_api_free(void *p) { free(p); }
+
+/* The chaining stage on seeds and intervals given by the caller (tests/test_chain_reference.py; the library's twin is ssg_dbg_chain): read r's seeds are
+ * seeds[4 * seed_off[r] .. 4 * seed_off[r + 1]) as (rbeg, qbeg, len, rid) in visiting order, its intervals intv[intv_off[r] .. intv_off[r + 1]).  Out, per read
+ * (chain_off[n_reads + 1]): the chains as orc_mem_chain_flt leaves them AFTER ITS SORT, those it marks kept = 0 included -- 7 values a chain: pos, rid, n, w, kept,
+ * the bits of frac_rep, where its n seed indices (counted from the read's first seed, insertion order) begin in chain_seeds.  Room for one chain and one index per
+ * seed suffices.  The container of mem_chain is the calling thread's (orc_api_set_chain_container). */
+void orc_api_chain(const orc_opt_t *opt, int64_t l_pac, int n_reads, const int32_t *read_len, const int64_t *seed_off, const int64_t *seeds,
+                   const int64_t *intv_off, const orc_intv_t *intv, int64_t *chain_off, int64_t *chains, int32_t *chain_seeds)
+{
+	int64_t nc = 0, nq = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		const int64_t s0 = seed_off[r], ns = seed_off[r + 1] - s0;
+		orc_seed_t *sd = calloc((size_t)(ns + 1), sizeof(orc_seed_t)); int *rd = malloc(sizeof(int) * (size_t)(ns + 1));
+		for (int64_t k = 0; k < ns; ++k) {   /* (score carries the seed's index through the chain lists: nothing in this stage reads it) */
+			const int64_t *p = seeds + 4 * (s0 + k);
+			sd[k].rbeg = p[0]; sd[k].qbeg = (int32_t)p[1]; sd[k].len = (int32_t)p[2]; sd[k].score = (int32_t)k; rd[k] = (int)p[3];
+		}
+		orc_chain_v c = orc_chain_seeds(opt, l_pac, ns, sd, rd);
+		const float frac_rep = orc_frac_rep(opt, read_len[r], (int)(intv_off[r + 1] - intv_off[r]), intv + intv_off[r]);
+		for (size_t i = 0; i < c.n; ++i) c.a[i].frac_rep = frac_rep;
+		const int n = orc_mem_chain_flt_mark(opt, (int)c.n, c.a);
+		chain_off[r] = nc;
+		for (int i = 0; i < n; ++i) {
+			const orc_chain_t *x = &c.a[i];
+			int64_t *o = chains + 7 * nc++;
+			uint32_t fb; memcpy(&fb, &x->frac_rep, 4);
+			o[0] = x->pos; o[1] = x->rid; o[2] = x->n; o[3] = x->w; o[4] = x->kept; o[5] = fb; o[6] = nq;
+			for (int j = 0; j < x->n; ++j) chain_seeds[nq++] = x->seeds[j].score;
+			free(x->seeds);
+		}
+		free(c.a); free(sd); free(rd);
+	}
+	chain_off[n_reads] = nc;
+}
 
 /* the paired-end decision stage on region lists given by the caller (tests/test_pair_reference.py; the library's twins are ssg_dbg_pestat / ssg_dbg_pair_final):
  * read r's regions are regs[reg_off[r] .. reg_off[r + 1]), read 1 and read 2 of a pair interleaved.

@@ -295,26 +295,89 @@ static __thread int orc_chain_container = -1;   /* -1: not chosen yet on this th
 void orc_set_chain_container(int kbtree) { orc_chain_container = kbtree; }
 static int chain_container(void) { if (orc_chain_container < 0) orc_chain_container = getenv("ORC_CHAIN_ARRAY") ? 0 : 1; return orc_chain_container; }
 
-orc_chain_v orc_mem_chain(const orc_opt_t *opt, const orc_idx_t *idx, int len, const uint8_t *seq)
-{	/* upstream mem_chain */
-	int i, b, e, l_rep;
-	const orc_bwt_t *bwt = idx->bwt; const orc_bns_t *bns = idx->bns;
-	int64_t l_pac = bns->l_pac;
+/* mem_chain's loop over the seeds of one read, in visiting order, on a list the caller gives (orc_mem_chain below makes the list from the read's intervals;
+ * orc_api_chain takes it from a test): rid[i] < 0 is a seed upstream drops.  The chains in the container's order, frac_rep not set. */
+orc_chain_v orc_chain_seeds(const orc_opt_t *opt, int64_t l_pac, int64_t n_seeds, const orc_seed_t *seeds, const int *rids)
+{
 	orc_chain_v chain = {0,0,0};
-	orc_intv_v mem = {0,0,0};
 	kbt_t tree = { 0, 0 };
-	if (len < opt->min_seed_len) return chain;
 	const int use_tree = chain_container();
 	if (use_tree) tree.root = calloc(1, sizeof(kbn_t));
-	orc_collect_intv(opt, bwt, len, seq, &mem);
-	for (i = 0, b = e = l_rep = 0; i < (int)mem.n; ++i) { /* frac_rep */
-		orc_intv_t *p = &mem.a[i];
+	for (int64_t si = 0; si < n_seeds; ++si) {
+		const orc_seed_t s = seeds[si];
+		const int rid = rids[si];
+		int to_add = 0;
+		if (rid < 0) continue;
+		if (use_tree) {   /* klib's B-tree; chain.a is the pool, in order of creation */
+			tree.pool = chain.a;
+			const int lw = chain.n ? kb_interval_lower(&tree, s.rbeg) : -1;
+			if (lw < 0 || !test_and_merge(opt, l_pac, &chain.a[lw], &s, rid)) {
+				orc_chain_t tmp; memset(&tmp, 0, sizeof(tmp));
+				tmp.pos = s.rbeg; tmp.n = 1; tmp.m = 4;
+				tmp.seeds = calloc(tmp.m, sizeof(orc_seed_t));
+				tmp.seeds[0] = s; tmp.rid = rid; tmp.is_alt = 0;
+				if (chain.n == chain.m) { chain.m = chain.m ? chain.m << 1 : 8; chain.a = realloc(chain.a, chain.m * sizeof(orc_chain_t)); }
+				chain.a[chain.n++] = tmp;
+				tree.pool = chain.a;
+				kb_putp(&tree, (int)chain.n - 1);
+			}
+			continue;
+		}
+		/* sorted-array stand-in for kb_intervalp/kb_putp (see file header) */
+		size_t lo = 0, hi = chain.n;
+		while (lo < hi) { size_t mid = (lo + hi) >> 1; if (chain.a[mid].pos < s.rbeg) lo = mid + 1; else hi = mid; }
+		long li = (lo < chain.n && chain.a[lo].pos == s.rbeg) ? (long)lo : (long)lo - 1;
+		if (chain.n) {
+			if (li < 0 || !test_and_merge(opt, l_pac, &chain.a[li], &s, rid)) to_add = 1;
+		} else to_add = 1;
+		if (to_add) {
+			orc_chain_t tmp; memset(&tmp, 0, sizeof(tmp));
+			tmp.pos = s.rbeg; tmp.n = 1; tmp.m = 4;
+			tmp.seeds = calloc(tmp.m, sizeof(orc_seed_t));
+			tmp.seeds[0] = s; tmp.rid = rid; tmp.is_alt = 0;
+			if (chain.n == chain.m) { chain.m = chain.m ? chain.m << 1 : 8; chain.a = realloc(chain.a, chain.m * sizeof(orc_chain_t)); }
+			size_t at = (size_t)(li + 1);
+			memmove(chain.a + at + 1, chain.a + at, (chain.n - at) * sizeof(orc_chain_t));
+			chain.a[at] = tmp; ++chain.n;
+		}
+	}
+	if (use_tree) {   /* the chains in the tree's order (mem_chain: __kb_traverse into the vector) */
+		int *ord = malloc((chain.n + 1) * sizeof(int)), no = 0;
+		orc_chain_t *srt = malloc((chain.n + 1) * sizeof(orc_chain_t));
+		kb_traverse(tree.root, ord, &no);
+		for (int i = 0; i < no; ++i) srt[i] = chain.a[ord[i]];
+		memcpy(chain.a, srt, no * sizeof(orc_chain_t));
+		free(ord); free(srt); kb_free(tree.root);
+	}
+	return chain;
+}
+
+/* upstream mem_chain's frac_rep head: the query bases under intervals with more than max_occ occurrences (a running merge of the start-sorted list), over the read length */
+float orc_frac_rep(const orc_opt_t *opt, int len, int n_intv, const orc_intv_t *intv)
+{
+	int i, b, e, l_rep;
+	for (i = 0, b = e = l_rep = 0; i < n_intv; ++i) {
+		const orc_intv_t *p = &intv[i];
 		int sb = (p->info >> 32), se = (uint32_t)p->info;
 		if (p->x[2] <= (uint64_t)opt->max_occ) continue;
 		if (sb > e) l_rep += e - b, b = sb, e = se;
 		else e = e > se ? e : se;
 	}
 	l_rep += e - b;
+	return (float)l_rep / len;
+}
+
+orc_chain_v orc_mem_chain(const orc_opt_t *opt, const orc_idx_t *idx, int len, const uint8_t *seq)
+{	/* upstream mem_chain */
+	int i;
+	const orc_bwt_t *bwt = idx->bwt; const orc_bns_t *bns = idx->bns;
+	orc_chain_v chain = {0,0,0};
+	orc_intv_v mem = {0,0,0};
+	struct { size_t n, m; orc_seed_t *a; } sd = {0,0,0};
+	struct { size_t n, m; int *a; } rd = {0,0,0};
+	if (len < opt->min_seed_len) return chain;
+	orc_collect_intv(opt, bwt, len, seq, &mem);
+	const float frac_rep = orc_frac_rep(opt, len, (int)mem.n, mem.a);
 	for (i = 0; i < (int)mem.n; ++i) {
 		orc_intv_t *p = &mem.a[i];
 		int step, count, slen = (uint32_t)p->info - (p->info >> 32);
@@ -322,56 +385,18 @@ orc_chain_v orc_mem_chain(const orc_opt_t *opt, const orc_idx_t *idx, int len, c
 		step = p->x[2] > (uint64_t)opt->max_occ ? p->x[2] / opt->max_occ : 1;
 		for (k = count = 0; k < (int64_t)p->x[2] && count < opt->max_occ; k += step, ++count) {
 			orc_seed_t s;
-			int rid, to_add = 0;
+			int rid;
+			memset(&s, 0, sizeof(s));   /* (padding included: orc_chain_exposure compares seeds as bytes) */
 			s.rbeg = orc_bwt_sa(bwt, p->x[0] + k);
 			s.qbeg = p->info >> 32;
 			s.score = s.len = slen;
 			rid = orc_bns_intv2rid(bns, s.rbeg, s.rbeg + s.len);
-			if (rid < 0) continue;
-			if (use_tree) {   /* klib's B-tree; chain.a is the pool, in order of creation */
-				tree.pool = chain.a;
-				const int lw = chain.n ? kb_interval_lower(&tree, s.rbeg) : -1;
-				if (lw < 0 || !test_and_merge(opt, l_pac, &chain.a[lw], &s, rid)) {
-					orc_chain_t tmp; memset(&tmp, 0, sizeof(tmp));
-					tmp.pos = s.rbeg; tmp.n = 1; tmp.m = 4;
-					tmp.seeds = calloc(tmp.m, sizeof(orc_seed_t));
-					tmp.seeds[0] = s; tmp.rid = rid; tmp.is_alt = 0;
-					if (chain.n == chain.m) { chain.m = chain.m ? chain.m << 1 : 8; chain.a = realloc(chain.a, chain.m * sizeof(orc_chain_t)); }
-					chain.a[chain.n++] = tmp;
-					tree.pool = chain.a;
-					kb_putp(&tree, (int)chain.n - 1);
-				}
-				continue;
-			}
-			/* sorted-array stand-in for kb_intervalp/kb_putp (see file header) */
-			size_t lo = 0, hi = chain.n;
-			while (lo < hi) { size_t mid = (lo + hi) >> 1; if (chain.a[mid].pos < s.rbeg) lo = mid + 1; else hi = mid; }
-			long li = (lo < chain.n && chain.a[lo].pos == s.rbeg) ? (long)lo : (long)lo - 1;
-			if (chain.n) {
-				if (li < 0 || !test_and_merge(opt, l_pac, &chain.a[li], &s, rid)) to_add = 1;
-			} else to_add = 1;
-			if (to_add) {
-				orc_chain_t tmp; memset(&tmp, 0, sizeof(tmp));
-				tmp.pos = s.rbeg; tmp.n = 1; tmp.m = 4;
-				tmp.seeds = calloc(tmp.m, sizeof(orc_seed_t));
-				tmp.seeds[0] = s; tmp.rid = rid; tmp.is_alt = 0;
-				if (chain.n == chain.m) { chain.m = chain.m ? chain.m << 1 : 8; chain.a = realloc(chain.a, chain.m * sizeof(orc_chain_t)); }
-				size_t at = (size_t)(li + 1);
-				memmove(chain.a + at + 1, chain.a + at, (chain.n - at) * sizeof(orc_chain_t));
-				chain.a[at] = tmp; ++chain.n;
-			}
+			PUSH(sd, orc_seed_t, s); PUSH(rd, int, rid);
 		}
 	}
-	if (use_tree) {   /* the chains in the tree's order (mem_chain: __kb_traverse into the vector) */
-		int *ord = malloc((chain.n + 1) * sizeof(int)), no = 0;
-		orc_chain_t *srt = malloc((chain.n + 1) * sizeof(orc_chain_t));
-		kb_traverse(tree.root, ord, &no);
-		for (i = 0; i < no; ++i) srt[i] = chain.a[ord[i]];
-		memcpy(chain.a, srt, no * sizeof(orc_chain_t));
-		free(ord); free(srt); kb_free(tree.root);
-	}
-	for (i = 0; i < (int)chain.n; ++i) chain.a[i].frac_rep = (float)l_rep / len;
-	free(mem.a);
+	chain = orc_chain_seeds(opt, bns->l_pac, (int64_t)sd.n, sd.a, rd.a);
+	for (i = 0; i < (int)chain.n; ++i) chain.a[i].frac_rep = frac_rep;
+	free(mem.a); free(sd.a); free(rd.a);
 	return chain;
 }
 
@@ -420,8 +445,10 @@ static int flt_lt(const void *a, const void *b) { return ((const orc_chain_t*)a)
 #define chn_beg(ch) ((ch).seeds->qbeg)
 #define chn_end(ch) ((ch).seeds[(ch).n-1].qbeg + (ch).seeds[(ch).n-1].len)
 
-int orc_mem_chain_flt(const orc_opt_t *opt, int n_chn, orc_chain_t *a)
-{	/* upstream mem_chain_flt */
+/* upstream mem_chain_flt up to its last loop: the chains below min_chain_weight dropped, the rest sorted by weight and marked (kept = 0 .. 3), none of the
+ * marked ones removed yet.  Returns their number.  orc_mem_chain_flt below finishes; orc_api_chain shows this state to the chaining reference's tests. */
+int orc_mem_chain_flt_mark(const orc_opt_t *opt, int n_chn, orc_chain_t *a)
+{
 	int i, k;
 	struct { size_t n, m; int *a; } chains = {0,0,0};
 	if (n_chn == 0) return 0;
@@ -433,6 +460,7 @@ int orc_mem_chain_flt(const orc_opt_t *opt, int n_chn, orc_chain_t *a)
 		else a[k++] = *c;
 	}
 	n_chn = k;
+	if (n_chn == 0) return 0;   /* every chain below min_chain_weight */
 	orc_introsort(a, n_chn, sizeof(orc_chain_t), flt_lt);
 	a[0].kept = 3;
 	PUSH(chains, int, 0);
@@ -465,6 +493,13 @@ int orc_mem_chain_flt(const orc_opt_t *opt, int n_chn, orc_chain_t *a)
 		if (++k >= opt->max_chain_extend) break;
 	}
 	for (; i < n_chn; ++i) if (a[i].kept < 3) a[i].kept = 0;
+	return n_chn;
+}
+
+int orc_mem_chain_flt(const orc_opt_t *opt, int n_chn, orc_chain_t *a)
+{	/* upstream mem_chain_flt */
+	int i, k;
+	n_chn = orc_mem_chain_flt_mark(opt, n_chn, a);
 	for (i = k = 0; i < n_chn; ++i) {
 		orc_chain_t *c = &a[i];
 		if (c->kept == 0) free(c->seeds);

@@ -27,6 +27,12 @@ OPT_DT = np.dtype([
 ], align=False)
 INTV_DT = np.dtype([("x0", "u8"), ("x1", "u8"), ("x2", "u8"), ("info", "u8")])
 SEED_DT = np.dtype([("rbeg", "i8"), ("qbeg", "i4"), ("len", "i4"), ("score", "i4"), ("next", "i4")])
+CHAIN_DT = np.dtype([("pos", "i8"), ("first_seed", "i4"), ("last_seed", "i4"), ("n", "i4"), ("rid", "i4"), ("w", "i4"), ("kept", "i4"), ("first", "i4"), ("sec", "i4"),
+                     ("left", "i4"), ("right", "i4"), ("frac_rep", "f4"), ("_pad", "i4")])
+# ssg_dbg_chain's form[]: the kernel that chained a read (include/ssgpu.h SSG_CHAIN_FORM_*)
+CHAIN_FORM_LANE, CHAIN_FORM_LDS16, CHAIN_FORM_LDS32, CHAIN_FORM_LDS64 = 0, 1, 2, 3
+CHAIN_FORM_WAVE256, CHAIN_FORM_WAVE512, CHAIN_FORM_WAVE1024, CHAIN_FORM_WAVE2048, CHAIN_FORM_WAVE5120 = 4, 5, 6, 7, 8
+CHAIN_FORM_TREE = 0x10
 EXT_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("w", "i4"), ("end_bonus", "i4"), ("zdrop", "i4"), ("h0", "i4")])
 EXT_RES_DT = np.dtype([("score", "i4"), ("qle", "i4"), ("tle", "i4"), ("gtle", "i4"), ("gscore", "i4"), ("max_off", "i4")])
 SW_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("xtra", "i4"), ("_pad", "i4")])
@@ -174,6 +180,28 @@ class Lib:
         o0, o1 = np.zeros(len(keys), dtype=np.int64), np.zeros(len(keys), dtype=np.int64)
         self._chk(self.l.ssg_dbg_chain_sort(_ptr(keys), C.c_int(len(keys)), _ptr(o0), _ptr(o1)))
         return o0, o1
+
+    def dbg_chain(self, opt, l_pac, n_ctg, read_len, seed_off, seeds, rids, intv_off, intv):
+        """the chaining stage on given seeds and intervals (ssg_dbg_chain): (chain_off, surviving chains in final order [CHAIN_DT; first_seed = offset into the
+        next array], their seed indices counted from the read's first seed, the kernel form that took each read [CHAIN_FORM_*])"""
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.int64)
+        intv_off = np.ascontiguousarray(intv_off, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=SEED_DT)
+        rids = np.ascontiguousarray(rids, dtype=np.int32)
+        intv = np.ascontiguousarray(intv, dtype=INTV_DT)
+        n = len(read_len)
+        assert len(seed_off) == n + 1 and len(intv_off) == n + 1 and len(seeds) >= seed_off[-1] and len(rids) >= seed_off[-1] and len(intv) >= intv_off[-1]
+        chain_off, form = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        cp, sp = C.c_void_p(), C.c_void_p()
+        self._chk(self.l.ssg_dbg_chain(_ptr(opt), C.c_int64(l_pac), C.c_int(n_ctg), C.c_int(n), _ptr(read_len), _ptr(seed_off), _ptr(seeds), _ptr(rids), _ptr(intv_off), _ptr(intv),
+                                       _ptr(chain_off), C.byref(cp), C.byref(sp), _ptr(form)))
+        nc = int(chain_off[n])
+        chains = np.frombuffer((C.c_char * (nc * CHAIN_DT.itemsize)).from_address(cp.value), dtype=CHAIN_DT, count=nc).copy() if nc else np.zeros(0, CHAIN_DT)
+        ns = int(chains["n"].sum()) if nc else 0
+        cseeds = np.frombuffer((C.c_char * (ns * 4)).from_address(sp.value), dtype=np.int32, count=ns).copy() if ns else np.zeros(0, np.int32)
+        self.l.ssg_free(cp); self.l.ssg_free(sp)
+        return chain_off, chains, cseeds, form
 
     def dbg_pestat(self, idx, opt, reg_off, regs, pair_batch, n_batches):
         """mem_pestat on given region lists (ssg_dbg_pestat): n_batches x 4 insert-size models"""

@@ -281,9 +281,13 @@ SSG_DEVFN int wv_chain_read(const ssg_index_view_t &ix, const ssg_mem_opt_t &opt
 				const int stride = (nc + 63) >> 6;
 				const int e1 = (lane + 1) * stride - 1;
 				const int nb = __popcll(wv_ballot(e1 < nc && L.b8[e1 < nc ? e1 : 0] < rbeg));   /* blocks wholly below rbeg */
-				const int e2 = nb * stride + lane;
-				const int in = lane < stride && e2 < nc;
-				cnt = nb * stride + __popcll(wv_ballot(in && L.b8[in ? e2 : 0] < rbeg));
+				int below = 0;   /* inside that block: it has `stride' entries, more than the wave has lanes once a read has more than 4096 chains (the 5120 class alone) */
+				for (int o = 0; o < (CAPC > 4096 ? stride : 1); o += 64) {
+					const int e2 = nb * stride + o + lane;
+					const int in = o + lane < stride && e2 < nc;
+					below += __popcll(wv_ballot(in && L.b8[in ? e2 : 0] < rbeg));
+				}
+				cnt = nb * stride + below;
 			}
 			const int eq = cnt < nc && L.b8[cnt < nc ? cnt : 0] == rbeg;
 			const int lower = cnt - 1 + eq;

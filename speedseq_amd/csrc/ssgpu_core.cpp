@@ -730,6 +730,140 @@ static int run_locate(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 }
 
 static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, long n);   /* (defined behind the pairing stage: see there) */
+/* The chaining stage (upstream mem_chain + mem_chain_flt, rows a4-a5) of a batch whose seeds are placed: the class split by seed count, the launches of every kernel
+ * form with the SSG_CHAIN_* switches, and the second pass on klib's B-tree.  One function for stage 1 of the pipeline (run_align1) and for the test entry on seeds
+ * given by the caller (ssg_dbg_chain), which hands over a view with l_pac and n_ctg alone: the kernels read nothing else of the index.  d_work: the reads heaviest
+ * first (seed count), d_queue: 8 zeroed counters.  n_tree (may be NULL): reads chained again on the tree.  form (may be NULL, host, n_reads): the kernel form that
+ * took each read, SSG_CHAIN_FORM_* of ssgpu.h. */
+static int run_chain(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const int64_t *d_off, int max_len, const ssg_intv_t *d_intv, const int32_t *d_nintv, int cap,
+                     const int32_t *d_nseed, const int64_t *seed_off, ssg_seed_t *d_seeds, const int32_t *d_srid, ssg_chain_t *d_chains, int32_t *d_order, int32_t *d_kept,
+                     int32_t *d_cseeds, int32_t *d_nchain, const int32_t *d_work, unsigned int *d_queue, uint64_t *n_tree, int32_t *form)
+{
+	/* d_work is heaviest first.  Reads with >= T seeds chain one wave each with their state in LDS, in four size classes that run
+	 * concurrently (up to 5120, 2048, 1024, 512, 256 seeds = chains: 155 / 62 / 31 / 16 / 8 KB); the light rest one lane per read; the (very
+	 * few) reads beyond 5120 seeds one lane each on their own stream.  The LDS kernels keep contig ids in 16 bits: an index with
+	 * more contigs chains every read in the lane kernel.  SSG_CHAIN_WAVE_BIG = n sends every wave-class read with more than n seeds
+	 * to the top class (tests); SSG_CHAIN_RANKED = 0 selects the array-shifting form of the insertion (A/B, tests). */
+	const int T = ix.n_ctg > 32767 ? 1 << 30 : std::max(1, env_int("SSG_CHAIN_WAVE_MIN", 48));
+	const int TB = env_int("SSG_CHAIN_WAVE_BIG", 0) > 0 ? env_int("SSG_CHAIN_WAVE_BIG", 0) : 1 << 30;
+	const bool ranked = env_int("SSG_CHAIN_RANKED", 1) != 0;
+	const int cap_lim = env_int("SSG_CHAIN_CAP_TEST", 1 << 30);   /* tests: pretend the ranked form holds fewer chains, to walk its fall-back (the shifting form) */
+	int g[7], gl[3];   /* gl: reads with more than 63 / 31 / 15 seeds (the classes of the light reads' LDS kernel) */
+	{	/* "greater than" counts of the seeds-per-read array (d_work sorts it descending: a binary search per threshold; thresholds descending: the counts ascend) */
+		ssg_thr6_t th = { { 1 << 30, 5120, std::min(2048, TB), std::min(1024, TB), std::min(512, TB), std::min(256, TB), T - 1, 63, 31, 15 } };
+		dbuf<unsigned int> d_c(16); unsigned int c[10];
+		CHKA(d_c); CHK(d_c.zero());
+		SSG_LAUNCH(ssg_k_count_gt6, 1, 64, 0, d_nseed, d_work, (long)n_reads, th, d_c.p);
+		CHK(d_c.down(c, 10));
+		for (int i = 0; i < 7; ++i) g[i] = (int)std::min(c[i], c[6]);
+		for (int i = 1; i < 7; ++i) g[i] = std::max(g[i], g[i - 1]);
+		for (int i = 0; i < 3; ++i) gl[i] = (int)c[7 + i];
+	}
+	const int n_heavy = g[6];
+	const int nC = g[1], n5120 = g[2] - g[1], n2048 = g[3] - g[2], n1024 = g[4] - g[3], n512 = g[5] - g[4], n256 = g[6] - g[5];
+	const int dbgp = ssg_debug() >= 2 ? -1 : 0;
+	/* reads whose chains may lie differently in upstream's B-tree than in the kernels' (pos, sec) order -- more than 9 chains AND two at one position -- are flagged by
+	 * every chaining kernel and chained again on the tree itself afterwards (k_chain.h ssg_k_chain_kb); SSG_CHAIN_KBTREE=0 leaves them as they are (the array order: tests) */
+	dbuf<int32_t> d_kbflag((size_t)n_reads);
+	CHKA(d_kbflag); CHK(d_kbflag.zero());
+	int32_t *const kbf = env_int("SSG_CHAIN_KBTREE", 1) ? d_kbflag.p : (int32_t*)0;
+	/* an error return between the fork and the join below hands this scope's buffers back to the arena: not before the side streams' kernels, which write them, are done */
+	struct fork_guard_t { int n; bool armed; ~fork_guard_t() { if (armed) { ssg_join(n); (void)rt_sync(); } } } fork_guard = { 3, true };
+	ssg_fork(3);
+	int lb[4];   /* places in d_work where the light reads' classes begin: global lane, LDS 64, 32, 16 */
+	{	/* The light reads go first, on a stream of their own, while this one ranks the heavy reads' seeds (small latency-bound launches that leave the chip idle); behind the wave
+		 * kernels they would wait for LDS (the 63-seed class asks for 94 KB a workgroup) and run as a tail.  Heaviest first: up to 15 / 31 / 63 seeds with the read's state in the lane's part of LDS (k_chain.h), the rest -- and everything when the
+		 * index has too many contigs for 14 bits, a read is too long for 9-bit query coordinates, or SSG_CHAIN_LDS = 0 (A/B, tests) -- on global memory */
+		const bool use_lds = env_int("SSG_CHAIN_LDS", 1) != 0 && ix.n_ctg < 0x3fff && max_len < 512;
+		const int r0 = n_heavy;
+		const int b63 = use_lds ? std::min(n_reads, std::max(r0, gl[0])) : n_reads, b31 = std::min(n_reads, std::max(b63, gl[1])), b15 = std::min(n_reads, std::max(b31, gl[2]));
+		lb[0] = r0; lb[1] = b63; lb[2] = b31; lb[3] = b15;
+		if (b63 > r0) SSG_LAUNCH_ON(2, ssg_k_chain, (b63 - r0 + 63) / 64, 64, 0, ix, *opt, r0, b63, d_off, d_intv, d_nintv, cap, seed_off, d_seeds, d_srid,
+		                   d_chains, d_order, d_kept, d_cseeds, d_nchain, dbgp, d_work, kbf);
+#define SSG_CL_LAUNCH(CC, LN, from, to) do { if ((to) > (from)) SSG_LAUNCH_ON(2, (ssg_k_chain_lds<CC, LN>), ((to) - (from) + (LN) - 1) / (LN), (LN), 0, ix, *opt, (from), (to), d_off, d_intv, d_nintv, cap, seed_off, d_seeds, d_srid, \
+		d_chains, d_order, d_cseeds, d_nchain, d_work, kbf); } while (0)
+		SSG_CL_LAUNCH(64, 32, b63, b31);   /* 32 reads a workgroup: 47 KB instead of 94, fits beside the wave kernels' blocks */
+		SSG_CL_LAUNCH(32, 64, b31, b15);
+		SSG_CL_LAUNCH(16, 64, b15, n_reads);
+#undef SSG_CL_LAUNCH
+	}
+	/* position ranks of the heavy reads' seeds: one stable radix sort of (read, reference position) over all of them */
+	dbuf<uint16_t> d_hrank; dbuf<int64_t> d_hoff;
+	if (ranked && n_heavy > nC) {
+		dbuf<int32_t> d_hns(n_heavy);
+		CHKA(d_hns);
+		if (!d_hoff.alloc((size_t)n_heavy + 1)) { ssg_err_msg = "device allocation failed: d_hoff"; return SSG_ENOMEM; }
+		SSG_LAUNCH(ssg_k_chw_count, (n_heavy + 255) / 256, 256, 0, n_heavy, d_work, seed_off, d_hns.p);
+		int64_t n_hs = 0;
+		CHK(ssg_dev_exclusive_scan(d_hns.p, d_hoff.p, n_heavy, &n_hs));
+		if (n_hs >= (1LL << 32)) { ssg_err_msg = "more than 2^32 seeds in repeat-heavy reads of one call"; return SSG_EOVERFLOW; }
+		dbuf<uint64_t> d_hk((size_t)n_hs + 1), d_hks((size_t)n_hs + 1); dbuf<uint32_t> d_hv((size_t)n_hs + 1), d_hvs((size_t)n_hs + 1);
+		CHKA(d_hk); CHKA(d_hks); CHKA(d_hv); CHKA(d_hvs);
+		if (!d_hrank.alloc((size_t)n_hs + 1)) { ssg_err_msg = "device allocation failed: d_hrank"; return SSG_ENOMEM; }
+		SSG_LAUNCH(ssg_k_chw_keys, n_heavy, 64, 0, n_heavy, d_work, seed_off, d_seeds, d_hoff.p, d_hk.p, d_hv.p);
+		CHK(sort_pairs_u64(d_hk.p, d_hks.p, d_hv.p, d_hvs.p, (long)n_hs)); CHK(rt_sync());
+		SSG_LAUNCH(ssg_k_chw_ranks, (n_hs + 255) / 256, 256, 0, (long)n_hs, d_hks.p, d_hvs.p, d_hoff.p, d_hrank.p);
+		CHK(rt_sync());
+	}
+	const uint16_t *hr = ranked ? d_hrank.p : (const uint16_t*)0; const int64_t *ho = ranked ? d_hoff.p : (const int64_t*)0;
+	/* the classes are independent and each of the heavy ones fills a fraction of the chip: overlap them */
+	/* four queues: the two big classes one each, the short jobs (top class, small classes, then the one-lane monsters) in a row on the third,
+	 * the light reads' lane kernel on the default stream (more streams than hardware queues serialize behind one another anyway) */
+	ssg_fork(2);   /* (again, the wave kernels' two streams: they read the ranks) */
+	int r0 = nC;
+#define SSG_CHW_LAUNCH(si, CC, cnt, maxwg, qi) do { if ((cnt) > 0) SSG_LAUNCH_ON(si, ssg_k_chain_wave<CC>, std::min((int)(cnt), (int)(maxwg)), 64, 0, ix, *opt, r0, r0 + (cnt), d_off, d_intv, d_nintv, cap, \
+	seed_off, d_seeds, d_srid, d_chains, d_order, d_cseeds, d_nchain, d_work, d_queue + (qi), kbf, hr, ho, std::min((int)(CC), cap_lim)); r0 += (cnt); } while (0)
+	SSG_CHW_LAUNCH(0, 5120, n5120, 256, 1);
+	SSG_CHW_LAUNCH(1, 2048, n2048, 512, 3);
+	SSG_CHW_LAUNCH(1, 1024, n1024, 1280, 2);   /* (behind the 2048 class: this stream + two side streams + the light reads' stream are the four hardware queues; a fifth stream shares one) */
+	SSG_CHW_LAUNCH(0, 512, n512, 2560, 5);
+	SSG_CHW_LAUNCH(0, 256, n256, 5120, 4);
+#undef SSG_CHW_LAUNCH
+	if (nC) SSG_LAUNCH_ON(0, ssg_k_chain, (nC + 63) / 64, 64, 0, ix, *opt, 0, nC, d_off, d_intv, d_nintv, cap, seed_off, d_seeds, d_srid,
+	                   d_chains, d_order, d_kept, d_cseeds, d_nchain, dbgp, d_work, kbf);
+	ssg_join(3);
+	fork_guard.armed = false;
+	if (form) {   /* the class of every place of the work order, as launched above */
+		std::vector<int32_t> hw((size_t)n_reads);
+		CHK(rt_d2h(hw.data(), d_work, (size_t)n_reads * sizeof(int32_t)));
+		const int wb[6] = { nC, nC + n5120, nC + n5120 + n2048, nC + n5120 + n2048 + n1024, nC + n5120 + n2048 + n1024 + n512, n_heavy };
+		for (int k = 0; k < n_reads; ++k) {
+			int f = SSG_CHAIN_FORM_LANE;
+			if (k >= lb[3]) f = SSG_CHAIN_FORM_LDS16; else if (k >= lb[2]) f = SSG_CHAIN_FORM_LDS32; else if (k >= lb[1]) f = SSG_CHAIN_FORM_LDS64;
+			else if (k >= lb[0]) f = SSG_CHAIN_FORM_LANE;
+			else for (int c = 0; c < 5; ++c) if (k >= wb[c] && k < wb[c + 1]) f = SSG_CHAIN_FORM_WAVE5120 - c;
+			form[hw[k]] = f;
+		}
+	}
+	if (kbf) {   /* the flagged reads (none in a million simulated human pairs; the constructed reads of tests/test_chain_btree.py) on klib's B-tree */
+		dbuf<int32_t> d_klist((size_t)n_reads), d_kneed((size_t)n_reads); dbuf<unsigned int> d_nk(1);
+		CHKA(d_klist); CHKA(d_kneed); CHKA(d_nk); CHK(d_nk.zero());
+		SSG_LAUNCH(ssg_k_chain_kb_list, (n_reads + 255) / 256, 256, 0, n_reads, (const int32_t*)d_kbflag.p, seed_off, d_klist.p, d_kneed.p, d_nk.p);
+		unsigned int nk = 0;
+		CHK(d_nk.down(&nk, 1));
+		if (n_tree) *n_tree = nk;
+		if (nk) {
+			std::vector<int32_t> kl(nk), kn(nk);   /* (the list in read order: the kernel's atomics hand out places as they come) */
+			CHK(d_klist.down(kl.data(), nk)); CHK(d_kneed.down(kn.data(), nk));
+			std::vector<size_t> by(nk); for (size_t i = 0; i < nk; ++i) by[i] = i;
+			std::sort(by.begin(), by.end(), [&](size_t a, size_t b) { return kl[a] < kl[b]; });
+			std::vector<int32_t> kl2(nk); std::vector<int64_t> ko((size_t)nk + 1, 0);
+			for (size_t i = 0; i < nk; ++i) { kl2[i] = kl[by[i]]; ko[i + 1] = ko[i] + kn[by[i]]; }
+			dbuf<int32_t> d_slab((size_t)ko[nk] + 1), d_kerr(1); dbuf<int64_t> d_ko((size_t)nk + 1);
+			CHKA(d_slab); CHKA(d_kerr); CHKA(d_ko); CHK(d_kerr.zero());
+			CHK(d_klist.up(kl2.data(), nk)); CHK(d_ko.up(ko.data(), (size_t)nk + 1));
+			SSG_LAUNCH(ssg_k_chain_kb, (nk + 63) / 64, 64, 0, ix, *opt, (int)nk, (const int32_t*)d_klist.p, d_off, d_intv, d_nintv, cap, seed_off, d_seeds, d_srid,
+			           d_chains, d_order, d_kept, d_cseeds, d_nchain, d_slab.p, (const int64_t*)d_ko.p, d_kerr.p);
+			int32_t ke = 0;
+			CHK(d_kerr.down(&ke, 1));
+			if (ke) { ssg_err_msg = "chaining on the B-tree exceeded its node slab"; return SSG_EOVERFLOW; }
+			if (ssg_debug()) fprintf(stderr, "[ssgpu] %u reads chained again on klib's B-tree (more than 9 chains and two at one position)\n", nk);
+			if (form) for (size_t i = 0; i < nk; ++i) form[kl2[i]] |= SSG_CHAIN_FORM_TREE;
+		}
+	}
+	return 0;
+}
+
 static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len,
                       align1_dev_t &o, uint64_t stats[8])
 {
@@ -780,114 +914,8 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		for (int r = 0; r < n_reads; ++r) { int b = 0; while ((1 << b) <= hns[r] && b < 19) ++b; ++cnt[b]; sum[b] += hns[r]; }
 		for (int b = 0; b < 20; ++b) if (cnt[b]) fprintf(stderr, "[ssg] seeds/read < %d: %ld reads, %ld seeds\n", 1 << b, cnt[b], sum[b]);
 	}
-	{	/* d_work is heaviest first.  Reads with >= T seeds chain one wave each with their state in LDS, in four size classes that run
-		 * concurrently (up to 5120, 2048, 1024, 512, 256 seeds = chains: 155 / 62 / 31 / 16 / 8 KB); the light rest one lane per read; the (very
-		 * few) reads beyond 5120 seeds one lane each on their own stream.  The LDS kernels keep contig ids in 16 bits: an index with
-		 * more contigs chains every read in the lane kernel.  SSG_CHAIN_WAVE_BIG = n sends every wave-class read with more than n seeds
-		 * to the top class (tests); SSG_CHAIN_RANKED = 0 selects the array-shifting form of the insertion (A/B, tests). */
-		const int T = idx->v.n_ctg > 32767 ? 1 << 30 : std::max(1, env_int("SSG_CHAIN_WAVE_MIN", 48));
-		const int TB = env_int("SSG_CHAIN_WAVE_BIG", 0) > 0 ? env_int("SSG_CHAIN_WAVE_BIG", 0) : 1 << 30;
-		const bool ranked = env_int("SSG_CHAIN_RANKED", 1) != 0;
-		const int cap_lim = env_int("SSG_CHAIN_CAP_TEST", 1 << 30);   /* tests: pretend the ranked form holds fewer chains, to walk its fall-back (the shifting form) */
-		int g[7], gl[3];   /* gl: reads with more than 63 / 31 / 15 seeds (the classes of the light reads' LDS kernel) */
-		{	/* "greater than" counts of the seeds-per-read array (d_work sorts it descending: a binary search per threshold; thresholds descending: the counts ascend) */
-			ssg_thr6_t th = { { 1 << 30, 5120, std::min(2048, TB), std::min(1024, TB), std::min(512, TB), std::min(256, TB), T - 1, 63, 31, 15 } };
-			dbuf<unsigned int> d_c(16); unsigned int c[10];
-			CHKA(d_c); CHK(d_c.zero());
-			SSG_LAUNCH(ssg_k_count_gt6, 1, 64, 0, d_nseed.p, d_work.p, (long)n_reads, th, d_c.p);
-			CHK(d_c.down(c, 10));
-			for (int i = 0; i < 7; ++i) g[i] = (int)std::min(c[i], c[6]);
-			for (int i = 1; i < 7; ++i) g[i] = std::max(g[i], g[i - 1]);
-			for (int i = 0; i < 3; ++i) gl[i] = (int)c[7 + i];
-		}
-		const int n_heavy = g[6];
-		const int nC = g[1], n5120 = g[2] - g[1], n2048 = g[3] - g[2], n1024 = g[4] - g[3], n512 = g[5] - g[4], n256 = g[6] - g[5];
-		const int dbgp = ssg_debug() >= 2 ? -1 : 0;
-		/* reads whose chains may lie differently in upstream's B-tree than in the kernels' (pos, sec) order -- more than 9 chains AND two at one position -- are flagged by
-		 * every chaining kernel and chained again on the tree itself afterwards (k_chain.h ssg_k_chain_kb); SSG_CHAIN_KBTREE=0 leaves them as they are (the array order: tests) */
-		dbuf<int32_t> d_kbflag((size_t)n_reads);
-		CHKA(d_kbflag); CHK(d_kbflag.zero());
-		int32_t *const kbf = env_int("SSG_CHAIN_KBTREE", 1) ? d_kbflag.p : (int32_t*)0;
-		/* an error return between the fork and the join below hands this scope's buffers back to the arena: not before the side streams' kernels, which write them, are done */
-		struct fork_guard_t { int n; bool armed; ~fork_guard_t() { if (armed) { ssg_join(n); (void)rt_sync(); } } } fork_guard = { 3, true };
-		ssg_fork(3);
-		{	/* The light reads go first, on a stream of their own, while this one ranks the heavy reads' seeds (small latency-bound launches that leave the chip idle); behind the wave
-			 * kernels they would wait for LDS (the 63-seed class asks for 94 KB a workgroup) and run as a tail.  Heaviest first: up to 15 / 31 / 63 seeds with the read's state in the lane's part of LDS (k_chain.h), the rest -- and everything when the
-			 * index has too many contigs for 14 bits, a read is too long for 9-bit query coordinates, or SSG_CHAIN_LDS = 0 (A/B, tests) -- on global memory */
-			const bool use_lds = env_int("SSG_CHAIN_LDS", 1) != 0 && idx->v.n_ctg < 0x3fff && max_len < 512;
-			const int r0 = n_heavy;
-			const int b63 = use_lds ? std::min(n_reads, std::max(r0, gl[0])) : n_reads, b31 = std::min(n_reads, std::max(b63, gl[1])), b15 = std::min(n_reads, std::max(b31, gl[2]));
-			if (b63 > r0) SSG_LAUNCH_ON(2, ssg_k_chain, (b63 - r0 + 63) / 64, 64, 0, idx->v, *opt, r0, b63, d_off, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p,
-			                   d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p, dbgp, d_work.p, kbf);
-#define SSG_CL_LAUNCH(CC, LN, from, to) do { if ((to) > (from)) SSG_LAUNCH_ON(2, (ssg_k_chain_lds<CC, LN>), ((to) - (from) + (LN) - 1) / (LN), (LN), 0, idx->v, *opt, (from), (to), d_off, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p, \
-			d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, kbf); } while (0)
-			SSG_CL_LAUNCH(64, 32, b63, b31);   /* 32 reads a workgroup: 47 KB instead of 94, fits beside the wave kernels' blocks */
-			SSG_CL_LAUNCH(32, 64, b31, b15);
-			SSG_CL_LAUNCH(16, 64, b15, n_reads);
-#undef SSG_CL_LAUNCH
-		}
-		/* position ranks of the heavy reads' seeds: one stable radix sort of (read, reference position) over all of them */
-		dbuf<uint16_t> d_hrank; dbuf<int64_t> d_hoff;
-		if (ranked && n_heavy > nC) {
-			dbuf<int32_t> d_hns(n_heavy);
-			CHKA(d_hns);
-			if (!d_hoff.alloc((size_t)n_heavy + 1)) { ssg_err_msg = "device allocation failed: d_hoff"; return SSG_ENOMEM; }
-			SSG_LAUNCH(ssg_k_chw_count, (n_heavy + 255) / 256, 256, 0, n_heavy, d_work.p, o.seed_off.p, d_hns.p);
-			int64_t n_hs = 0;
-			CHK(ssg_dev_exclusive_scan(d_hns.p, d_hoff.p, n_heavy, &n_hs));
-			if (n_hs >= (1LL << 32)) { ssg_err_msg = "more than 2^32 seeds in repeat-heavy reads of one call"; return SSG_EOVERFLOW; }
-			dbuf<uint64_t> d_hk((size_t)n_hs + 1), d_hks((size_t)n_hs + 1); dbuf<uint32_t> d_hv((size_t)n_hs + 1), d_hvs((size_t)n_hs + 1);
-			CHKA(d_hk); CHKA(d_hks); CHKA(d_hv); CHKA(d_hvs);
-			if (!d_hrank.alloc((size_t)n_hs + 1)) { ssg_err_msg = "device allocation failed: d_hrank"; return SSG_ENOMEM; }
-			SSG_LAUNCH(ssg_k_chw_keys, n_heavy, 64, 0, n_heavy, d_work.p, o.seed_off.p, d_seeds.p, d_hoff.p, d_hk.p, d_hv.p);
-			CHK(sort_pairs_u64(d_hk.p, d_hks.p, d_hv.p, d_hvs.p, (long)n_hs)); CHK(rt_sync());
-			SSG_LAUNCH(ssg_k_chw_ranks, (n_hs + 255) / 256, 256, 0, (long)n_hs, d_hks.p, d_hvs.p, d_hoff.p, d_hrank.p);
-			CHK(rt_sync());
-		}
-		const uint16_t *hr = ranked ? d_hrank.p : (const uint16_t*)0; const int64_t *ho = ranked ? d_hoff.p : (const int64_t*)0;
-		/* the classes are independent and each of the heavy ones fills a fraction of the chip: overlap them */
-		/* four queues: the two big classes one each, the short jobs (top class, small classes, then the one-lane monsters) in a row on the third,
-		 * the light reads' lane kernel on the default stream (more streams than hardware queues serialize behind one another anyway) */
-		ssg_fork(2);   /* (again, the wave kernels' two streams: they read the ranks) */
-		int r0 = nC;
-#define SSG_CHW_LAUNCH(si, CC, cnt, maxwg, qi) do { if ((cnt) > 0) SSG_LAUNCH_ON(si, ssg_k_chain_wave<CC>, std::min((int)(cnt), (int)(maxwg)), 64, 0, idx->v, *opt, r0, r0 + (cnt), d_off, d_intv.p, d_nintv.p, cap, \
-		o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p + (qi), kbf, hr, ho, std::min((int)(CC), cap_lim)); r0 += (cnt); } while (0)
-		SSG_CHW_LAUNCH(0, 5120, n5120, 256, 1);
-		SSG_CHW_LAUNCH(1, 2048, n2048, 512, 3);
-		SSG_CHW_LAUNCH(1, 1024, n1024, 1280, 2);   /* (behind the 2048 class: this stream + two side streams + the light reads' stream are the four hardware queues; a fifth stream shares one) */
-		SSG_CHW_LAUNCH(0, 512, n512, 2560, 5);
-		SSG_CHW_LAUNCH(0, 256, n256, 5120, 4);
-#undef SSG_CHW_LAUNCH
-		if (nC) SSG_LAUNCH_ON(0, ssg_k_chain, (nC + 63) / 64, 64, 0, idx->v, *opt, 0, nC, d_off, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p,
-		                   d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p, dbgp, d_work.p, kbf);
-		ssg_join(3);
-		fork_guard.armed = false;
-		if (kbf) {   /* the flagged reads (none in a million simulated human pairs; the constructed reads of tests/test_chain_btree.py) on klib's B-tree */
-			dbuf<int32_t> d_klist((size_t)n_reads), d_kneed((size_t)n_reads); dbuf<unsigned int> d_nk(1);
-			CHKA(d_klist); CHKA(d_kneed); CHKA(d_nk); CHK(d_nk.zero());
-			SSG_LAUNCH(ssg_k_chain_kb_list, (n_reads + 255) / 256, 256, 0, n_reads, (const int32_t*)d_kbflag.p, o.seed_off.p, d_klist.p, d_kneed.p, d_nk.p);
-			unsigned int nk = 0;
-			CHK(d_nk.down(&nk, 1));
-			if (stats) stats[7] = nk;
-			if (nk) {
-				std::vector<int32_t> kl(nk), kn(nk);   /* (the list in read order: the kernel's atomics hand out places as they come) */
-				CHK(d_klist.down(kl.data(), nk)); CHK(d_kneed.down(kn.data(), nk));
-				std::vector<size_t> by(nk); for (size_t i = 0; i < nk; ++i) by[i] = i;
-				std::sort(by.begin(), by.end(), [&](size_t a, size_t b) { return kl[a] < kl[b]; });
-				std::vector<int32_t> kl2(nk); std::vector<int64_t> ko((size_t)nk + 1, 0);
-				for (size_t i = 0; i < nk; ++i) { kl2[i] = kl[by[i]]; ko[i + 1] = ko[i] + kn[by[i]]; }
-				dbuf<int32_t> d_slab((size_t)ko[nk] + 1), d_kerr(1); dbuf<int64_t> d_ko((size_t)nk + 1);
-				CHKA(d_slab); CHKA(d_kerr); CHKA(d_ko); CHK(d_kerr.zero());
-				CHK(d_klist.up(kl2.data(), nk)); CHK(d_ko.up(ko.data(), (size_t)nk + 1));
-				SSG_LAUNCH(ssg_k_chain_kb, (nk + 63) / 64, 64, 0, idx->v, *opt, (int)nk, (const int32_t*)d_klist.p, d_off, d_intv.p, d_nintv.p, cap, o.seed_off.p, d_seeds.p, d_srid.p,
-				           d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p, d_slab.p, (const int64_t*)d_ko.p, d_kerr.p);
-				int32_t ke = 0;
-				CHK(d_kerr.down(&ke, 1));
-				if (ke) { ssg_err_msg = "chaining on the B-tree exceeded its node slab"; return SSG_EOVERFLOW; }
-				if (ssg_debug()) fprintf(stderr, "[ssgpu] %u reads chained again on klib's B-tree (more than 9 chains and two at one position)\n", nk);
-			}
-		}
-	}
+	CHK(run_chain(idx->v, opt, n_reads, d_off, max_len, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p,
+	              d_work.p, d_queue.p, stats ? &stats[7] : (uint64_t*)0, (int32_t*)0));
 	STAGE("chain");
 	/* ---- extensions of every chain's first seed, one lane each (k_extlane.h) ---- */
 	dbuf<int64_t> d_choff((size_t)n_reads + 1);
@@ -1005,6 +1033,96 @@ int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_read
 	if (!*seeds || !*rids) { free(*seeds); free(*rids); *seeds = 0; *rids = 0; ssg_err_msg = "host allocation failed"; return SSG_ENOMEM; }
 	CHK(d_seeds.down(*seeds, (size_t)tot)); CHK(d_srid.down(*rids, (size_t)tot));
 	return 0;
+}
+
+/* test entry: the chaining stage on the caller's seeds and intervals (include/ssgpu.h), through run_chain as stage 1 goes through it */
+int ssg_dbg_chain(const ssg_mem_opt_t *opt, int64_t l_pac, int n_ctg, int n_reads, const int32_t *read_len, const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *rids,
+                  const int64_t *intv_off, const ssg_intv_t *intv, int64_t *chain_off, ssg_chain_t **chains, int32_t **chain_seeds, int32_t *form)
+{
+	static thread_local char msg[160];
+	CHK(ssg_need_device());
+	*chains = 0; *chain_seeds = 0;
+	if (n_reads < 0 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) { ssg_err_msg = "ssg_dbg_chain: need n_reads >= 0, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
+	if (n_reads == 0) { chain_off[0] = 0; return SSG_OK; }
+	const char *bad = 0; long at = 0;
+	if (seed_off[0] != 0 || intv_off[0] != 0) bad = "offsets start at 0: read";
+	int max_len = 0, cap = 1;
+	for (int r = 0; !bad && r < n_reads; ++r) {
+		const int len = read_len[r];
+		at = r;
+		if (seed_off[r + 1] < seed_off[r] || intv_off[r + 1] < intv_off[r]) { bad = "offsets must not decrease: read"; break; }
+		if (seed_off[r + 1] - seed_off[r] >= (int64_t)1 << 24 || intv_off[r + 1] - intv_off[r] >= (int64_t)1 << 24) { bad = "more than 2^24 seeds or intervals: read"; break; }
+		if (len < 1 || len > SSG_MAX_READ_LEN) { bad = "need 1 <= read_len <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
+		max_len = std::max(max_len, len); cap = std::max(cap, (int)(intv_off[r + 1] - intv_off[r]));
+		for (int64_t k = seed_off[r]; !bad && k < seed_off[r + 1]; ++k) {
+			const ssg_seed_t &s = seeds[k];
+			if (!(0 <= s.qbeg && 1 <= s.len && s.qbeg <= len - s.len)) bad = "need 0 <= qbeg, 1 <= len, qbeg + len <= read_len: seed";
+			else if (!(0 <= s.rbeg && s.rbeg <= 2 * l_pac - s.len)) bad = "need 0 <= rbeg, rbeg + len <= 2 l_pac: seed";
+			else if (rids[k] >= n_ctg) bad = "rid beyond the contigs: seed";
+			if (bad) at = (long)k;
+		}
+		int64_t prev = 0;
+		for (int64_t k = intv_off[r]; !bad && k < intv_off[r + 1]; ++k) {
+			const int64_t sb = (int64_t)(intv[k].info >> 32), se = (int64_t)(uint32_t)intv[k].info;
+			if (!(sb < se && se <= len)) bad = "need 0 <= start < end <= read_len: interval";
+			else if (sb < prev) bad = "intervals must be sorted by start: interval";
+			prev = sb;
+			if (bad) at = (long)k;
+		}
+	}
+	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_chain: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
+	const int64_t tot = seed_off[n_reads];
+	if (tot >= (int64_t)1 << 31) { ssg_err_msg = "ssg_dbg_chain: more than 2^31 seeds"; return SSG_EINVAL; }
+	/* the stage's inputs as the seeding stage leaves them: read offsets, the dense interval layout (cap entries a read), seeds with score = len */
+	const size_t ts = (size_t)tot + 1;
+	std::vector<int64_t> h_off((size_t)n_reads + 1, 0); std::vector<int32_t> h_ni((size_t)n_reads), h_ns((size_t)n_reads);
+	std::vector<ssg_intv_t> h_iv((size_t)n_reads * cap); std::vector<ssg_seed_t> h_sd(ts);
+	memset(h_iv.data(), 0, h_iv.size() * sizeof(ssg_intv_t));
+	for (int r = 0; r < n_reads; ++r) {
+		h_off[r + 1] = h_off[r] + read_len[r]; h_ni[r] = (int32_t)(intv_off[r + 1] - intv_off[r]); h_ns[r] = (int32_t)(seed_off[r + 1] - seed_off[r]);
+		for (int k = 0; k < h_ni[r]; ++k) h_iv[(size_t)r * cap + k] = intv[intv_off[r] + k];
+	}
+	for (int64_t k = 0; k < tot; ++k) { h_sd[k] = seeds[k]; h_sd[k].score = seeds[k].len; h_sd[k].next = -1; }
+	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
+	ix.l_pac = l_pac; ix.n_ctg = n_ctg;
+	dbuf<int64_t> d_off((size_t)n_reads + 1), d_soff((size_t)n_reads + 1); dbuf<ssg_intv_t> d_intv((size_t)n_reads * cap); dbuf<int32_t> d_nintv(n_reads), d_nseed(n_reads);
+	dbuf<ssg_seed_t> d_seeds(ts); dbuf<int32_t> d_srid(ts), d_order(ts), d_kept(ts), d_cseeds(ts), d_nchain(n_reads), d_work(n_reads); dbuf<ssg_chain_t> d_chains(ts); dbuf<unsigned int> d_queue(8);
+	CHKA(d_off); CHKA(d_soff); CHKA(d_intv); CHKA(d_nintv); CHKA(d_nseed); CHKA(d_seeds); CHKA(d_srid); CHKA(d_order); CHKA(d_kept); CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_work); CHKA(d_chains); CHKA(d_queue);
+	CHK(d_off.up(h_off.data(), (size_t)n_reads + 1)); CHK(d_soff.up(seed_off, (size_t)n_reads + 1)); CHK(d_intv.up(h_iv.data(), h_iv.size())); CHK(d_nintv.up(h_ni.data(), n_reads));
+	CHK(d_nseed.up(h_ns.data(), n_reads)); CHK(d_seeds.up(h_sd.data(), (size_t)tot)); CHK(d_srid.up(rids, (size_t)tot)); CHK(d_nchain.zero());
+	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());   /* (as run_align1 makes the work order) */
+	CHK(run_chain(ix, opt, n_reads, d_off.p, max_len, d_intv.p, d_nintv.p, cap, d_nseed.p, d_soff.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p,
+	              d_work.p, d_queue.p, (uint64_t*)0, form));
+	CHK(rt_sync());
+	std::vector<int32_t> h_nc((size_t)n_reads), h_ord(ts), h_cs(ts); std::vector<ssg_chain_t> h_ch(ts);
+	CHK(d_nchain.down(h_nc.data(), n_reads)); CHK(d_order.down(h_ord.data(), (size_t)tot)); CHK(d_cseeds.down(h_cs.data(), (size_t)tot)); CHK(d_chains.down(h_ch.data(), (size_t)tot));
+	/* the survivors in the stage's order; what the kernels left is checked against the slices before it is followed */
+	int64_t n_out = 0, n_sd = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (h_nc[r] < 0 || h_nc[r] > h_ns[r]) { ssg_err_msg = "ssg_dbg_chain: a read's chain count is outside its slice"; return SSG_EOVERFLOW; }
+		for (int i = 0; i < h_nc[r]; ++i) {
+			const int32_t id = h_ord[seed_off[r] + i];
+			if (id < 0 || id >= h_ns[r]) { ssg_err_msg = "ssg_dbg_chain: a chain id is outside its read's slice"; return SSG_EOVERFLOW; }
+			const ssg_chain_t &c = h_ch[seed_off[r] + id];
+			if (c.n < 1 || c.first_seed < seed_off[r] || (int64_t)c.first_seed + c.n > seed_off[r + 1]) { ssg_err_msg = "ssg_dbg_chain: a chain's seed list is outside its read's slice"; return SSG_EOVERFLOW; }
+			++n_out; n_sd += c.n;
+		}
+	}
+	ssg_chain_t *oc = (ssg_chain_t*)calloc((size_t)n_out + 1, sizeof(ssg_chain_t)); int32_t *os = (int32_t*)calloc((size_t)n_sd + 1, sizeof(int32_t));
+	if (!oc || !os) { free(oc); free(os); ssg_err_msg = "host allocation failed: chains"; return SSG_ENOMEM; }
+	int64_t k = 0, q = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		chain_off[r] = k;
+		for (int i = 0; i < h_nc[r]; ++i) {
+			const ssg_chain_t &c = h_ch[seed_off[r] + h_ord[seed_off[r] + i]];
+			ssg_chain_t &o = oc[k++];
+			o.pos = c.pos; o.rid = c.rid; o.n = c.n; o.w = c.w; o.kept = c.kept; o.frac_rep = c.frac_rep; o.first_seed = (int32_t)q;
+			for (int j = 0; j < c.n; ++j) os[q++] = (int32_t)(h_cs[c.first_seed + j] - seed_off[r]);
+		}
+	}
+	chain_off[n_reads] = k;
+	*chains = oc; *chain_seeds = os;
+	return SSG_OK;
 }
 
 int ssg_align1_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,

@@ -88,6 +88,31 @@ class Oracle:
         assert n <= cap
         return out[:n]
 
+    def opt_chain2(self, opt, w, min_seed_len, max_occ):
+        """the remaining knobs of the chaining stage on an option block of opt_chain()"""
+        self.l.orc_api_opt_chain2(opt, C.c_int(w), C.c_int(min_seed_len), C.c_int(max_occ))
+        return opt
+
+    def chain(self, l_pac, read_len, seed_off, seeds4, intv_off, intv, opt=None, kbtree=1):
+        """the chaining stage on given seeds ((rbeg, qbeg, len, rid) rows) and intervals (orc_api_chain): (chain_off, rows (pos, rid, n, w, kept, frac_rep bits, offset of
+        the seed indices) of the chains as mem_chain_flt leaves them after its sort -- kept = 0 included --, seed indices counted from the read's first seed)"""
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.int64)
+        intv_off = np.ascontiguousarray(intv_off, dtype=np.int64)
+        seeds4 = np.ascontiguousarray(seeds4, dtype=np.int64).reshape(-1, 4)
+        intv = np.ascontiguousarray(intv, dtype=INTV_DT)
+        n, tot = len(read_len), int(seed_off[-1])
+        assert len(seed_off) == n + 1 and len(intv_off) == n + 1 and len(seeds4) >= tot and len(intv) >= intv_off[-1]
+        chain_off = np.zeros(n + 1, dtype=np.int64)
+        chains = np.zeros((tot + 1, 7), dtype=np.int64)
+        cseeds = np.zeros(tot + 1, dtype=np.int32)
+        self.l.orc_api_set_chain_container(C.c_int(kbtree))
+        self.l.orc_api_chain(opt or self.opt, C.c_int64(l_pac), C.c_int(n), _ptr(read_len), _ptr(seed_off), _ptr(seeds4), _ptr(intv_off), _ptr(intv),
+                             _ptr(chain_off), _ptr(chains), _ptr(cseeds))
+        self.l.orc_api_set_chain_container(C.c_int(-1))   # back to "not chosen": the next call on this thread chooses as before
+        nc =int(chain_off[n])
+        return chain_off, chains[:nc], cseeds[:int(chains[:nc, 2].sum())]
+
     def align1_batch(self, idx, seq, off, opt=None):
         n = len(off) - 1
         reg_off = np.zeros(n + 1, dtype=np.int64)
