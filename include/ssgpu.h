@@ -28,6 +28,7 @@ extern "C" {
 #define SSG_EINVAL   (-22)
 #define SSG_EIO      (-5)
 #define SSG_EOVERFLOW (-75) /* an on-device capacity was exceeded; nothing was silently dropped */
+#define SSG_EALIGN   (-71)  /* ssg_recs_scan: a BGZF block that does not start at a record -- a property of the file, callers fall back on it */
 #define SSG_EHIP     (-1000)
 
 const char *ssg_version(void);
@@ -393,6 +394,37 @@ int ssg_recs_order(ssg_recs_t *r, const uint64_t *loc, const uint64_t *cum, int6
 int ssg_recs_gather(ssg_recs_t *r, uint64_t v0, uint64_t v1, uint8_t *out);
 int ssg_bgzf_compress_recs(ssg_recs_t *r, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc);
 void ssg_recs_free(ssg_recs_t *r);
+/* ---- BAM read into the store: members inflated there, their records found there (row f1; the reader in the reference: bgzf_read_block and bam_read1, htslib) ----
+ * ssg_recs_append_bgzf: ssg_bgzf_inflate whose output becomes a new chunk of the store instead of a host buffer: the same walk of the headers on the host, the
+ *   same SSG_EINVAL cases, the same status[] and SSG_EIO, out_off[] the prefix sum of the ISIZEs.  The chunk holds out_off[n_blocks] bytes (plus the store's
+ *   16 bytes of slack) and is never copied to the host; *chunk_id receives its id.  The capacity rule is ssg_recs_append's (SSG_ENOMEM, store unchanged and
+ *   usable).  A bad member (SSG_EINVAL, SSG_EIO) leaves the store as it was: no chunk, the capacity unchanged.  n_blocks <= 0: out_off[0] = 0, no chunk.
+ *   Refused (SSG_EINVAL) while an order is declared, as ssg_recs_append.
+ * ssg_recs_scan: the records of a chunk.  The chunk's bytes first .. hint[n_hints] are one stream of BAM records (block_size word, block_size bytes, ...).
+ *   hint[0 .. n_hints] (n_hints + 1 values, ascending, hint[n_hints] <= the chunk's length, first <= hint[n_hints]) are offsets at which a record is expected to
+ *   begin -- the members' out_off[]: every mainstream writer starts a BGZF block at a record (htslib's bgzf_flush_try) -- and the intervals between them are
+ *   walked side by side on the device; what lies before `first' (a header's bytes) is skipped.  Per record, in stream order: loc[i] = chunk_id << 40 | offset of
+ *   its block_size word (the store's encoding); key[i] = the coordinate key of `sambamba sort' (bam1_lt: tid << 32 | (pos + 1) << 1 | reverse, tid = -1 as it
+ *   comes); ent[i] = tid, pos, end (bam_endpos: pos + 1 for an unmapped record or one without CIGAR, else pos + the lengths of its M, D, N, = and X
+ *   operations), flag, len = 4 + block_size, pad = 0.  loc / key / ent: host arrays of `cap' elements.  Returns
+ *     0              *n_rec records returned;
+ *     SSG_EOVERFLOW  cap < *n_rec: *n_rec is set, nothing is written to loc / key / ent (length of the stream / 36 always suffices as cap);
+ *     SSG_EIO        a malformed stream, its offset in ssg_last_error(): a block_size below 32, a record that runs past hint[n_hints], or a record whose
+ *                    l_qname + 4 n_cigar exceeds block_size - 32;
+ *     SSG_EALIGN     not record-aligned at hint b (b and the offsets in ssg_last_error()): the walk that entered at hint[b] passed hint[b+1] without landing
+ *                    on it.  A property of the file (a writer that splits records over blocks), not an error of the call: callers fall back on it.
+ *   Nothing is valid in loc / key / ent unless 0 is returned; the store is unchanged by every outcome.  SSG_EINVAL for a chunk that does not exist or is released,
+ *   or hints that do not ascend inside the chunk.
+ * ssg_recs_reopen: drops a declared order: the store takes appends again, and a later ssg_recs_order declares a new stream.
+ * ssg_recs_release: frees a chunk's device memory and returns its bytes to the capacity.  The id stays taken (later chunks keep theirs); ssg_recs_order refuses
+ *   a location in a released chunk with SSG_EINVAL.  Refused (SSG_EINVAL) while an order is declared: ssg_recs_reopen first. */
+typedef struct { int32_t tid, pos, end; uint32_t flag, len, pad; } ssg_bam_ent_t;
+int ssg_recs_append_bgzf(ssg_recs_t *r, const uint8_t *members, const uint64_t *moff, long n_blocks, uint32_t *chunk_id, uint64_t *out_off, int32_t *status);
+int ssg_recs_scan(ssg_recs_t *r, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t cap, uint64_t *n_rec, uint64_t *loc, uint64_t *key, ssg_bam_ent_t *ent);
+int ssg_recs_reopen(ssg_recs_t *r);
+int ssg_recs_release(ssg_recs_t *r, uint32_t chunk_id);
+/* bytes of device memory that are free / that the calling thread's device has: what a caller sizes a store from */
+int ssg_device_memory(uint64_t *free_bytes, uint64_t *total_bytes);
 void *ssg_host_alloc(size_t n);
 void ssg_host_free(void *p);
 

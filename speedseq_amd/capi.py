@@ -537,6 +537,64 @@ def bgzf_compress_recs(lib, recs, cut, want_crc=True, out_cap=None):
     return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
 
 
+BAM_ENT_DT = np.dtype([("tid", "i4"), ("pos", "i4"), ("end", "i4"), ("flag", "u4"), ("len", "u4"), ("pad", "u4")])
+SSG_EALIGN = -71
+
+
+def recs_append_bgzf(lib, recs, members, moff, want_status=True):
+    """ssg_recs_append_bgzf: the BGZF members members[moff[b] .. moff[b+1]) inflated into a new chunk of the store.  Returns (rc, chunk_id, out_off, status):
+    rc 0 or SSG_EIO (-5: a bad member, status[] says which; no chunk was added and chunk_id is None); every other return code raises."""
+    members = _bytes_u8(members)
+    moff = np.ascontiguousarray(moff, dtype=np.uint64)
+    n = len(moff) - 1
+    off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32) if want_status else None
+    cid = C.c_uint32(0xffffffff)
+    rc = lib.l.ssg_recs_append_bgzf(recs.h, _ptr(members) if members.size else None, _ptr(moff), C.c_long(n), C.byref(cid), _ptr(off), _ptr(status) if want_status else None)
+    if rc != -5:
+        lib._chk(rc)
+    return rc, (int(cid.value) if rc == 0 and n > 0 else None), off, (status[:max(n, 0)] if want_status else None)
+
+
+def recs_scan(lib, recs, chunk_id, hint, first=0, cap=None):
+    """ssg_recs_scan: the records of a chunk, found on the device.  hint: n_hints + 1 ascending offsets (the members' out_off).  Returns (rc, n_rec, loc, key, ent):
+    rc 0, or SSG_EOVERFLOW (-75), SSG_EIO (-5), SSG_EALIGN (-71) with the arrays as the call left them (cap elements, prefilled with 0xAB bytes); every other
+    return code raises.  ent has dtype BAM_ENT_DT."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_hints = len(hint) - 1
+    if cap is None:
+        cap = int(hint[-1]) // 36 if n_hints >= 0 and len(hint) else 0
+    loc = np.full(cap + 1, 0xABABABABABABABAB, dtype=np.uint64)
+    key = np.full(cap + 1, 0xABABABABABABABAB, dtype=np.uint64)
+    ent = np.frombuffer(np.full((cap + 1) * BAM_ENT_DT.itemsize, 0xAB, dtype=np.uint8).tobytes(), dtype=BAM_ENT_DT).copy()
+    n_rec = C.c_uint64(0)
+    rc = lib.l.ssg_recs_scan(recs.h, C.c_uint32(chunk_id), _ptr(hint), C.c_int64(n_hints), C.c_uint64(first), C.c_uint64(cap), C.byref(n_rec), _ptr(loc), _ptr(key), _ptr(ent))
+    if rc not in (0, -5, -75, SSG_EALIGN):
+        lib._chk(rc)
+    n = int(n_rec.value)
+    if rc == 0:
+        assert int(loc[cap]) == 0xABABABABABABABAB and int(key[cap]) == 0xABABABABABABABAB and ent[cap:].tobytes() == b"\xab" * BAM_ENT_DT.itemsize   # nothing behind cap
+        return rc, n, loc[:n], key[:n], ent[:n]
+    return rc, n, loc, key, ent
+
+
+def device_memory(lib):
+    """ssg_device_memory: (free, total) bytes of the calling thread's device."""
+    f, t = C.c_uint64(0), C.c_uint64(0)
+    lib._chk(lib.l.ssg_device_memory(C.byref(f), C.byref(t)))
+    return int(f.value), int(t.value)
+
+
+def recs_reopen(lib, recs):
+    """ssg_recs_reopen: drops a declared order; the store takes appends again."""
+    lib._chk(lib.l.ssg_recs_reopen(recs.h))
+
+
+def recs_release(lib, recs, chunk_id):
+    """ssg_recs_release: frees a chunk's device memory and returns its bytes to the capacity; the id stays taken."""
+    lib._chk(lib.l.ssg_recs_release(recs.h, C.c_uint32(chunk_id)))
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

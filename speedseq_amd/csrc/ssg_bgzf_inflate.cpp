@@ -17,14 +17,12 @@ static inline uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] <
 
 extern "C" {
 
-int ssg_bgzf_inflate(const uint8_t *members, const uint64_t *moff, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *status)
+/* every header (bgzf.c check_header: a gzip member with FEXTRA and a BC subfield of two bytes), the stream's bounds, ISIZE: rng[2b], rng[2b + 1] = the deflate
+ * stream of member b in members[], out_off[] = the prefix sum of the ISIZEs.  SSG_EINVAL with `who' and the member in ssg_last_error() */
+int ssg_bgzf_walk_members(const char *who, const uint8_t *members, const uint64_t *moff, long n_blocks, uint64_t *rng, uint64_t *out_off)
 {
-	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
 	out_off[0] = 0;
-	if (n_blocks <= 0) return 0;
-	/* every header (bgzf.c check_header: a gzip member with FEXTRA and a BC subfield of two bytes), the stream's bounds, ISIZE */
-	std::vector<uint64_t> rng((size_t)n_blocks * 2);
-	auto refuse = [&](long b, const char *why) { ssg_err_msg = "ssg_bgzf_inflate: member " + std::to_string(b) + ": " + why; return SSG_EINVAL; };
+	auto refuse = [&](long b, const char *why) { ssg_err_msg = std::string(who) + ": member " + std::to_string(b) + ": " + why; return SSG_EINVAL; };
 	for (long b = 0; b < n_blocks; ++b) {
 		if (moff[b + 1] < moff[b] || moff[b + 1] - moff[b] < 28) return refuse(b, "a span shorter than 28 bytes");
 		const uint8_t *h = members + moff[b]; const uint64_t span = moff[b + 1] - moff[b];
@@ -40,6 +38,25 @@ int ssg_bgzf_inflate(const uint8_t *members, const uint64_t *moff, long n_blocks
 		rng[(size_t)b * 2] = moff[b] + 12 + xlen; rng[(size_t)b * 2 + 1] = moff[b + 1] - 8;
 		out_off[b + 1] = out_off[b] + isize;
 	}
+	return 0;
+}
+
+/* nb members (at most 4096 a call, as ssg_bgzf_compress: at most 256 MB in, 256 MB out) inflated and checksummed, queued on the calling thread's stream; device
+ * buffers: member k's stream d_in[d_rng[2k] .. d_rng[2k + 1]) to d_out[d_ooff[k] .. d_ooff[k + 1]), d_st[k] as the kernel leaves it, d_crc[k] the output's CRC-32 */
+int ssg_bgzf_inflate_dev(const uint8_t *d_in, const uint64_t *d_rng, const uint64_t *d_ooff, long nb, uint8_t *d_out, int32_t *d_st, uint32_t *d_crc)
+{
+	const long grid = std::min<long>((nb + 3) / 4, 4096);   /* four waves per workgroup, a wave per member */
+	SSG_LAUNCH(ssg_k_bgzf_inflate, grid, 256, 0, d_in, d_rng, d_ooff, nb, d_out, d_st);
+	return ssg_crc32_ranges_dev(d_out, d_ooff, nb, d_crc);   /* the output is in HBM: its checksum is one more read of it */
+}
+
+int ssg_bgzf_inflate(const uint8_t *members, const uint64_t *moff, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *status)
+{
+	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
+	out_off[0] = 0;
+	if (n_blocks <= 0) return 0;
+	std::vector<uint64_t> rng((size_t)n_blocks * 2);
+	CHK(ssg_bgzf_walk_members("ssg_bgzf_inflate", members, moff, n_blocks, rng.data(), out_off));
 	if (out_off[n_blocks] > out_cap) { ssg_err_msg = "ssg_bgzf_inflate: output buffer too small"; return SSG_EOVERFLOW; }
 	const long BB = 4096;   /* members per device call, as ssg_bgzf_compress: at most 256 MB in, 256 MB out */
 	const long nbmax = std::min(BB, n_blocks);
@@ -57,9 +74,7 @@ int ssg_bgzf_inflate(const uint8_t *members, const uint64_t *moff, long n_blocks
 		for (long k = 0; k < 2 * nb; ++k) rel[(size_t)k] = rng[(size_t)(2 * b0 + k)] - ibase;
 		for (long k = 0; k <= nb; ++k) orel[(size_t)k] = out_off[b0 + k] - obase;
 		CHK(rt_h2d(d_in.p, members + ibase, ibytes)); CHK(d_rng.up(rel.data(), (size_t)nb * 2)); CHK(d_ooff.up(orel.data(), (size_t)nb + 1));
-		const long grid = std::min<long>((nb + 3) / 4, 4096);   /* four waves per workgroup, a wave per member */
-		SSG_LAUNCH(ssg_k_bgzf_inflate, grid, 256, 0, (const uint8_t*)d_in.p, (const uint64_t*)d_rng.p, (const uint64_t*)d_ooff.p, nb, d_out.p, d_st.p);
-		CHK(ssg_crc32_ranges_dev(d_out.p, d_ooff.p, nb, d_crc.p));   /* the output is in HBM: its checksum is one more read of it */
+		CHK(ssg_bgzf_inflate_dev(d_in.p, d_rng.p, d_ooff.p, nb, d_out.p, d_st.p, d_crc.p));
 		CHK(rt_sync());
 		CHK(d_st.down(st.data(), (size_t)nb)); CHK(d_crc.down(crc.data(), (size_t)nb));
 		CHK(rt_d2h(out + obase, d_out.p, obytes));

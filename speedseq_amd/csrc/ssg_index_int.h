@@ -38,6 +38,11 @@ extern "C" int ssg_sa_verify(const ssg_index *ix, int new_intv, const uint64_t *
 /* ssg_bgzf_frame.cpp: the launchers of the CRC-32 and framing kernels (k_bgzf_frame.h), queued on the calling thread's stream; device buffers */
 extern "C" int ssg_crc32_ranges_dev(const uint8_t *d_data, const uint64_t *d_cut, long n, uint32_t *d_crc);
 extern "C" int ssg_bgzf_frame_dev(const uint8_t *d_tmp, uint32_t tmp_stride, const uint64_t *d_cut, const uint64_t *d_moff, const uint32_t *d_crc, long n_blocks, uint8_t *d_dense);
+/* ssg_bgzf_inflate.cpp: the walk of the members' headers on the host (rng[2b], rng[2b + 1]: member b's deflate stream in members[]; out_off[]: the prefix sum of
+ * the ISIZEs; SSG_EINVAL with `who' and the member in ssg_last_error()), and the launcher of the inflate and CRC-32 kernels for at most 4096 members, queued on
+ * the calling thread's stream; device buffers */
+extern "C" int ssg_bgzf_walk_members(const char *who, const uint8_t *members, const uint64_t *moff, long n_blocks, uint64_t *rng, uint64_t *out_off);
+extern "C" int ssg_bgzf_inflate_dev(const uint8_t *d_in, const uint64_t *d_rng, const uint64_t *d_ooff, long nb, uint8_t *d_out, int32_t *d_st, uint32_t *d_crc);
 /* ssg_rec_gather.cpp: the launcher of the gather kernel (k_rec_gather.h), queued on the calling thread's stream: bytes v0 .. v1 of the store's sorted stream to
  * d_out[0 .. v1 - v0), a device buffer with room for v1 - v0 bytes rounded up to 16 */
 struct ssg_recs;

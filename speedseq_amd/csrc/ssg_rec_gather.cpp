@@ -1,6 +1,6 @@
 /*
  * ssg_rec_gather.cpp -- the records of `sambamba sort`'s input kept in HBM in the chunks they arrived in, and the sorted stream gathered from them on the
- * device (k_rec_gather.h): ssg_recs_create / append / order / gather / free, and the launcher ssg_bgzf_compress_recs
+ * device (k_rec_gather.h): ssg_recs_create / append / order / gather / reopen / release / free, and the launcher ssg_bgzf_compress_recs
  * (ssg_bgzf.cpp) puts in front of the deflate kernel.  A translation unit of its own: a kernel added to ssg_bgzf.cpp or ssg_bgzf_frame.cpp would be
  * compiled next to kernels whose machine code is pinned (tools/isa_pin.py).
  */
@@ -10,31 +10,9 @@
 #include "k_rec_gather.h"
 #include "../../include/ssgpu.h"
 #include "ssg_index_int.h"
+#include "ssg_recs_int.h"
 
 SSG_ABI_FP_DEFINE(rec_gather)
-
-/* the device mirror of the sort's record store (rec_store_t, sambamba_main.cpp): a chunk is a device allocation of its own, outside the arena -- gigabytes
- * that go back to the driver with the store -- with 16 bytes of slack behind it, so that a 16-byte load that starts inside a record stays inside */
-struct ssg_recs {
-	int dev; uint64_t cap, bytes;
-	std::vector<uint8_t*> d_chunk; std::vector<uint64_t> len;
-	/* what ssg_recs_order leaves for the kernel */
-	bool ordered; int64_t n; uint64_t total;
-	uint8_t **d_ptr; uint64_t *d_loc, *d_cum;
-	ssg_recs() : dev(0), cap(0), bytes(0), ordered(false), n(0), total(0), d_ptr(0), d_loc(0), d_cum(0) {}
-};
-static void recs_drop_order(ssg_recs *r)
-{
-	rt_free_raw(r->d_ptr); rt_free_raw(r->d_loc); rt_free_raw(r->d_cum);
-	r->d_ptr = 0; r->d_loc = r->d_cum = 0; r->ordered = false; r->n = 0; r->total = 0;
-}
-static int recs_usable(const ssg_recs *r, const char *who)
-{
-	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
-	if (!r) { ssg_err_msg = std::string(who) + ": no record store"; return SSG_EINVAL; }
-	if (r->dev != ssg_cur_dev) { ssg_err_msg = std::string(who) + ": the record store lives on device " + std::to_string(r->dev) + ", the calling thread drives device " + std::to_string(ssg_cur_dev); return SSG_EINVAL; }
-	return 0;
-}
 
 extern "C" {
 
@@ -80,6 +58,7 @@ int ssg_recs_order(ssg_recs_t *r, const uint64_t *loc, const uint64_t *cum, int6
 	for (int64_t i = 0; i < n; ++i) {
 		if (cum[i + 1] < cum[i]) { ssg_err_msg = "ssg_recs_order: cum[] decreases at record " + std::to_string(i); return SSG_EINVAL; }
 		const uint64_t c = loc[i] >> 40, o = loc[i] & RG_OFF_MASK, l = cum[i + 1] - cum[i];
+		if (c < r->d_chunk.size() && !r->d_chunk[(size_t)c]) { ssg_err_msg = "ssg_recs_order: record " + std::to_string(i) + " names chunk " + std::to_string(c) + ", which ssg_recs_release has released"; return SSG_EINVAL; }
 		if (c >= r->d_chunk.size()) { ssg_err_msg = "ssg_recs_order: record " + std::to_string(i) + " names chunk " + std::to_string(c) + ", the store has " + std::to_string(r->d_chunk.size()); return SSG_EINVAL; }
 		if (o > r->len[(size_t)c] || l > r->len[(size_t)c] - o) { ssg_err_msg = "ssg_recs_order: record " + std::to_string(i) + " runs past the end of chunk " + std::to_string(c); return SSG_EINVAL; }
 	}
@@ -94,6 +73,24 @@ int ssg_recs_order(ssg_recs_t *r, const uint64_t *loc, const uint64_t *cum, int6
 	if (!rc) rc = rt_h2d(r->d_cum, cum, ((size_t)n + 1) * 8);
 	if (rc) { recs_drop_order(r); return rc; }
 	r->n = n; r->total = cum[n]; r->ordered = true;
+	return 0;
+}
+
+int ssg_recs_reopen(ssg_recs_t *r)
+{
+	CHK(recs_usable(r, "ssg_recs_reopen"));
+	recs_drop_order(r);
+	return 0;
+}
+
+int ssg_recs_release(ssg_recs_t *r, uint32_t chunk_id)
+{
+	CHK(recs_usable(r, "ssg_recs_release"));
+	if (r->ordered) { ssg_err_msg = "ssg_recs_release: an order is declared (the gather may read the chunk): ssg_recs_reopen first"; return SSG_EINVAL; }
+	if (chunk_id >= r->d_chunk.size() || !r->d_chunk[chunk_id]) { ssg_err_msg = "ssg_recs_release: chunk " + std::to_string(chunk_id) + " does not exist or is released already"; return SSG_EINVAL; }
+	CHK(rt_sync());   /* (nothing queued on this thread's stream reads it any more) */
+	rt_free_raw(r->d_chunk[chunk_id]);
+	r->d_chunk[chunk_id] = 0; r->bytes -= r->len[chunk_id]; r->len[chunk_id] = 0;
 	return 0;
 }
 

@@ -1,0 +1,35 @@
+/*
+ * ssg_recs_int.h -- the record store shared by the translation units that work on it (ssg_rec_gather.cpp: create / append / order / gather / reopen /
+ * release / free; ssg_bam_scan.cpp: BGZF members inflated into a chunk, the records of a chunk found on the device).
+ */
+#ifndef SSG_RECS_INT_H
+#define SSG_RECS_INT_H
+#include <string>
+#include <vector>
+#include "ssg_rt.h"
+#include "../../include/ssgpu.h"
+
+/* the device mirror of the sort's record store (rec_store_t, sambamba_main.cpp): a chunk is a device allocation of its own, outside the arena -- gigabytes
+ * that go back to the driver with the store -- with 16 bytes of slack behind it, so that a 16-byte load that starts inside a record stays inside.  A released
+ * chunk (ssg_recs_release) keeps its id: d_chunk[id] = NULL, len[id] = 0 */
+struct ssg_recs {
+	int dev; uint64_t cap, bytes;
+	std::vector<uint8_t*> d_chunk; std::vector<uint64_t> len;
+	/* what ssg_recs_order leaves for the kernel */
+	bool ordered; int64_t n; uint64_t total;
+	uint8_t **d_ptr; uint64_t *d_loc, *d_cum;
+	ssg_recs() : dev(0), cap(0), bytes(0), ordered(false), n(0), total(0), d_ptr(0), d_loc(0), d_cum(0) {}
+};
+static inline void recs_drop_order(ssg_recs *r)
+{
+	rt_free_raw(r->d_ptr); rt_free_raw(r->d_loc); rt_free_raw(r->d_cum);
+	r->d_ptr = 0; r->d_loc = r->d_cum = 0; r->ordered = false; r->n = 0; r->total = 0;
+}
+static inline int recs_usable(const ssg_recs *r, const char *who)
+{
+	if (rt_device_count() < 1) { ssg_err_msg = "no HIP device visible: libssgpu has no CPU path"; return SSG_ENODEV; }
+	if (!r) { ssg_err_msg = std::string(who) + ": no record store"; return SSG_EINVAL; }
+	if (r->dev != ssg_cur_dev) { ssg_err_msg = std::string(who) + ": the record store lives on device " + std::to_string(r->dev) + ", the calling thread drives device " + std::to_string(ssg_cur_dev); return SSG_EINVAL; }
+	return 0;
+}
+#endif

@@ -1247,6 +1247,292 @@ static int cmd_flagstat(int argc, char **argv)
 	return 0;
 }
 
+/* ---------------- merge and index on device-resident records (SSG_MERGE_DEVICE=1, SSG_INDEX_DEVICE=1) ----------------
+ * The input is read as raw BGZF members, inflated into the record store (ssg_recs_append_bgzf) and walked there (ssg_recs_scan): of every record 40 bytes come
+ * back -- its location in the store, its sort key, the fields of its index entry -- and the payload stays in HBM.  `index' needs no more; `merge' declares the
+ * merged order of what it has loaded (ssg_recs_order) and has the device gather, deflate and frame the output blocks (ssg_bgzf_compress_recs).
+ * Both need a file whose blocks start at records (htslib's bgzf_flush_try, sambamba, this repository's writers); for any other they fall back on the host loops. */
+static bool env_is_1(const char *name) { const char *e = getenv(name); return e && !strcmp(e, "1"); }
+/* SSG_PROF=1: the device time of every kernel of the command's device path (HIP events around each launch), one line each at the end */
+static void dev_prof_begin() { if (getenv("SSG_PROF")) { ssg_prof_reset(); ssg_prof_enable(1); } }
+static void dev_prof_report(const char *cmd)
+{
+	if (!getenv("SSG_PROF")) return;
+	const char *nm[64]; double ms[64]; long cnt[64];
+	const int n = std::min(ssg_prof_get(64, nm, ms, cnt), 64);
+	for (int i = 0; i < n; ++i) fprintf(stderr, "[sambamba] %s: kernel %-24s %9.1f ms in %ld launches\n", cmd, nm[i], ms[i], cnt[i]);
+}
+
+/* whole BGZF members of a file, read at offsets of its own (pread): a bgzf_in_t on the same descriptor is not disturbed */
+struct raw_members_t {
+	int fd; const char *name; uint64_t fpos, addr; bool eof; std::vector<uint8_t> buf; size_t used;   /* buf[0] lies at file offset addr; buf[0 .. used) are the members of the last next() */
+	std::vector<uint64_t> moff; uint64_t inflated; bool at_end;
+	raw_members_t() : fd(-1), name(""), fpos(0), addr(0), eof(false), used(0), inflated(0), at_end(false) {}
+	void start(int fd_, const char *name_, uint64_t file_off) { fd = fd_; name = name_; fpos = addr = file_off; eof = false; buf.clear(); used = 0; }
+	bool fill(size_t need)
+	{
+		const size_t STEP = (size_t)8 << 20;
+		while (buf.size() < need && !eof) {
+			const size_t old = buf.size(); buf.resize(old + STEP);
+			const ssize_t r = pread(fd, buf.data() + old, STEP, (off_t)fpos);
+			if (r < 0) { buf.resize(old); if (errno == EINTR) continue; die(std::string("cannot read ") + name + ": " + strerror(errno)); }
+			buf.resize(old + (size_t)r); fpos += (uint64_t)r;
+			if (r == 0) eof = true;
+		}
+		return buf.size() >= need;
+	}
+	/* the next members: as many as inflate to at most `window' bytes -- but at least up to the first that has any -- and at most max_members; false at the end of the file */
+	bool next(uint64_t window, size_t max_members)
+	{
+		if (used) { buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)used); addr += used; used = 0; }
+		moff.assign(1, 0); inflated = 0;
+		size_t pos = 0;
+		while (moff.size() - 1 < max_members) {
+			if (!fill(pos + 18)) { if (buf.size() > pos) die(std::string("truncated BGZF header in ") + name); break; }
+			if (buf[pos] != 0x1f || buf[pos + 1] != 0x8b || buf[pos + 2] != 8 || !(buf[pos + 3] & 4)) die(std::string("not a BGZF block in ") + name);
+			const size_t xlen = buf[pos + 10] | (size_t)buf[pos + 11] << 8;
+			if (!fill(pos + 12 + xlen)) die(std::string("truncated BGZF header in ") + name);
+			size_t bsize = 0;
+			for (size_t o = 12; o + 4 <= 12 + xlen; ) { const uint8_t *h = buf.data() + pos; const size_t sl = h[o + 2] | (size_t)h[o + 3] << 8; if (h[o] == 'B' && h[o + 1] == 'C' && sl == 2 && o + 6 <= 12 + xlen) bsize = (size_t)(h[o + 4] | (size_t)h[o + 5] << 8) + 1; o += 4 + sl; }
+			if (bsize < 28 || !fill(pos + bsize)) die(std::string("truncated BGZF block in ") + name);
+			uint32_t isz; memcpy(&isz, buf.data() + pos + bsize - 4, 4);
+			if (inflated > 0 && inflated + isz > window) break;
+			pos += bsize; moff.push_back(pos); inflated += isz;
+		}
+		used = pos;
+		at_end = !fill(pos + 1);   /* (nothing behind these members: the caller need not come back to learn it) */
+		return moff.size() > 1;
+	}
+	size_t n() const { return moff.size() - 1; }
+	uint64_t end_addr() const { return addr + used; }
+};
+
+struct recs_holder_t { ssg_recs_t *r; recs_holder_t() : r(0) {} ~recs_holder_t() { if (r) ssg_recs_free(r); } };
+/* what the device read path needs before it starts: a device, and an input that can be read at offsets */
+static bool dev_read_ready(int fd, std::string &why)
+{
+	if (ssg_device_count() < 1) { why = "no device"; return false; }
+	struct stat sb;
+	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { why = "an input is not a regular file"; return false; }
+	return true;
+}
+static const uint64_t LOC_OFF_MASK = ((uint64_t)1 << 40) - 1;
+
+/* one load: the reader's members into a new chunk, its records appended to loc / key / ent.  0; 1 with `why' (the caller falls back, or ends); bad data ends the program as the host readers do */
+static int dev_load(ssg_recs_t *recs, raw_members_t &rd, uint64_t first, const char *cmd, uint32_t &cid, std::vector<uint64_t> &out_off, uint64_t &n_new,
+                    std::vector<uint64_t> &loc, std::vector<uint64_t> &key, std::vector<ssg_bam_ent_t> &ent, std::string &why)
+{
+	const size_t nm = rd.n();
+	out_off.resize(nm + 1); std::vector<int32_t> status(nm, 0);
+	int rc = ssg_recs_append_bgzf(recs, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
+	if (rc == SSG_EIO) { size_t k = 0; while (k + 1 < nm && !status[k]) ++k; die(std::string(cmd) + ": inflate failed: BGZF member at file offset " + std::to_string(rd.addr + rd.moff[k]) + " of " + rd.name + " (device status " + std::to_string(status[k]) + ")"); }
+	if (rc) { why = ssg_last_error(); return 1; }
+	const size_t have = loc.size(), cap = (size_t)(out_off[nm] / 36) + 1;
+	loc.resize(have + cap); key.resize(have + cap); ent.resize(have + cap);
+	n_new = 0;
+	rc = ssg_recs_scan(recs, cid, out_off.data(), (int64_t)nm, first, cap, &n_new, loc.data() + have, key.data() + have, ent.data() + have);
+	/* (a stream the scan calls malformed goes to the host reader as well: a record that runs past the last of these members may be a truncated file, or one more block
+	 * that does not start at a record -- the host reader tells them apart, and ends the program for the first) */
+	if (rc) { loc.resize(have); key.resize(have); ent.resize(have); why = rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_recs_scan: ")) : std::string(ssg_last_error()); n_new = 0; return 1; }
+	loc.resize(have + n_new); key.resize(have + n_new); ent.resize(have + n_new);
+	return 0;
+}
+
+/* `sambamba index' from the device: true when the .bai is written; false with `why' -- nothing was written, the host loop takes over */
+static bool index_device(const char *in, int fd, int n_ref, uint64_t v0, std::string &why)
+{
+	if (!dev_read_ready(fd, why)) return false;
+	recs_holder_t S;
+	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) { why = ssg_last_error(); return false; }
+	dev_prof_begin();
+	raw_members_t rd; rd.start(fd, in, v0 >> 16);
+	bai_t idx(n_ref, v0);
+	uint64_t first = v0 & 0xffff, n_total = 0; bool have = false; ssg_bam_ent_t p; memset(&p, 0, sizeof(p));
+	std::vector<uint64_t> out_off, loc, key; std::vector<ssg_bam_ent_t> ent;
+	const double t0 = wall(); double t_dev = 0;
+	/* a batch: the 4096 members of one device call of the inflate, at most 256 MB of records */
+	while (rd.next((uint64_t)256 << 20, 4096)) {
+		uint32_t cid = 0; uint64_t n = 0; loc.clear(); key.clear(); ent.clear();
+		const double t1 = wall();
+		if (dev_load(S.r, rd, first, "index", cid, out_off, n, loc, key, ent, why)) return false;
+		t_dev += wall() - t1;
+		first = 0;
+		size_t m = 0;
+		for (uint64_t i = 0; i < n; ++i) {   /* the record's virtual offset: the member that holds its first byte (one without bytes holds none) */
+			const uint64_t o = loc[i] & LOC_OFF_MASK;
+			while (out_off[m + 1] <= o) ++m;
+			const uint64_t v = (rd.addr + rd.moff[m]) << 16 | (o - out_off[m]);
+			if (have && idx.push(p.tid, p.pos, p.end, v, !(p.flag & 4)) < 0) die("index: the file is not coordinate-sorted");
+			p = ent[i]; have = true;
+		}
+		n_total += n;
+		if (ssg_recs_release(S.r, cid)) { why = ssg_last_error(); return false; }
+	}
+	const uint64_t eof_v = rd.end_addr() << 16;
+	if (have && idx.push(p.tid, p.pos, p.end, eof_v, !(p.flag & 4)) < 0) die("index: the file is not coordinate-sorted");
+	idx.finish(eof_v);
+	idx.save((std::string(in) + ".bai").c_str());
+	dev_prof_report("index");
+	if (dbg()) fprintf(stderr, "[sambamba] index: %llu records found on the device in %.2f s (inflate into the store + scan %.2f s)\n", (unsigned long long)n_total, wall() - t0, t_dev);
+	return true;
+}
+
+/* one input of the device merge: its reader, and what is loaded of it and not yet written, in file order */
+struct dm_src_t {
+	raw_members_t rd; bool ended; uint64_t first, n_seen, last_key, pend_bytes;
+	std::vector<uint64_t> loc, key; std::vector<ssg_bam_ent_t> ent;
+	std::deque<std::pair<uint32_t, uint64_t> > chunks;   /* chunk id, its records not yet written */
+	dm_src_t() : ended(false), first(0), n_seen(0), last_key(0), pend_bytes(0) {}
+};
+
+/* `sambamba merge' on the device.  true: the file, its .bai and the note are written.  false with `why': nothing was written, the host merge takes over.
+ * A failure after output began ends the program (the partial file is removed). */
+static bool merge_device(const std::vector<const char*> &files, std::vector<merge_src_t> &src, const bam_hdr_t &h, int level, int threads, std::string &why)
+{
+	const size_t F = src.size();
+	if (level == 0) { why = "-l 0: the device writes no stored blocks"; return false; }
+	for (size_t f = 0; f < F; ++f) if (!dev_read_ready(src[f].fd, why)) return false;
+	recs_holder_t S;
+	if (ssg_set_device(0)) { why = ssg_last_error(); return false; }
+	/* HBM: a quarter of what is free for the records (the rest: what is loaded and not yet written of the inputs that are ahead, the members on their way in, the
+	 * gathered and deflated blocks on their way out), split over the inputs, at most 1 GB each (one load takes at most the 4096 members of one device call of the inflate, 256 MB); SSG_MERGE_WINDOW and SSG_MERGE_POOL (bytes) override */
+	uint64_t hbm_free = 0, hbm_total = 0;
+	if (ssg_device_memory(&hbm_free, &hbm_total)) { why = ssg_last_error(); return false; }
+	uint64_t window = std::min<uint64_t>((uint64_t)1 << 30, std::max<uint64_t>(hbm_free / 4 / F, (uint64_t)1 << 20)), pool = hbm_free / 2;
+	{ const char *e = getenv("SSG_MERGE_WINDOW"); if (e && atoll(e) > 0) window = (uint64_t)atoll(e); }
+	{ const char *e = getenv("SSG_MERGE_POOL"); if (e && atoll(e) > 0) pool = (uint64_t)atoll(e); }
+	if (ssg_recs_create(pool, &S.r)) { why = ssg_last_error(); return false; }
+	dev_prof_begin();
+	std::vector<dm_src_t> in(F);
+	for (size_t f = 0; f < F; ++f) { const uint64_t v = src[f].in->tell(); in[f].rd.start(src[f].fd, files[f + 1], v >> 16); in[f].first = v & 0xffff; }
+	int ofd = -1; uint64_t coff = 0;
+	auto fail = [&](const std::string &m) {   /* after output began */
+		if (ofd >= 0) { close(ofd); unlink(files[0]); }
+		die("merge: " + m + "; the partial output was removed -- SSG_MERGE_DEVICE=0 merges on the host");
+	};
+	std::vector<uint64_t> out_off;
+	/* an input that has less than half a window loaded takes its next members (a round loads every input at the start; an input that is ahead of the others waits) */
+	auto load = [&](bool &ok) {
+		ok = true;
+		for (size_t f = 0; f < F && ok; ++f) {
+			dm_src_t &s = in[f];
+			while (!s.ended && (s.key.empty() || s.pend_bytes < window / 2)) {
+				if (!s.rd.next(window, 4096)) { s.ended = true; break; }
+				uint32_t cid = 0; uint64_t n = 0; const size_t have = s.key.size();
+				if (dev_load(S.r, s.rd, s.first, "merge", cid, out_off, n, s.loc, s.key, s.ent, why)) { ok = false; break; }
+				s.first = 0;
+				for (size_t i = have; i < have + n; ++i) {
+					if (s.n_seen && s.key[i] < s.last_key) { const std::string m = std::string(files[f + 1]) + " is not coordinate-sorted: its record " + std::to_string(s.n_seen) + " (counted from 0) descends"; if (ofd >= 0) fail(m); die("merge: " + m); }
+					s.last_key = s.key[i]; ++s.n_seen; s.pend_bytes += s.ent[i].len;
+				}
+				if (n) s.chunks.push_back(std::make_pair(cid, n));
+				else if (ssg_recs_release(S.r, cid)) { ok = false; why = ssg_last_error(); break; }
+				if (s.rd.at_end) s.ended = true;
+				if (s.key.size() > have) break;   /* (one load a round for an input that got records) */
+			}
+		}
+	};
+	bool ok = true;
+	load(ok);
+	if (!ok) return false;
+	bool any = false; for (const dm_src_t &s : in) any = any || !s.key.empty();
+	/* from here on there is output */
+	ofd = open(files[0], O_WRONLY | O_CREAT | O_TRUNC, 0644); if (ofd < 0) die(std::string("merge: cannot write ") + files[0]);
+	{ bgzf_out_t out(ofd, level, threads); hdr_write(out, h); out.drain(true); }
+	{ const off_t o = lseek(ofd, 0, SEEK_CUR); if (o < 0) fail("the output cannot be sought"); coff = (uint64_t)o; }
+	bai_t idx((int)h.names.size(), (any ? coff : coff + 28) << 16);
+	bool have_p = false; ssg_bam_ent_t p; memset(&p, 0, sizeof(p));
+	const long BATCH = 1024;   /* blocks per device call: 64 MB of records */
+	const uint64_t out_cap = ssg_bgzf_bound((uint64_t)BATCH * BGZF_MAX_PAYLOAD, BATCH);
+	uint8_t *const obuf = (uint8_t*)ssg_host_alloc((size_t)out_cap);
+	if (!obuf) fail("no page-locked memory for the output blocks");
+	std::vector<uint64_t> keys, sloc, cum, cut, boff((size_t)BATCH + 1); std::vector<uint32_t> perm, from; std::vector<ssg_bam_ent_t> sent; std::vector<size_t> take(F), base(F + 1);
+	uint64_t n_written = 0, n_rounds = 0, n_blocks = 0; const double t0 = wall(); double t_load = 0, t_sort = 0, t_write = 0;
+	for (;;) {
+		/* what may be written: everything below the smallest last key of the inputs that have not ended -- what they have not loaded yet sorts behind it */
+		bool all_ended = true; uint64_t Kb = 0; size_t fb = 0;
+		for (size_t f = 0; f < F; ++f) if (!in[f].ended) { const uint64_t K = in[f].key.back(); if (all_ended || K < Kb) { Kb = K; fb = f; } all_ended = false; }
+		uint64_t E = 0;
+		for (size_t f = 0; f < F; ++f) {
+			const std::vector<uint64_t> &k = in[f].key;
+			take[f] = all_ended ? k.size() : (size_t)((f <= fb ? std::upper_bound(k.begin(), k.end(), Kb) : std::lower_bound(k.begin(), k.end(), Kb)) - k.begin());
+			base[f] = (size_t)E; E += take[f];
+		}
+		base[F] = (size_t)E;
+		if (E >= ((uint64_t)1 << 32)) fail("more than 2^32 records in one round: a smaller SSG_MERGE_WINDOW is needed");
+		if (E) {
+			const double t1 = wall();
+			/* the merged order (key, input, position in the input): the inputs' keys one after the other, sorted by a stable sort */
+			keys.resize((size_t)E); perm.resize((size_t)E);
+			for (size_t f = 0; f < F; ++f) std::copy(in[f].key.begin(), in[f].key.begin() + (ptrdiff_t)take[f], keys.begin() + (ptrdiff_t)base[f]);
+			if (ssg_sort_u64_perm(keys.data(), (int64_t)E, perm.data())) fail(ssg_last_error());
+			sloc.resize((size_t)E); sent.resize((size_t)E); cum.resize((size_t)E + 1); cum[0] = 0;
+			for (uint64_t j = 0; j < E; ++j) {
+				const size_t g = perm[(size_t)j], f = (size_t)(std::upper_bound(base.begin(), base.end(), g) - base.begin()) - 1, i = g - base[f];
+				sloc[(size_t)j] = in[f].loc[i]; sent[(size_t)j] = in[f].ent[i]; cum[(size_t)j + 1] = cum[(size_t)j] + in[f].ent[i].len;
+			}
+			/* the blocks, cut as bgzf_out_t::record cuts them: a block closes when the next record would not fit, a record longer than a block is split; a round ends its last block */
+			cut.assign(1, 0); uint64_t open_ = 0;
+			for (uint64_t j = 0; j < E; ++j) {
+				const uint64_t c0 = cum[(size_t)j], c1 = cum[(size_t)j + 1];
+				if (c0 > open_ && c1 - open_ > BGZF_MAX_PAYLOAD) { cut.push_back(c0); open_ = c0; }
+				while (c1 - open_ >= BGZF_MAX_PAYLOAD) { open_ += BGZF_MAX_PAYLOAD; cut.push_back(open_); }
+			}
+			if (cum[(size_t)E] > cut.back()) cut.push_back(cum[(size_t)E]);
+			t_sort += wall() - t1;
+			const double t2 = wall();
+			if (ssg_recs_order(S.r, sloc.data(), cum.data(), (int64_t)E)) fail(ssg_last_error());
+			const size_t nb = cut.size() - 1; uint64_t j = 0;
+			for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
+				const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
+				if (ssg_bgzf_compress_recs(S.r, cut.data() + b0, k, obuf, out_cap, boff.data(), 0)) fail(ssg_last_error());
+				io_write_all(ofd, obuf, (size_t)boff[(size_t)k]);
+				/* the index entries of the records that begin in these blocks: an entry closes at the virtual offset of the record behind it */
+				size_t b = b0;
+				for (; j < E && cum[(size_t)j] < cut[b0 + (size_t)k]; ++j) {
+					while (cut[b + 1] <= cum[(size_t)j]) ++b;
+					const uint64_t v = (coff + boff[b - b0]) << 16 | (cum[(size_t)j] - cut[b]);
+					if (have_p && idx.push(p.tid, p.pos, p.end, v, !(p.flag & 4)) < 0) fail("the merged records are not in coordinate order");
+					p = sent[(size_t)j]; have_p = true;
+				}
+				coff += boff[(size_t)k];
+			}
+			n_blocks += nb;
+			if (ssg_recs_reopen(S.r)) fail(ssg_last_error());
+			/* what is written leaves the host lists, and a chunk all of whose records are written leaves the device */
+			for (size_t f = 0; f < F; ++f) {
+				dm_src_t &s = in[f]; uint64_t t = take[f];
+				for (size_t i = 0; i < take[f]; ++i) s.pend_bytes -= s.ent[i].len;
+				s.loc.erase(s.loc.begin(), s.loc.begin() + (ptrdiff_t)take[f]); s.key.erase(s.key.begin(), s.key.begin() + (ptrdiff_t)take[f]); s.ent.erase(s.ent.begin(), s.ent.begin() + (ptrdiff_t)take[f]);
+				while (t) {
+					std::pair<uint32_t, uint64_t> &c = s.chunks.front(); const uint64_t d = std::min(t, c.second);
+					c.second -= d; t -= d;
+					if (!c.second) { if (ssg_recs_release(S.r, c.first)) fail(ssg_last_error()); s.chunks.pop_front(); }
+				}
+			}
+			n_written += E; ++n_rounds;
+			t_write += wall() - t2;
+		}
+		if (all_ended) break;
+		const double t3 = wall();
+		load(ok);
+		if (!ok) fail(why);
+		t_load += wall() - t3;
+	}
+	ssg_host_free(obuf);
+	io_write_all(ofd, BGZF_EOF, 28);
+	const uint64_t eof_v = (coff + 28) << 16;
+	if (have_p && idx.push(p.tid, p.pos, p.end, eof_v, !(p.flag & 4)) < 0) fail("the merged records are not in coordinate order");
+	idx.finish(eof_v);
+	if (close(ofd) != 0) { ofd = -1; fail(std::string("cannot write ") + files[0]); }
+	idx.save((std::string(files[0]) + ".bai").c_str());
+	bai_note_write(files[0]);
+	dev_prof_report("merge");
+	if (dbg()) fprintf(stderr, "[sambamba] merge: %llu records of %zu inputs merged on the device in %llu round(s) of at most %llu bytes an input: %llu blocks, %.2f s (after the first load: inflate + scan %.2f s, order %.2f s, gather + deflate + write %.2f s)\n",
+	                   (unsigned long long)n_written, F, (unsigned long long)n_rounds, (unsigned long long)window, (unsigned long long)n_blocks, wall() - t0, t_load, t_sort, t_write);
+	return true;
+}
+
 static int cmd_index(int argc, char **argv)
 {
 	const char *in = 0; int threads = hw_threads();
@@ -1269,6 +1555,11 @@ static int cmd_index(int argc, char **argv)
 	const int fd = open_in(in);
 	bgzf_in_t bi(fd, threads); bam_hdr_t h;
 	if (!hdr_read(bi, h)) die("index: not a BAM file");
+	if (env_is_1("SSG_INDEX_DEVICE")) {   /* the records are found on the device; the host loop below takes over, from the start, when that cannot be */
+		std::string why;
+		if (index_device(in, fd, (int)h.names.size(), bi.tell(), why)) return 0;
+		if (dbg()) fprintf(stderr, "[sambamba] index: device index off (%s): the file is walked on the host\n", why.c_str());
+	}
 	bai_t idx((int)h.names.size(), bi.tell());
 	std::vector<uint8_t> rec;
 	for (;;) {   /* only the fixed fields, the name and the CIGAR of a record are looked at: the rest (sequence, qualities, tags) is skipped in place */
@@ -1351,6 +1642,11 @@ static int cmd_merge(int argc, char **argv)
 			if (line.size() > 3 && (!line.compare(0, 3, "@RG") || !line.compare(0, 3, "@PG") || !line.compare(0, 3, "@CO")) && ("\n" + h.text).find("\n" + line + "\n") == std::string::npos) h.text += line + "\n";
 			p = e + 1;
 		}
+	}
+	if (env_is_1("SSG_MERGE_DEVICE")) {   /* order, gather and deflate on the device, the index written with the file; the host merge below takes over when that cannot be */
+		std::string why;
+		if (merge_device(files, src, h, level, threads, why)) return 0;
+		if (dbg()) fprintf(stderr, "[sambamba] merge: device merge off (%s): the inputs are merged on the host\n", why.c_str());
 	}
 	int ofd = open(files[0], O_WRONLY | O_CREAT | O_TRUNC, 0644); if (ofd < 0) die(std::string("merge: cannot write ") + files[0]);
 	bgzf_out_t out(ofd, level, threads); hdr_write(out, h);
