@@ -146,6 +146,30 @@ int ssg_dbg_chain_sort(const int64_t *keys, int n, int64_t *out_lane, int64_t *o
 int ssg_dbg_chain(const ssg_mem_opt_t *opt, int64_t l_pac, int n_ctg, int n_reads, const int32_t *read_len, const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *rids,
                   const int64_t *intv_off, const ssg_intv_t *intv, int64_t *chain_off, ssg_chain_t **chains, int32_t **chain_seeds, int32_t *form);
 
+/* Test entry of the region stage (rows a6-a8: upstream mem_chain2aln for every chain in order, then mem_sort_dedup_patch with mem_patch_reg): the stage on chains
+ * given by the caller instead of the chaining stage's, through the one host function stage 1 of the pipeline runs -- the extension jobs in their column classes, the
+ * lane kernel, the wave kernel for what the lane kernel leaves, every form of the containment scan and of the dedup.  Of the index the kernels read the 2-bit
+ * reference, l_pac and the contig table and nothing else, so no index is needed:
+ *   pac[l_pac / 4 + 1] (the .pac file's layout: base k in byte k >> 2 at bits (~k & 3) * 2), n_ctg contigs that tile [0, l_pac) in order;
+ *   seq / off[n_reads + 1] the reads (codes 0 .. 4); read r's seeds are seeds[seed_off[r] .. seed_off[r + 1]) (rbeg, qbeg, len are read; the score is set to len,
+ *   as bwa 0.7.12 sets it); its chains are chains[chain_off[r] .. chain_off[r + 1]) in the form ssg_dbg_chain returns, so the two entries compose: rid, n, frac_rep
+ *   and first_seed are read.  first_seed is an offset into chain_seeds that runs on over ALL chains of the call (0 for the first chain of read 0, the chain
+ *   before's first_seed + n after that, across reads); chain_seeds[first_seed .. first_seed + n) are the chain's seeds as indices counted from the read's first
+ *   seed (0 = seeds[seed_off[r]]).
+ * Validated first, SSG_EINVAL with a message otherwise: 1 <= l_pac < 2^33, offsets from 0 and monotone, 1 <= read length <= 310, codes <= 4, 0 <= qbeg, 1 <= len,
+ * qbeg + len <= read length, 0 <= rbeg, rbeg + len <= 2 l_pac, every chain with n >= 1 seeds of its read, first_seed running on from the chain before, no seed in
+ * two chains (so chains <= seeds per read: the capacity of a read's region list), rid the contig of the chain's first seed, every seed of a chain inside the contig
+ * and strand of the chain's first seed (the window is cut to them), and the scoring limits of the pipeline (a x 2 x length + 64 < 8191, a <= 31, b <= 32,
+ * 0 <= -w <= 65535).
+ * Out: reg_off[n_reads + 1]; *regs (malloc'd, ssg_free) the regions as the stage leaves them, every field; route[r] (may be NULL), from what the kernels leave:
+ * SSG_REG_ROUTE_WAVE when the lane kernel left read r to the wave kernel, SSG_REG_ROUTE_PATCH when its list did not come from the dedup on compact keys (a pair
+ * of regions reached mem_patch_reg's test, or the list had more than 2048 regions).  SSG_EOVERFLOW as from the pipeline when a reference window exceeds 32768 bases. */
+#define SSG_REG_ROUTE_WAVE  1
+#define SSG_REG_ROUTE_PATCH 2
+int ssg_dbg_regions(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
+                    const int64_t *seed_off, const ssg_seed_t *seeds, const int64_t *chain_off, const ssg_chain_t *chains, const int32_t *chain_seeds,
+                    int64_t *reg_off, ssg_alnreg_t **regs, int32_t *route);
+
 /* Test entries of the paired-end decision stage (rows a9, a11): the stage on region lists given by the caller instead of stage 1's, through the kernels and
  * the host code of the pipeline itself -- the form that takes a pair (lane in LDS, lane on global memory, wave) is chosen as ssg_mem_process_pairs chooses it.
  * reg_off[2 n_pairs + 1]: read r's regions are regs[reg_off[r] .. reg_off[r + 1]) (read 1 and read 2 of a pair interleaved).  The lists are validated first

@@ -51,6 +51,9 @@ void orc_api_opt_pair(orc_opt_t *o, int flag, int max_XA_hits, float mapQ_coef_l
 { o->flag = flag; o->max_XA_hits = max_XA_hits; o->mapQ_coef_len = mapQ_coef_len; o->mapQ_coef_fac = mapQ_coef_fac; o->T = T; o->pen_unpaired = pen_unpaired; }
 /* the chaining stage's remaining knobs (bwa mem -w, -k, -c), for the chaining reference's tests */
 void orc_api_opt_chain2(orc_opt_t *o, int w, int min_seed_len, int max_occ) { o->w = w; o->min_seed_len = min_seed_len; o->max_occ = max_occ; }
+/* the region stage's knobs (bwa mem -w, -d, -L and the compiled-in max_chain_gap / mask_level_redun), for the region reference's tests */
+void orc_api_opt_regions(orc_opt_t *o, int w, int zdrop, int pen_clip5, int pen_clip3, int max_chain_gap, float mask_level_redun)
+{ o->w = w; o->zdrop = zdrop; o->pen_clip5 = pen_clip5; o->pen_clip3 = pen_clip3; o->max_chain_gap = max_chain_gap; o->mask_level_redun = mask_level_redun; }
 void orc_api_free(void *p) { free(p); }
 
 /* The chaining stage on seeds and intervals given by the caller (tests/test_chain_reference.py; the library's twin is ssg_dbg_chain): read r's seeds are
@@ -170,6 +173,49 @@ int64_t orc_api_align1_batch(const orc_opt_t *opt, const orc_idx_t *idx, int n_r
 		free(v.a); free(s);
 	}
 	reg_off[n_reads] = tot;
+	return tot;
+}
+
+/* The region stage on chains given by the caller (tests/test_region_reference.py; the library's twin is ssg_dbg_regions): orc_mem_chain2aln for every chain of a read
+ * in order, then orc_mem_sort_dedup_patch, no change of behaviour.  The index is the 2-bit reference with its contig table.  Read r's seeds are
+ * seeds[4 * seed_off[r] ..) as (rbeg, qbeg, len, unused) with score = len, its chains chains[3 * chain_off[r] ..) as (rid, n, the bits of frac_rep) with their seed
+ * indices (counted from the read's first seed) one after another in chain_seeds.  Out: reg_off[n_reads + 1], out (cap entries; the count is returned), and
+ * n_before[r] (may be NULL) = regions of read r before mem_sort_dedup_patch. */
+int64_t orc_api_regions(const orc_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq,
+                        const int64_t *off, const int64_t *seed_off, const int64_t *seeds, const int64_t *chain_off, const int64_t *chains, const int32_t *chain_seeds,
+                        int64_t *reg_off, orc_flatreg_t *out, int64_t cap, int32_t *n_before)
+{
+	orc_bns_t bns; orc_idx_t idx;
+	memset(&bns, 0, sizeof(bns)); memset(&idx, 0, sizeof(idx));
+	bns.l_pac = l_pac; bns.n_seqs = n_ctg; bns.anns = calloc((size_t)n_ctg, sizeof(orc_ann_t));
+	for (int c = 0; c < n_ctg; ++c) { bns.anns[c].offset = ctg_off[c]; bns.anns[c].len = ctg_len[c]; }
+	idx.bns = &bns; idx.pac = (uint8_t*)pac;
+	int64_t tot = 0, q = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		const int len = (int)(off[r + 1] - off[r]);
+		uint8_t *s = malloc((size_t)len + 1); memcpy(s, seq + off[r], (size_t)len);
+		orc_alnreg_v v = {0, 0, 0};
+		for (int64_t k = chain_off[r]; k < chain_off[r + 1]; ++k) {
+			orc_chain_t c; memset(&c, 0, sizeof(c));
+			uint32_t fb = (uint32_t)chains[3 * k + 2];
+			c.rid = (int)chains[3 * k]; c.n = c.m = (int)chains[3 * k + 1]; memcpy(&c.frac_rep, &fb, 4);
+			c.seeds = malloc(sizeof(orc_seed_t) * (size_t)(c.n + 1));
+			for (int j = 0; j < c.n; ++j) {
+				const int64_t *p = seeds + 4 * (seed_off[r] + chain_seeds[q++]);
+				c.seeds[j].rbeg = p[0]; c.seeds[j].qbeg = (int32_t)p[1]; c.seeds[j].len = c.seeds[j].score = (int32_t)p[2];
+			}
+			c.pos = c.seeds[0].rbeg;
+			orc_mem_chain2aln(opt, &idx, len, s, &c, &v);
+			free(c.seeds);
+		}
+		if (n_before) n_before[r] = (int32_t)v.n;
+		v.n = (size_t)orc_mem_sort_dedup_patch(opt, &idx, s, (int)v.n, v.a);
+		reg_off[r] = tot;
+		for (size_t i = 0; i < v.n; ++i) { if (tot < cap) flatten(&v.a[i], &out[tot]); ++tot; }
+		free(v.a); free(s);
+	}
+	reg_off[n_reads] = tot;
+	free(bns.anns);
 	return tot;
 }
 

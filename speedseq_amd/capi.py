@@ -33,6 +33,8 @@ CHAIN_DT = np.dtype([("pos", "i8"), ("first_seed", "i4"), ("last_seed", "i4"), (
 CHAIN_FORM_LANE, CHAIN_FORM_LDS16, CHAIN_FORM_LDS32, CHAIN_FORM_LDS64 = 0, 1, 2, 3
 CHAIN_FORM_WAVE256, CHAIN_FORM_WAVE512, CHAIN_FORM_WAVE1024, CHAIN_FORM_WAVE2048, CHAIN_FORM_WAVE5120 = 4, 5, 6, 7, 8
 CHAIN_FORM_TREE = 0x10
+# ssg_dbg_regions' route[] bits (include/ssgpu.h SSG_REG_ROUTE_*)
+REG_ROUTE_WAVE, REG_ROUTE_PATCH = 1, 2
 EXT_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("w", "i4"), ("end_bonus", "i4"), ("zdrop", "i4"), ("h0", "i4")])
 EXT_RES_DT = np.dtype([("score", "i4"), ("qle", "i4"), ("tle", "i4"), ("gtle", "i4"), ("gscore", "i4"), ("max_off", "i4")])
 SW_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("xtra", "i4"), ("_pad", "i4")])
@@ -202,6 +204,31 @@ class Lib:
         cseeds = np.frombuffer((C.c_char * (ns * 4)).from_address(sp.value), dtype=np.int32, count=ns).copy() if ns else np.zeros(0, np.int32)
         self.l.ssg_free(cp); self.l.ssg_free(sp)
         return chain_off, chains, cseeds, form
+
+    def dbg_regions(self, opt, pac, l_pac, ctg_off, ctg_len, seq, off, seed_off, seeds, chain_off, chains, chain_seeds):
+        """the region stage on given chains (ssg_dbg_regions; chains and chain_seeds in the form dbg_chain returns): (reg_off, regions [ALNREG_DT], route per read
+        [REG_ROUTE_* bits])"""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        ctg_off = np.ascontiguousarray(ctg_off, dtype=np.int64)
+        ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.int64)
+        chain_off = np.ascontiguousarray(chain_off, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=SEED_DT)
+        chains = np.ascontiguousarray(chains, dtype=CHAIN_DT)
+        chain_seeds = np.ascontiguousarray(chain_seeds, dtype=np.int32)
+        n = len(off) - 1
+        assert len(pac) >= l_pac // 4 + 1 and len(ctg_off) == len(ctg_len) and len(seed_off) == n + 1 and len(chain_off) == n + 1
+        assert len(seq) >= off[-1] and len(seeds) >= seed_off[-1] and len(chains) >= chain_off[-1] and len(chain_seeds) >= int(chains["n"][:int(chain_off[-1])].sum())
+        reg_off, route = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        rp = C.c_void_p()
+        self._chk(self.l.ssg_dbg_regions(_ptr(opt), _ptr(pac), C.c_int64(l_pac), C.c_int(len(ctg_off)), _ptr(ctg_off), _ptr(ctg_len), C.c_int(n), _ptr(seq), _ptr(off),
+                                         _ptr(seed_off), _ptr(seeds), _ptr(chain_off), _ptr(chains), _ptr(chain_seeds), _ptr(reg_off), C.byref(rp), _ptr(route)))
+        tot = int(reg_off[n])
+        regs = np.frombuffer((C.c_char * (tot * ALNREG_DT.itemsize)).from_address(rp.value), dtype=ALNREG_DT, count=tot).copy() if tot else np.zeros(0, ALNREG_DT)
+        self.l.ssg_free(rp)
+        return reg_off, regs, route
 
     def dbg_pestat(self, idx, opt, reg_off, regs, pair_batch, n_batches):
         """mem_pestat on given region lists (ssg_dbg_pestat): n_batches x 4 insert-size models"""

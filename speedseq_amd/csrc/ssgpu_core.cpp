@@ -864,64 +864,35 @@ static int run_chain(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n
 	return 0;
 }
 
-static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len,
-                      align1_dev_t &o, uint64_t stats[8])
+/* A region's band travels in 16 bits through the containment keys of the wave kernel (k_extend.h lk_m: the first 448 regions of a read).  The band of a region is
+ * opt.w, or opt.w << 1 after a band retry; a retry needs max_off >= 3/4 of the band, and max_off is below the sides of the DP matrix -- the read and its window, at
+ * most 310 + cal_max_gap < 310 + 4064 with the scores the DP cells allow (a x 2 x length + 64 < 8191) --, so no band above 5900 is ever doubled and opt.w up to
+ * 65535 is stored whole.  Above it the low 16 bits would stand for the band (0 at -w 65536: no seed is ever "contained"). */
+static int check_band(const ssg_mem_opt_t *opt)
 {
-	/* intervals per read in the dense layout: upstream's list is unbounded; a batch that needs more widens the layout for itself
-	 * and for the calls after it (low-complexity reads collect > len / 2 intervals from the re-seeding passes).  The layout starts at 5/4 of the
-	 * read length: at len / 2 (until round 6) one batch in three or four of the 1 M-pair bench met a read beyond it and paid the one-lane kernel of
-	 * the slow path (24-36 ms with the chip idle) plus a second run of the whole seeding stage (44-52 ms) -- profiles/r05_kernel_stats.csv shows the
-	 * fourth ssg_k_smem2 launch in three steps; only the entries a read has are ever touched, so the width costs HBM (12 GB per million pairs), not time */
-	static std::atomic<int> learned_cap(0);
-	int cap = std::max(std::max(96, (max_len * 5 / 4 + 31) / 32 * 32), learned_cap.load());
-	{ const int e = env_int("SSG_SMEM_CAP", 0); if (e > 0) cap = e; }   /* tests: a narrow layout walks the widening path */
-	dbuf<ssg_intv_t> d_intv; dbuf<int32_t> d_nintv(n_reads), d_nseed(n_reads);
-	CHKA(d_nintv); CHKA(d_nseed);
-	dbuf<unsigned long long> d_next(1);
-	CHKA(d_next);
-	for (;;) {
-		int need = 0;
-		if (!d_intv.alloc((size_t)n_reads * cap)) { ssg_err_msg = "device allocation failed: d_intv"; return SSG_ENOMEM; }
-		CHK(d_next.zero());
-		CHK(run_smem(idx, opt, n_reads, d_seq, d_off, max_len, cap, d_intv.p, d_nintv.p, d_next.p, &need));
-		if (need <= cap) break;
-		cap = (need + 31) / 32 * 32;
-		{ int seen = learned_cap.load(); while (seen < cap && !learned_cap.compare_exchange_weak(seen, cap)) {} }
-		if (ssg_debug()) fprintf(stderr, "[ssgpu] SMEM interval capacity widened to %d per read\n", cap);
-	}
-	if (stats) { unsigned long long c; CHK(d_next.down(&c, 1)); stats[5] = c; }
-	STAGE("smem");
-	int64_t tot = 0;
-	if (!o.seed_off.alloc(n_reads + 1)) { ssg_err_msg = "device allocation failed: seed_off"; return SSG_ENOMEM; }
-	dbuf<ssg_seed_t> d_seeds; dbuf<int32_t> d_srid, d_order, d_kept;
-	CHK(run_locate(idx, opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, &tot, d_seeds, d_srid, d_order, d_kept));   /* (d_order / d_kept are free until the chaining stage) */
-	o.tot_seeds = tot; o.h_seed_off.clear();
-	size_t ts = (size_t)tot + 1;
-	dbuf<int32_t> d_cseeds(ts), d_nchain(n_reads), d_err(n_reads);
-	dbuf<ssg_chain_t> d_chains(ts); dbuf<uint64_t> d_srt(ts); dbuf<unsigned long long> d_cells(1);
-	CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_err); CHKA(d_chains); CHKA(d_srt); CHKA(d_cells);
-	if (!o.regs.alloc(ts) || !o.n_reg.alloc(n_reads)) { ssg_err_msg = "device allocation failed: regs"; return SSG_ENOMEM; }
+	if (opt->w < 0 || opt->w > 65535) { ssg_err_msg = "band width (-w) outside 0 .. 65535: beyond the 16-bit band field of the region keys"; return SSG_EINVAL; }
+	return 0;
+}
+
+/* The region stage (upstream mem_chain2aln per chain, then mem_sort_dedup_patch with mem_patch_reg; rows a6-a8) of a batch whose chains are laid out as run_chain
+ * leaves them: per read a slice that starts at seed_off[r] in d_chains / d_order (the surviving chains' ids, n_chain[r] of them) and in d_cseeds (the chains' seed
+ * lists, absolute seed indices; a chain's first_seed is an absolute index too).  One function for stage 1 of the pipeline (run_align1) and for the test entry on chains
+ * given by the caller (ssg_dbg_regions), which hands over a view with pac, l_pac and the contig table alone: the kernels read nothing else of the index.  ts: entries of
+ * the per-seed arrays (seeds + 1).  d_work: the reads heaviest first, d_queue: a zeroed counter.  o.seed_off, o.regs (ts) and o.n_reg are the caller's; o.sdp_fixed is
+ * made here.  cells / n_jobs_out (may be NULL): SW cells and extension jobs.  todo (may be NULL, host): the reads the lane kernel left to the wave kernel. */
+static int run_regions(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, size_t ts,
+                       const ssg_seed_t *d_seeds_p, const ssg_chain_t *d_chains_p, const int32_t *d_order_p, const int32_t *d_cseeds_p, const int32_t *d_nchain_p,
+                       const int32_t *d_work_p, unsigned int *d_queue_p, align1_dev_t &o, uint64_t *cells, uint64_t *n_jobs_out, std::vector<int32_t> *todo)
+{
+	CHK(check_band(opt));
+	dbuf<int32_t> d_err(n_reads); dbuf<uint64_t> d_srt(ts); dbuf<unsigned long long> d_cells(1);
+	CHKA(d_err); CHKA(d_srt); CHKA(d_cells);
 	CHK(d_cells.zero());
-	STAGE("sal");
-	/* heaviest-first work order (seed count): the per-read cost of chaining / extension is heavy-tailed */
-	dbuf<int32_t> d_work(n_reads); dbuf<unsigned int> d_queue(8);
-	CHKA(d_work); CHKA(d_queue);
-	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());
-	if (ssg_debug() >= 2) { /* tuning: seeds-per-read histogram (power-of-two bins) */
-		std::vector<int32_t> hns(n_reads);
-		CHK(d_nseed.down(hns.data(), n_reads));
-		long cnt[20] = {0}, sum[20] = {0};
-		for (int r = 0; r < n_reads; ++r) { int b = 0; while ((1 << b) <= hns[r] && b < 19) ++b; ++cnt[b]; sum[b] += hns[r]; }
-		for (int b = 0; b < 20; ++b) if (cnt[b]) fprintf(stderr, "[ssg] seeds/read < %d: %ld reads, %ld seeds\n", 1 << b, cnt[b], sum[b]);
-	}
-	CHK(run_chain(idx->v, opt, n_reads, d_off, max_len, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p,
-	              d_work.p, d_queue.p, stats ? &stats[7] : (uint64_t*)0, (int32_t*)0));
-	STAGE("chain");
 	/* ---- extensions of every chain's first seed, one lane each (k_extlane.h) ---- */
 	dbuf<int64_t> d_choff((size_t)n_reads + 1);
 	CHKA(d_choff);
 	int64_t n_jobs64 = 0;
-	CHK(ssg_dev_exclusive_scan(d_nchain.p, d_choff.p, n_reads, &n_jobs64));
+	CHK(ssg_dev_exclusive_scan(d_nchain_p, d_choff.p, n_reads, &n_jobs64));
 	if (n_jobs64 >= (int64_t)1 << 31) { ssg_err_msg = "more than 2^31 chains in one call"; return SSG_EOVERFLOW; }
 	const long n_jobs = (long)n_jobs64;
 	dbuf<ssg_xjob_t> d_xjobs((size_t)n_jobs + 1); dbuf<ssg_xres_t> d_xl((size_t)n_jobs + 1), d_xr((size_t)n_jobs + 1);
@@ -932,7 +903,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		if (opt->min_chain_weight > 0 && 2.8f * (float)opt->min_chain_weight <= 0.05f * (float)max_len) {   /* upstream mem_flt_chained_seeds would run (MEM_HSP_COEF x W <= MEM_SEEDSW_COEF x l): its seed-level SW is not built */
 			ssg_err_msg = "-W this small against this read length turns on upstream's chained-seed filter (long-read path), which this build does not have"; return SSG_EINVAL; }
 		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
-		SSG_LAUNCH(ssg_k_ext_prep, (n_jobs + 255) / 256, 256, 0, idx->v, *opt, n_reads, n_jobs, d_off, o.seed_off.p, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p,
+		SSG_LAUNCH(ssg_k_ext_prep, (n_jobs + 255) / 256, 256, 0, ix, *opt, n_reads, n_jobs, d_off, o.seed_off.p, d_seeds_p, d_chains_p, d_order_p, d_cseeds_p,
 		           d_choff.p, d_seq, (int)SSG_TWIN_GLB, d_xjobs.p, d_kl.p, d_kr.p);
 		CHK(prim_sort_keys(d_kl.p, d_sl.p, n_jobs, 32, 50)); CHK(prim_sort_keys(d_kr.p, d_sr.p, n_jobs, 32, 50));   /* 9 + 9 bits: 511 - side length, 511 - expected rows */
 		if (ssg_debug()) fprintf(stderr, "[ssgpu] ext jobs %ld\n", n_jobs);
@@ -970,7 +941,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 				 * 125.3 vs 119.4 ms at 2x150, 157.7 vs 151.3 at 2x250, profiles/r06f_ext_unroll_ab*.json: the cell loop waits for its own dependent VALU chain, not for LDS) */
 				const int c = caps[k], U = c > 72 ? 4 : 2; const size_t lds = (size_t)(c + 2 * U) * 256;
 				const bool xl_eq = opt->o_del + opt->e_del == opt->o_ins + opt->e_ins;   /* k_extlane.h: one `M - (open + extend)' per cell serves E and F */
-#define SSG_XL_GO1(LAUNCH, UU, EE, ...) LAUNCH(__VA_ARGS__ (ssg_k_ext_lane_dyn<UU, EE>), (to - from + 63) / 64, 64, lds, idx->v, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c)
+#define SSG_XL_GO1(LAUNCH, UU, EE, ...) LAUNCH(__VA_ARGS__ (ssg_k_ext_lane_dyn<UU, EE>), (to - from + 63) / 64, 64, lds, ix, *opt, side, from, to, srt, d_xjobs.p, d_seq, d_off, d_xl.p, d_xr.p, d_cells.p, c)
 #define SSG_XL_GO(LAUNCH, ...) do { if (U == 4) { if (xl_eq) SSG_XL_GO1(LAUNCH, 4, true, __VA_ARGS__); else SSG_XL_GO1(LAUNCH, 4, false, __VA_ARGS__); } \
                                     else { if (xl_eq) SSG_XL_GO1(LAUNCH, 2, true, __VA_ARGS__); else SSG_XL_GO1(LAUNCH, 2, false, __VA_ARGS__); } } while (0)
 				if (q % 3 == 0) SSG_XL_GO(SSG_LAUNCH); else if (q % 3 == 1) SSG_XL_GO(SSG_LAUNCH_ON, 0,); else SSG_XL_GO(SSG_LAUNCH_ON, 1,);
@@ -992,15 +963,76 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 		CHKA(d_todo); CHKA(d_ntodo); CHK(d_ntodo.zero());
 		if (!o.sdp_fixed.alloc((size_t)n_reads)) { ssg_err_msg = "device allocation failed: sdp_fixed"; return SSG_ENOMEM; }
 		CHK(o.sdp_fixed.zero());
-		SSG_LAUNCH(ssg_k_chain2aln_lane, (n_reads + 63) / 64, 64, 0, idx->v, *opt, n_reads, d_off, o.seed_off.p, d_seeds.p, d_cseeds.p, d_nchain.p, o.regs.p, o.n_reg.p, d_err.p,
-		           d_choff.p, d_xjobs.p, d_xl.p, d_xr.p, d_work.p, d_todo.p, d_ntodo.p, o.sdp_fixed.p);
-		SSG_LAUNCH_W(max_len > 255, ssg_k_chain2aln, nwg, wpb * 64, 0, idx->v, *opt, n_reads, d_seq, d_off, o.seed_off.p, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p,
-		           d_nchain.p, d_srt.p, o.regs.p, o.n_reg.p, d_tglb.p, d_err.p, d_cells.p, d_work.p, d_queue.p, ssg_debug() >= 2, d_sdpbig.p, d_bcopy.p,
+		SSG_LAUNCH(ssg_k_chain2aln_lane, (n_reads + 63) / 64, 64, 0, ix, *opt, n_reads, d_off, o.seed_off.p, d_seeds_p, d_cseeds_p, d_nchain_p, o.regs.p, o.n_reg.p, d_err.p,
+		           d_choff.p, d_xjobs.p, d_xl.p, d_xr.p, d_work_p, d_todo.p, d_ntodo.p, o.sdp_fixed.p);
+		SSG_LAUNCH_W(max_len > 255, ssg_k_chain2aln, nwg, wpb * 64, 0, ix, *opt, n_reads, d_seq, d_off, o.seed_off.p, d_seeds_p, d_chains_p, d_order_p, d_cseeds_p,
+		           d_nchain_p, d_srt.p, o.regs.p, o.n_reg.p, d_tglb.p, d_err.p, d_cells.p, d_work_p, d_queue_p, ssg_debug() >= 2, d_sdpbig.p, d_bcopy.p,
 		           d_choff.p, d_xjobs.p, d_xl.p, d_xr.p, d_todo.p, d_ntodo.p, o.sdp_fixed.p);
 		CHK(rt_sync());
+		if (todo) { unsigned int nt = 0; CHK(d_ntodo.down(&nt, 1)); todo->resize(nt); if (nt) CHK(d_todo.down(todo->data(), nt)); }
 	}
 	{ unsigned int cc[5]; CHK(dev_class_counts(d_err.p, n_reads, 0, 0, 0, cc)); if (cc[4]) { ssg_err_msg = "reference window of a chain exceeds SSG_TWIN_GLB"; return SSG_EOVERFLOW; } }
-	if (stats) { unsigned long long c; CHK(d_cells.down(&c, 1)); stats[0] = (uint64_t)tot; stats[1] = c; stats[6] = (uint64_t)n_jobs; }
+	if (cells) { unsigned long long c; CHK(d_cells.down(&c, 1)); *cells = c; }
+	if (n_jobs_out) *n_jobs_out = (uint64_t)n_jobs;
+	return 0;
+}
+
+static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len,
+                      align1_dev_t &o, uint64_t stats[8])
+{
+	/* intervals per read in the dense layout: upstream's list is unbounded; a batch that needs more widens the layout for itself
+	 * and for the calls after it (low-complexity reads collect > len / 2 intervals from the re-seeding passes).  The layout starts at 5/4 of the
+	 * read length: at len / 2 (until round 6) one batch in three or four of the 1 M-pair bench met a read beyond it and paid the one-lane kernel of
+	 * the slow path (24-36 ms with the chip idle) plus a second run of the whole seeding stage (44-52 ms) -- profiles/r05_kernel_stats.csv shows the
+	 * fourth ssg_k_smem2 launch in three steps; only the entries a read has are ever touched, so the width costs HBM (12 GB per million pairs), not time */
+	CHK(check_band(opt));   /* (refused before the seeding stage runs, not after it) */
+	static std::atomic<int> learned_cap(0);
+	int cap = std::max(std::max(96, (max_len * 5 / 4 + 31) / 32 * 32), learned_cap.load());
+	{ const int e = env_int("SSG_SMEM_CAP", 0); if (e > 0) cap = e; }   /* tests: a narrow layout walks the widening path */
+	dbuf<ssg_intv_t> d_intv; dbuf<int32_t> d_nintv(n_reads), d_nseed(n_reads);
+	CHKA(d_nintv); CHKA(d_nseed);
+	dbuf<unsigned long long> d_next(1);
+	CHKA(d_next);
+	for (;;) {
+		int need = 0;
+		if (!d_intv.alloc((size_t)n_reads * cap)) { ssg_err_msg = "device allocation failed: d_intv"; return SSG_ENOMEM; }
+		CHK(d_next.zero());
+		CHK(run_smem(idx, opt, n_reads, d_seq, d_off, max_len, cap, d_intv.p, d_nintv.p, d_next.p, &need));
+		if (need <= cap) break;
+		cap = (need + 31) / 32 * 32;
+		{ int seen = learned_cap.load(); while (seen < cap && !learned_cap.compare_exchange_weak(seen, cap)) {} }
+		if (ssg_debug()) fprintf(stderr, "[ssgpu] SMEM interval capacity widened to %d per read\n", cap);
+	}
+	if (stats) { unsigned long long c; CHK(d_next.down(&c, 1)); stats[5] = c; }
+	STAGE("smem");
+	int64_t tot = 0;
+	if (!o.seed_off.alloc(n_reads + 1)) { ssg_err_msg = "device allocation failed: seed_off"; return SSG_ENOMEM; }
+	dbuf<ssg_seed_t> d_seeds; dbuf<int32_t> d_srid, d_order, d_kept;
+	CHK(run_locate(idx, opt, n_reads, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, &tot, d_seeds, d_srid, d_order, d_kept));   /* (d_order / d_kept are free until the chaining stage) */
+	o.tot_seeds = tot; o.h_seed_off.clear();
+	size_t ts = (size_t)tot + 1;
+	dbuf<int32_t> d_cseeds(ts), d_nchain(n_reads);
+	dbuf<ssg_chain_t> d_chains(ts);
+	CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_chains);
+	if (!o.regs.alloc(ts) || !o.n_reg.alloc(n_reads)) { ssg_err_msg = "device allocation failed: regs"; return SSG_ENOMEM; }
+	STAGE("sal");
+	/* heaviest-first work order (seed count): the per-read cost of chaining / extension is heavy-tailed */
+	dbuf<int32_t> d_work(n_reads); dbuf<unsigned int> d_queue(8);
+	CHKA(d_work); CHKA(d_queue);
+	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());
+	if (ssg_debug() >= 2) { /* tuning: seeds-per-read histogram (power-of-two bins) */
+		std::vector<int32_t> hns(n_reads);
+		CHK(d_nseed.down(hns.data(), n_reads));
+		long cnt[20] = {0}, sum[20] = {0};
+		for (int r = 0; r < n_reads; ++r) { int b = 0; while ((1 << b) <= hns[r] && b < 19) ++b; ++cnt[b]; sum[b] += hns[r]; }
+		for (int b = 0; b < 20; ++b) if (cnt[b]) fprintf(stderr, "[ssg] seeds/read < %d: %ld reads, %ld seeds\n", 1 << b, cnt[b], sum[b]);
+	}
+	CHK(run_chain(idx->v, opt, n_reads, d_off, max_len, d_intv.p, d_nintv.p, cap, d_nseed.p, o.seed_off.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p,
+	              d_work.p, d_queue.p, stats ? &stats[7] : (uint64_t*)0, (int32_t*)0));
+	STAGE("chain");
+	CHK(run_regions(idx->v, opt, n_reads, d_seq, d_off, max_len, ts, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p, o,
+	                stats ? &stats[1] : (uint64_t*)0, stats ? &stats[6] : (uint64_t*)0, (std::vector<int32_t>*)0));
+	if (stats) stats[0] = (uint64_t)tot;
 	return 0;
 }
 
@@ -1122,6 +1154,124 @@ int ssg_dbg_chain(const ssg_mem_opt_t *opt, int64_t l_pac, int n_ctg, int n_read
 	}
 	chain_off[n_reads] = k;
 	*chains = oc; *chain_seeds = os;
+	return SSG_OK;
+}
+
+/* test entry: the region stage on the caller's chains (include/ssgpu.h), through run_regions as stage 1 goes through it */
+int ssg_dbg_regions(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
+                    const int64_t *seed_off, const ssg_seed_t *seeds, const int64_t *chain_off, const ssg_chain_t *chains, const int32_t *chain_seeds,
+                    int64_t *reg_off, ssg_alnreg_t **regs, int32_t *route)
+{
+	static thread_local char msg[200];
+	CHK(ssg_need_device());
+	*regs = 0;
+	if (n_reads < 0 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) { ssg_err_msg = "ssg_dbg_regions: need n_reads >= 0, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
+	for (int c = 0; c < n_ctg; ++c)
+		if (ctg_len[c] < 1 || ctg_off[c] != (c ? ctg_off[c - 1] + ctg_len[c - 1] : 0) || ctg_off[c] + ctg_len[c] > l_pac || (c == n_ctg - 1 && ctg_off[c] + ctg_len[c] != l_pac)) {
+			ssg_err_msg = "ssg_dbg_regions: the contigs must tile [0, l_pac) in order"; return SSG_EINVAL; }
+	if (n_reads == 0) { reg_off[0] = 0; return SSG_OK; }
+	const char *bad = 0; long at = 0;
+	if (off[0] != 0 || seed_off[0] != 0 || chain_off[0] != 0) bad = "offsets start at 0: read";
+	int max_len = 0;
+	auto ctg_of = [&](int64_t p) { const int64_t f = p < l_pac ? p : 2 * l_pac - 1 - p; int lo = 0, hi = n_ctg - 1; while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ctg_off[mid] <= f) lo = mid; else hi = mid - 1; } return lo; };
+	std::vector<uint8_t> used;
+	for (int r = 0; !bad && r < n_reads; ++r) {
+		at = r;
+		if (off[r + 1] < off[r] || seed_off[r + 1] < seed_off[r] || chain_off[r + 1] < chain_off[r]) { bad = "offsets must not decrease: read"; break; }
+		const int64_t len64 = off[r + 1] - off[r], ns = seed_off[r + 1] - seed_off[r], nc = chain_off[r + 1] - chain_off[r];
+		if (len64 < 1 || len64 > SSG_MAX_READ_LEN) { bad = "need 1 <= read length <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
+		if (ns >= (int64_t)1 << 24) { bad = "more than 2^24 seeds: read"; break; }
+		if (nc > ns) { bad = "more chains than seeds: read"; break; }
+		const int len = (int)len64;
+		max_len = std::max(max_len, len);
+		for (int64_t k = off[r]; k < off[r + 1]; ++k) if (seq[k] > 4) { bad = "read codes are 0 .. 4: read"; break; }
+		for (int64_t k = seed_off[r]; !bad && k < seed_off[r + 1]; ++k) {
+			const ssg_seed_t &sd = seeds[k];
+			if (!(0 <= sd.qbeg && 1 <= sd.len && sd.qbeg <= len - sd.len)) bad = "need 0 <= qbeg, 1 <= len, qbeg + len <= read length: seed";
+			else if (!(0 <= sd.rbeg && sd.rbeg <= 2 * l_pac - sd.len)) bad = "need 0 <= rbeg, rbeg + len <= 2 l_pac: seed";
+			if (bad) at = (long)k;
+		}
+		used.assign((size_t)ns, 0);
+		for (int64_t k = chain_off[r]; !bad && k < chain_off[r + 1]; ++k) {
+			const ssg_chain_t &c = chains[k];
+			at = (long)k;
+			if (c.n < 1) { bad = "a chain has at least 1 seed: chain"; break; }
+			if (c.first_seed < 0 || (k > 0 && c.first_seed != chains[k - 1].first_seed + chains[k - 1].n) || (k == 0 && c.first_seed != 0)) { bad = "first_seed must run on from the chain before: chain"; break; }
+			for (int j = 0; j < c.n; ++j) {
+				const int32_t id = chain_seeds[c.first_seed + j];
+				if (id < 0 || id >= ns) { bad = "a seed index outside the read's seeds: chain"; break; }
+				if (used[(size_t)id]) { bad = "a seed in two chains: chain"; break; }
+				used[(size_t)id] = 1;
+			}
+			if (bad) break;
+			const int64_t first = seeds[seed_off[r] + chain_seeds[c.first_seed]].rbeg;
+			if (c.rid != ctg_of(first)) { bad = "rid must be the contig of the chain's first seed: chain"; break; }
+			/* the window is cut to the first seed's contig and strand (ssg_k_ext_prep): a seed outside it would index the window out of range */
+			int64_t cb = ctg_off[c.rid], ce = cb + ctg_len[c.rid];
+			if (first >= l_pac) { const int64_t t = cb; cb = 2 * l_pac - ce; ce = 2 * l_pac - t; }
+			for (int j = 0; j < c.n; ++j) {
+				const ssg_seed_t &sd = seeds[seed_off[r] + chain_seeds[c.first_seed + j]];
+				if (sd.rbeg < cb || sd.rbeg + sd.len > ce) { bad = "every seed of a chain must lie inside the contig and strand of its first seed: chain"; break; }
+			}
+			if (bad) break;
+		}
+	}
+	if (!bad) {   /* the scoring limits of the pipeline, whatever the chains: run_regions checks them only where there is a job */
+		if (opt->a * 2 * max_len + 64 >= 8191) { ssg_err_msg = "match score x read length beyond the 13-bit DP cells of the extension kernel"; return SSG_EINVAL; }
+		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
+		if (opt->e_del < 1 || opt->e_ins < 1) { ssg_err_msg = "ssg_dbg_regions: gap extension penalties must be positive"; return SSG_EINVAL; }
+	}
+	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_regions: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
+	const int64_t tot = seed_off[n_reads];
+	if (tot >= (int64_t)1 << 31) { ssg_err_msg = "ssg_dbg_regions: more than 2^31 seeds"; return SSG_EINVAL; }
+	/* the stage's inputs as the chaining stage leaves them: per read a slice at seed_off[r] of chain records, their order and their seed lists (absolute indices) */
+	const size_t ts = (size_t)tot + 1;
+	std::vector<ssg_seed_t> h_sd(ts); std::vector<ssg_chain_t> h_ch(ts); std::vector<int32_t> h_ord(ts, 0), h_cs(ts, 0), h_nc((size_t)n_reads), h_ns((size_t)n_reads);
+	memset(h_ch.data(), 0, ts * sizeof(ssg_chain_t)); memset(h_sd.data(), 0, ts * sizeof(ssg_seed_t));
+	for (int64_t k = 0; k < tot; ++k) { h_sd[k] = seeds[k]; h_sd[k].score = seeds[k].len; h_sd[k].next = -1; }
+	for (int r = 0; r < n_reads; ++r) {
+		const int64_t s0 = seed_off[r];
+		int64_t q = s0;
+		h_nc[r] = (int32_t)(chain_off[r + 1] - chain_off[r]); h_ns[r] = (int32_t)(seed_off[r + 1] - s0);
+		for (int i = 0; i < h_nc[r]; ++i) {
+			const ssg_chain_t &c = chains[chain_off[r] + i];
+			ssg_chain_t &d = h_ch[s0 + i];
+			d = c; d.first_seed = (int32_t)q; d.last_seed = -1;
+			h_ord[s0 + i] = i;
+			for (int j = 0; j < c.n; ++j) h_cs[q++] = (int32_t)(s0 + chain_seeds[c.first_seed + j]);
+		}
+	}
+	const size_t pac_bytes = (size_t)(l_pac / 4 + 1);
+	dbuf<uint8_t> d_pac(pac_bytes), d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_coff((size_t)n_ctg), d_off((size_t)n_reads + 1); dbuf<int32_t> d_clen((size_t)n_ctg);
+	dbuf<ssg_seed_t> d_seeds(ts); dbuf<ssg_chain_t> d_chains(ts); dbuf<int32_t> d_order(ts), d_cseeds(ts), d_nchain(n_reads), d_nseed(n_reads), d_work(n_reads); dbuf<unsigned int> d_queue(8);
+	CHKA(d_pac); CHKA(d_seq); CHKA(d_coff); CHKA(d_off); CHKA(d_clen); CHKA(d_seeds); CHKA(d_chains); CHKA(d_order); CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_nseed); CHKA(d_work); CHKA(d_queue);
+	CHK(d_pac.up(pac, pac_bytes)); CHK(d_seq.up(seq, (size_t)off[n_reads])); CHK(d_coff.up(ctg_off, (size_t)n_ctg)); CHK(d_clen.up(ctg_len, (size_t)n_ctg)); CHK(d_off.up(off, (size_t)n_reads + 1));
+	CHK(d_seeds.up(h_sd.data(), ts)); CHK(d_chains.up(h_ch.data(), ts)); CHK(d_order.up(h_ord.data(), ts)); CHK(d_cseeds.up(h_cs.data(), ts));
+	CHK(d_nchain.up(h_nc.data(), n_reads)); CHK(d_nseed.up(h_ns.data(), n_reads));
+	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());   /* (as run_align1 makes the work order) */
+	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
+	ix.pac = d_pac.p; ix.ctg_off = d_coff.p; ix.ctg_len = d_clen.p; ix.l_pac = l_pac; ix.n_ctg = n_ctg;
+	align1_dev_t o;
+	if (!o.seed_off.alloc((size_t)n_reads + 1) || !o.regs.alloc(ts) || !o.n_reg.alloc(n_reads)) { ssg_err_msg = "device allocation failed: regs"; return SSG_ENOMEM; }
+	CHK(o.seed_off.up(seed_off, (size_t)n_reads + 1));
+	std::vector<int32_t> todo;
+	CHK(run_regions(ix, opt, n_reads, d_seq.p, d_off.p, max_len, ts, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p, o, (uint64_t*)0, (uint64_t*)0, &todo));
+	std::vector<int32_t> hn((size_t)n_reads); std::vector<uint8_t> hf((size_t)n_reads); std::vector<ssg_alnreg_t> all(ts);
+	CHK(o.n_reg.down(hn.data(), n_reads)); CHK(o.sdp_fixed.down(hf.data(), n_reads)); CHK(o.regs.down(all.data(), (size_t)tot));
+	int64_t n_out = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (hn[r] < 0 || hn[r] > h_ns[r]) { ssg_err_msg = "ssg_dbg_regions: a read's region count is outside its slice"; return SSG_EOVERFLOW; }
+		reg_off[r] = n_out; n_out += hn[r];
+	}
+	reg_off[n_reads] = n_out;
+	ssg_alnreg_t *out = (ssg_alnreg_t*)malloc(sizeof(ssg_alnreg_t) * (size_t)(n_out + 1));
+	if (!out) { ssg_err_msg = "host allocation failed: regions"; return SSG_ENOMEM; }
+	for (int r = 0; r < n_reads; ++r) memcpy(out + reg_off[r], all.data() + seed_off[r], sizeof(ssg_alnreg_t) * (size_t)hn[r]);
+	if (route) {
+		for (int r = 0; r < n_reads; ++r) route[r] = hf[r] == 0 ? SSG_REG_ROUTE_PATCH : 0;
+		for (size_t k = 0; k < todo.size(); ++k) if (todo[k] >= 0 && todo[k] < n_reads) route[todo[k]] |= SSG_REG_ROUTE_WAVE;
+	}
+	*regs = out;
 	return SSG_OK;
 }
 

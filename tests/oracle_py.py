@@ -113,6 +113,36 @@ class Oracle:
         nc =int(chain_off[n])
         return chain_off, chains[:nc], cseeds[:int(chains[:nc, 2].sum())]
 
+    def opt_regions(self, opt, w, zdrop, pen_clip5, pen_clip3, max_chain_gap, mask_level_redun):
+        """the knobs of the region stage on an option block of opt_scores()"""
+        self.l.orc_api_opt_regions(opt, C.c_int(w), C.c_int(zdrop), C.c_int(pen_clip5), C.c_int(pen_clip3), C.c_int(max_chain_gap), C.c_float(mask_level_redun))
+        return opt
+
+    def regions(self, pac, l_pac, ctg_off, ctg_len, seq, off, seed_off, seeds4, chain_off, chains3, chain_seeds, opt=None):
+        """the region stage on given chains (orc_api_regions): seeds as (rbeg, qbeg, len, unused) rows, chains as (rid, n, frac_rep bits) rows with their seed indices
+        one after another in chain_seeds: (reg_off, regions [ALNREG_DT], regions per read before mem_sort_dedup_patch)"""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        ctg_off = np.ascontiguousarray(ctg_off, dtype=np.int64)
+        ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.int64)
+        chain_off = np.ascontiguousarray(chain_off, dtype=np.int64)
+        seeds4 = np.ascontiguousarray(seeds4, dtype=np.int64).reshape(-1, 4)
+        chains3 = np.ascontiguousarray(chains3, dtype=np.int64).reshape(-1, 3)
+        chain_seeds = np.ascontiguousarray(chain_seeds, dtype=np.int32)
+        n = len(off) - 1
+        assert len(pac) >= l_pac // 4 + 1 and len(seed_off) == n + 1 and len(chain_off) == n + 1 and len(seeds4) >= seed_off[-1] and len(chains3) >= chain_off[-1]
+        assert len(chain_seeds) >= int(chains3[:int(chain_off[-1]), 1].sum())
+        reg_off, n_before = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        cap = int(seed_off[-1]) + 1
+        out = np.zeros(cap, dtype=ALNREG_DT)
+        self.l.orc_api_regions.restype = C.c_int64
+        tot = self.l.orc_api_regions(opt or self.opt, _ptr(pac), C.c_int64(l_pac), C.c_int(len(ctg_off)), _ptr(ctg_off), _ptr(ctg_len), C.c_int(n), _ptr(seq), _ptr(off),
+                                     _ptr(seed_off), _ptr(seeds4), _ptr(chain_off), _ptr(chains3), _ptr(chain_seeds), _ptr(reg_off), _ptr(out), C.c_int64(cap), _ptr(n_before))
+        assert tot <= cap
+        return reg_off, out[:tot], n_before
+
     def align1_batch(self, idx, seq, off, opt=None):
         n = len(off) - 1
         reg_off = np.zeros(n + 1, dtype=np.int64)
