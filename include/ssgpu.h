@@ -382,6 +382,12 @@ int ssg_bgzf_deflate(const uint8_t *payload, const uint64_t *cut, long n_blocks,
  * header with BSIZE, the same deflate stream, CRC-32 and ISIZE of the payload, all made on the device; concatenated they are a BGZF file's body.  A block
  * without payload becomes the 28-byte end-of-file marker: a caller ends a file by appending one.  crc (may be NULL) receives the payloads' CRC-32. */
 int ssg_bgzf_compress(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc);
+/* The forms with a deflate level (zlib's scale; ssg_bgzf_compress_recs_level: below, with the record store).  1..6: the calls above, byte for byte -- the device has
+ * one parse below 7.  7, 8, 9: a chained match finder (csrc/k_bgzf_deep.h) that looks at up to 8 / 32 / 128 earlier positions of the hash, nearest first, where the
+ * parse above looks at six: smaller streams, more kernel time; the same contract (any inflate gives back the payload, a block that would not shrink is stored).
+ * SSG_EINVAL for level 0 (the device writes no stored-only file) and for anything outside 1..9. */
+int ssg_bgzf_deflate_level(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int level);
+int ssg_bgzf_compress_level(const uint8_t *payload, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc, int level);
 /* an out_cap that always suffices for ssg_bgzf_compress: payload + 31 per block (5 of the stored form, 26 of header and trailer; bgzf.c:298-342) */
 uint64_t ssg_bgzf_bound(uint64_t payload_bytes, long n_blocks);
 /* CRC-32 (zlib's, the one of a BGZF member's trailer, bgzf.c:298-342) of n byte ranges data[cut[i] .. cut[i+1]) of any length, on the device; host buffers.
@@ -417,6 +423,7 @@ int ssg_recs_append(ssg_recs_t *r, const uint8_t *bytes, uint64_t len, uint32_t 
 int ssg_recs_order(ssg_recs_t *r, const uint64_t *loc, const uint64_t *cum, int64_t n);
 int ssg_recs_gather(ssg_recs_t *r, uint64_t v0, uint64_t v1, uint8_t *out);
 int ssg_bgzf_compress_recs(ssg_recs_t *r, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc);
+int ssg_bgzf_compress_recs_level(ssg_recs_t *r, const uint64_t *cut, long n_blocks, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint32_t *crc, int level);   /* ssg_bgzf_compress_level's levels */
 void ssg_recs_free(ssg_recs_t *r);
 /* ---- BAM read into the store: members inflated there, their records found there (row f1; the reader in the reference: bgzf_read_block and bam_read1, htslib) ----
  * ssg_recs_append_bgzf: ssg_bgzf_inflate whose output becomes a new chunk of the store instead of a host buffer: the same walk of the headers on the host, the

@@ -470,9 +470,23 @@ def bgzf_bound(lib, payload_bytes, n_blocks):
     return int(lib.l.ssg_bgzf_bound(C.c_uint64(payload_bytes), C.c_long(n_blocks)))
 
 
-def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None):
-    """ssg_bgzf_compress: the blocks payload[cut[b] .. cut[b+1]) (<= 0xff00 bytes each) as complete BGZF members, deflated, checksummed and framed on
-    the device.  Returns (out, out_off, crc): member b is out[out_off[b]:out_off[b+1]], out[:out_off[-1]] a BGZF file's body; crc is None unless wanted."""
+def bgzf_deflate(lib, payload, cut, level=None):
+    """ssg_bgzf_deflate (level None) / ssg_bgzf_deflate_level: the raw deflate stream of every block payload[cut[b] .. cut[b+1]).  Returns (out, out_off):
+    block b's stream is out[out_off[b]:out_off[b+1]].  Levels 1..6 are the bytes of level None, 7..9 the chained match finder (csrc/k_bgzf_deep.h)."""
+    payload = _bytes_u8(payload)
+    cut = np.ascontiguousarray(cut, dtype=np.uint64)
+    n = len(cut) - 1
+    cap = (int(cut[-1] - cut[0]) if n > 0 else 0) + 5 * max(n, 0) + 64
+    out = np.zeros(cap, dtype=np.uint8)
+    off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+    args = (_ptr(payload) if payload.size else None, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off))
+    lib._chk(lib.l.ssg_bgzf_deflate(*args) if level is None else lib.l.ssg_bgzf_deflate_level(*args, C.c_int(level)))
+    return out[:int(off[-1])], off
+
+
+def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None, level=None):
+    """ssg_bgzf_compress (level None) / ssg_bgzf_compress_level: the blocks payload[cut[b] .. cut[b+1]) (<= 0xff00 bytes each) as complete BGZF members, deflated,
+    checksummed and framed on the device.  Returns (out, out_off, crc): member b is out[out_off[b]:out_off[b+1]], out[:out_off[-1]] a BGZF file's body; crc is None unless wanted."""
     payload = _bytes_u8(payload)
     cut = np.ascontiguousarray(cut, dtype=np.uint64)
     n = len(cut) - 1
@@ -480,8 +494,8 @@ def bgzf_compress(lib, payload, cut, want_crc=True, out_cap=None):
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
     crc = np.zeros(max(n, 1), dtype=np.uint32) if want_crc else None
-    lib._chk(lib.l.ssg_bgzf_compress(_ptr(payload) if payload.size else None, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off),
-                                     _ptr(crc) if want_crc else None))
+    args = (_ptr(payload) if payload.size else None, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off), _ptr(crc) if want_crc else None)
+    lib._chk(lib.l.ssg_bgzf_compress(*args) if level is None else lib.l.ssg_bgzf_compress_level(*args, C.c_int(level)))
     return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
 
 
@@ -552,15 +566,16 @@ def recs_gather(lib, recs, v0, v1, out=None):
     return out[:max(int(v1) - int(v0), 0)]
 
 
-def bgzf_compress_recs(lib, recs, cut, want_crc=True, out_cap=None):
-    """ssg_bgzf_compress_recs: bgzf_compress of the store's stream bytes cut[0] .. cut[-1] (absolute offsets), the payload gathered on the device."""
+def bgzf_compress_recs(lib, recs, cut, want_crc=True, out_cap=None, level=None):
+    """ssg_bgzf_compress_recs (level None) / ssg_bgzf_compress_recs_level: bgzf_compress of the store's stream bytes cut[0] .. cut[-1] (absolute offsets), the payload gathered on the device."""
     cut = np.ascontiguousarray(cut, dtype=np.uint64)
     n = len(cut) - 1
     cap = bgzf_bound(lib, int(cut[-1] - cut[0]) if n > 0 else 0, n) if out_cap is None else int(out_cap)
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     off = np.zeros(max(n, 0) + 1, dtype=np.uint64)
     crc = np.zeros(max(n, 1), dtype=np.uint32) if want_crc else None
-    lib._chk(lib.l.ssg_bgzf_compress_recs(recs.h, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off), _ptr(crc) if want_crc else None))
+    args = (recs.h, _ptr(cut), C.c_long(n), _ptr(out), C.c_uint64(cap), _ptr(off), _ptr(crc) if want_crc else None)
+    lib._chk(lib.l.ssg_bgzf_compress_recs(*args) if level is None else lib.l.ssg_bgzf_compress_recs_level(*args, C.c_int(level)))
     return out[:int(off[-1])], off, (crc[:max(n, 0)] if want_crc else None)
 
 

@@ -107,6 +107,8 @@ SSG_DEVFN void bz_w_put(bz_writer_t &w, uint32_t bits, int n)
 }
 SSG_DEVFN void bz_w_end(bz_writer_t &w) { if (w.nacc > 0) atomicOr(w.out + w.word, (uint32_t)w.acc); }
 
+#ifndef BZ_HELPERS_ONLY   /* k_bgzf_deep.h takes the helpers above into a translation unit of its own; the two kernels belong to ssg_bgzf.cpp alone */
+
 /*
  * payload: the concatenated block payloads, cut[b] .. cut[b+1] delimits block blk0 + b (<= BZ_MAX_PAYLOAD bytes).  tmp: BZ_OUT_STRIDE bytes
  * per launched wave... per block of this launch; sym: BZ_STRETCH_CAP * 64 words per block.  size[b] = bytes of the block's deflate stream in tmp.
@@ -314,4 +316,5 @@ __global__ void __launch_bounds__(256) ssg_k_bgzf_compact(const uint8_t *tmp, co
 	const uint32_t n = (uint32_t)(off[b + 1] - off[b]);
 	for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) d[k] = s[k];
 }
+#endif   /* BZ_HELPERS_ONLY */
 #endif

@@ -38,6 +38,11 @@ extern "C" int ssg_sa_verify(const ssg_index *ix, int new_intv, const uint64_t *
 /* ssg_bgzf_frame.cpp: the launchers of the CRC-32 and framing kernels (k_bgzf_frame.h), queued on the calling thread's stream; device buffers */
 extern "C" int ssg_crc32_ranges_dev(const uint8_t *d_data, const uint64_t *d_cut, long n, uint32_t *d_crc);
 extern "C" int ssg_bgzf_frame_dev(const uint8_t *d_tmp, uint32_t tmp_stride, const uint64_t *d_cut, const uint64_t *d_moff, const uint32_t *d_crc, long n_blocks, uint8_t *d_dense);
+/* ssg_bgzf_deep.cpp: the deflate kernel of levels 7-9 (k_bgzf_deep.h) in the place of ssg_k_bgzf_deflate: the search depth of a level (0: not its level), the bytes of
+ * link scratch for nb blocks, and the launcher, queued on the calling thread's stream; device buffers */
+extern "C" int ssg_bgzf_deep_depth(int level);
+extern "C" size_t ssg_bgzf_deep_scratch(long nb);
+extern "C" int ssg_bgzf_deflate_deep_dev(const uint8_t *d_pay, const uint64_t *d_cut, long nb, uint8_t *d_tmp, uint32_t *d_sym, uint32_t *d_size, uint16_t *d_prev, int depth);
 /* ssg_bgzf_inflate.cpp: the walk of the members' headers on the host (rng[2b], rng[2b + 1]: member b's deflate stream in members[]; out_off[]: the prefix sum of
  * the ISIZEs; SSG_EINVAL with `who' and the member in ssg_last_error()), and the launcher of the inflate and CRC-32 kernels for at most 4096 members, queued on
  * the calling thread's stream; device buffers */

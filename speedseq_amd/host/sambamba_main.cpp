@@ -281,6 +281,16 @@ struct dev_gather_t {
 };
 /* the blocks of a final file are deflated on the device (write_sorted's rule, which SSG_BGZF_DEVICE=0 / 1 overrides) */
 static bool bgzf_device_wanted() { const char *const bd = getenv("SSG_BGZF_DEVICE"); return !(bd && !strcmp(bd, "0")) && (bd || strcmp(ssg_backend(), "emu") != 0) && ssg_device_count() > 0; }
+/* SSG_BGZF_DEVICE_LEVELS=1 (off by default): what is deflated on the device -- the final file, a run's blocks when they go there, the device merge -- is deflated at
+ * the command's level (-l, else SSG_BAM_LEVEL, else 6) through the *_level entry points: 7, 8, 9 are the chained match finder of csrc/k_bgzf_deep.h, up to 6 the same
+ * bytes as without the switch.  `sort' and `merge' set the level once, before anything is written. */
+static int g_bgzf_dev_level = 6; static bool g_bgzf_dev_levels = false;
+static void bgzf_dev_level_set(int level) { const char *const e = getenv("SSG_BGZF_DEVICE_LEVELS"); if (e && *e && strcmp(e, "0")) { g_bgzf_dev_levels = true; g_bgzf_dev_level = level < 0 ? 6 : level > 9 ? 9 : level < 1 ? 1 : level; } }
+/* the end of SSG_SORT_LOG's "blocks deflated on" line with the switch on ("" without it: the line is what it was) */
+static std::string bgzf_dev_level_note() { return !g_bgzf_dev_levels ? std::string() : "; device deflate level " + std::to_string(g_bgzf_dev_level) + (g_bgzf_dev_level >= 7 ? ": chained match finder (k_bgzf_deep.h)" : ": the one parse of levels 1-6 (k_bgzf.h)"); }
+static int dev_bgzf_deflate(const uint8_t *p, const uint64_t *cut, long nb, uint8_t *out, uint64_t cap, uint64_t *off) { return ssg_bgzf_deflate_level(p, cut, nb, out, cap, off, g_bgzf_dev_level); }
+static int dev_bgzf_compress(const uint8_t *p, const uint64_t *cut, long nb, uint8_t *out, uint64_t cap, uint64_t *off, uint32_t *crc) { return ssg_bgzf_compress_level(p, cut, nb, out, cap, off, crc, g_bgzf_dev_level); }
+static int dev_bgzf_compress_recs(ssg_recs_t *r, const uint64_t *cut, long nb, uint8_t *out, uint64_t cap, uint64_t *off, uint32_t *crc) { return ssg_bgzf_compress_recs_level(r, cut, nb, out, cap, off, crc, g_bgzf_dev_level); }
 
 /* the sorted records as a BGZF stream.  Blocks are cut exactly as bgzf_out_t::record cuts them (a record does not straddle blocks
  * unless it is larger than one); the gather of a block's records and its deflate run on the thread pool, groups of blocks are
@@ -473,7 +483,7 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 			if (g0 >= next_write.load(std::memory_order_acquire) + window) { const double t0 = wall(); while (g0 >= next_write.load(std::memory_order_acquire) + window && !dev_failed.load()) nap(200); my_w += (long)((wall() - t0) * 1e6); }
 			if (dev_failed.load()) break;
 			const double t1 = wall();
-			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || ssg_bgzf_compress_recs(recs, &cut[b0], (long)n_b, O, O_cap, off.data(), 0)) {
+			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || dev_bgzf_compress_recs(recs, &cut[b0], (long)n_b, O, O_cap, off.data(), 0)) {
 				fprintf(stderr, "[sambamba] sort: BGZF deflate on the device failed: %s\n", fail_after >= 0 ? "(SSG_BGZF_FAIL_AFTER: test)" : ssg_last_error()); dev_failed = 1; break; }
 			const double t2 = wall();
 			parallel_for((int)std::min<size_t>((size_t)std::min(gth, 8), g1 - g0), g1 - g0, [&](size_t a, size_t e, int) {
@@ -537,7 +547,7 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 			if (st != 1) break;
 			const size_t b0 = sl.b0, n_b = sl.n_b, b1 = b0 + n_b, g0 = b0 / GRP, g1 = (b1 + GRP - 1) / GRP;
 			const double t1 = wall();
-			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || (dev_crc ? ssg_bgzf_compress(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data(), 0) : ssg_bgzf_deflate(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data()))) {
+			if ((fail_after >= 0 && dev_batches.fetch_add(1) >= fail_after) || (dev_crc ? dev_bgzf_compress(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data(), 0) : dev_bgzf_deflate(sl.P, sl.rel.data(), (long)n_b, O, O_cap, off.data()))) {
 				fprintf(stderr, "[sambamba] sort: BGZF deflate on the device failed: %s\n", fail_after >= 0 ? "(SSG_BGZF_FAIL_AFTER: test)" : ssg_last_error()); dev_failed = 1; break; }
 			const double t2 = wall();
 			parallel_for((int)std::min<size_t>((size_t)std::min(gth, 8), g1 - g0), g1 - g0, [&](size_t a, size_t e, int) {
@@ -649,11 +659,11 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	if (dbg() && !seg) fprintf(stderr, "[sambamba] sort: write: offsets and block cuts %.2f s, gather + deflate + write of %zu blocks %.2f s (record view for the index %.2f s, %d workers started in %.2f s; writer: waited %.2f s for blocks, wrote for %.2f s; "
 	                   "per worker: gather %.2f s, deflate %.2f s, held back by the writer's window %.2f s)\n", tw1 - tw0, nb, tw2 - tw1, tw_spawn0 - tw1, n_workers, tw_spawn - tw_spawn0, t_wr_wait, t_wr_io,
 	                   us_gather / 1e6 / std::max(1, n_workers + n_prod), us_deflate / 1e6 / std::max(1, n_workers + n_prod), us_window / 1e6 / std::max(1, n_workers + n_prod));
-	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; %s)%s%s\n", n_devs, n_prod,
+	if (dbg() && use_dev && !seg) fprintf(stderr, "[sambamba] sort: write: blocks deflated on %d device(s) (%d producer threads; %s)%s%s%s\n", n_devs, n_prod,
 	                                    dev_gather ? "`gather' = nothing, `deflate' = gather, deflate, CRC-32 and framing kernels + download: the payload is built in HBM" :
 	                                    dev_crc ? "`gather' = gather on the host, `deflate' = upload + kernels + download: CRC-32 on the device, framing too" : "`gather' = gather + CRC-32 on the host, `deflate' = upload + kernels + download, then framing on the host",
 	                                    host_slots ? (std::string("; ") + std::to_string(host_slots) + " of every " + std::to_string(slot_round) + " batches by the host's pool (zlib)").c_str() : "",
-	                                    dev_gather ? "; gather on the device" : "; gather on the host");
+	                                    dev_gather ? "; gather on the device" : "; gather on the host", bgzf_dev_level_note().c_str());
 	if (seg) seg->coff = coff;
 	if (seg && seg->ent_fd >= 0 && n) {   /* rank mode: what the index of the joined file needs of this stretch */
 		std::vector<uint8_t> eb(24 * n); size_t bk = 0;
@@ -915,6 +925,7 @@ static int cmd_sort(int argc, char **argv)
 	if (threads < 1) threads = 1;
 	const double t_start = wall();
 	{ const char *e = getenv("SSG_BAM_LEVEL"); if (level < 0 && e && *e) level = atoi(e); }   /* deflate level of the sorted file when -l is not given (default: zlib's 6, as sambamba's) */
+	bgzf_dev_level_set(level);
 	/* compression is CPU work the reference's `-t` undersizes on a host with hundreds of cores next to an MI355X: the pool may use more (SSG_SORT_THREADS) */
 	int pool = threads; { const char *e = getenv("SSG_SORT_THREADS"); if (e && atoi(e) > 0) pool = atoi(e); }
 	pool = ssg_pool_threads(pool);
@@ -1485,7 +1496,7 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 			const size_t nb = cut.size() - 1; uint64_t j = 0;
 			for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
 				const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
-				if (ssg_bgzf_compress_recs(S.r, cut.data() + b0, k, obuf, out_cap, boff.data(), 0)) fail(ssg_last_error());
+				if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, obuf, out_cap, boff.data(), 0)) fail(ssg_last_error());
 				io_write_all(ofd, obuf, (size_t)boff[(size_t)k]);
 				/* the index entries of the records that begin in these blocks: an entry closes at the virtual offset of the record behind it */
 				size_t b = b0;
@@ -1528,8 +1539,8 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 	idx.save((std::string(files[0]) + ".bai").c_str());
 	bai_note_write(files[0]);
 	dev_prof_report("merge");
-	if (dbg()) fprintf(stderr, "[sambamba] merge: %llu records of %zu inputs merged on the device in %llu round(s) of at most %llu bytes an input: %llu blocks, %.2f s (after the first load: inflate + scan %.2f s, order %.2f s, gather + deflate + write %.2f s)\n",
-	                   (unsigned long long)n_written, F, (unsigned long long)n_rounds, (unsigned long long)window, (unsigned long long)n_blocks, wall() - t0, t_load, t_sort, t_write);
+	if (dbg()) fprintf(stderr, "[sambamba] merge: %llu records of %zu inputs merged on the device in %llu round(s) of at most %llu bytes an input: %llu blocks, %.2f s (after the first load: inflate + scan %.2f s, order %.2f s, gather + deflate + write %.2f s)%s\n",
+	                   (unsigned long long)n_written, F, (unsigned long long)n_rounds, (unsigned long long)window, (unsigned long long)n_blocks, wall() - t0, t_load, t_sort, t_write, bgzf_dev_level_note().c_str());
 	return true;
 }
 
@@ -1645,6 +1656,7 @@ static int cmd_merge(int argc, char **argv)
 	}
 	if (env_is_1("SSG_MERGE_DEVICE")) {   /* order, gather and deflate on the device, the index written with the file; the host merge below takes over when that cannot be */
 		std::string why;
+		{ int dl = level; const char *e = getenv("SSG_BAM_LEVEL"); if (dl < 0 && e && *e) dl = atoi(e); if (dl != 0) bgzf_dev_level_set(dl); }   /* SSG_BGZF_DEVICE_LEVELS=1: -l, else SSG_BAM_LEVEL, else 6 */
 		if (merge_device(files, src, h, level, threads, why)) return 0;
 		if (dbg()) fprintf(stderr, "[sambamba] merge: device merge off (%s): the inputs are merged on the host\n", why.c_str());
 	}
