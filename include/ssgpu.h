@@ -194,6 +194,27 @@ int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
                        const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req);
 
+/* Test entry of the record stage (row a12: upstream mem_reg2aln -> bwa_gen_cigar2 -> ksw_global2, NM and MD): CIGAR, POS, NM and MD of requests on regions, both given
+ * by the caller instead of the pairing stage's, through the one host function the pipeline's request tail runs -- the gap-free lane kernel, the lane DP in its three
+ * band classes, the wave kernel for what they leave (SSG_R2A_DPLANE=0: for everything with a gap).  Of the index the kernels read the 2-bit reference, l_pac and the
+ * contig table (as ssg_dbg_regions); seq / off[n_reads + 1] are the reads (codes 0 .. 4); regs[n_regs] the regions (rb, re, qb, qe, truesc, w, score, sub, csub,
+ * secondary are read); req[n_req] the requests: read, reg (an index into regs; < 0: the unmapped record), kind, owner, flag, mapq.
+ * Validated first, SSG_EINVAL with a message otherwise: contigs that tile [0, l_pac), offsets from 0 and monotone, codes <= 4, 1 <= read length <= 310,
+ * 0 <= rb < re <= 2 l_pac, no region across l_pac, re - rb <= 32768, read and reg in range, 0 <= qb < qe <= the length of every read the region is requested for, and
+ * the scoring limits of the pipeline (as ssg_dbg_regions; gap open >= 0, gap extend >= 1, open + 32769 x extend < 2^27).
+ * Out: alns[n_req] the records (zeroed first: an unmapped record leaves cigar and md untouched); route[k] (may be NULL), from the lists the kernels leave:
+ * SSG_R2A_ROUTE_LANE the gap-free lane kernel made the record, SSG_R2A_ROUTE_DP0 / DP1 / DP2 the lane DP of band class 0 / 1 / 2 took it, SSG_R2A_ROUTE_WAVE the
+ * wave kernel made it -- a DP class with WAVE is a record the lane DP handed on; 0 for the unmapped record.  *dev_err (may be NULL) = the stage's device error code
+ * (5: the direction matrix exceeds its slab, 6: more than 62 CIGAR operations, 7: an MD of 319 characters or more); when it is not 0 the call returns SSG_EOVERFLOW,
+ * as the pipeline does, with alns and route filled for inspection. */
+#define SSG_R2A_ROUTE_LANE 1
+#define SSG_R2A_ROUTE_DP0  2
+#define SSG_R2A_ROUTE_DP1  4
+#define SSG_R2A_ROUTE_DP2  8
+#define SSG_R2A_ROUTE_WAVE 16
+int ssg_dbg_reg2aln(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
+                    int64_t n_regs, const ssg_alnreg_t *regs, int64_t n_req, const ssg_alnreq_t *req, ssg_aln_t *alns, int32_t *route, int32_t *dev_err);
+
 /* upstream mem_align1_core() (bwamem.c; rows a1-a8) for a batch of reads: SMEM -> SAL -> chain ->
  * filter -> extend -> sort/dedup/patch.  reg_off[n_reads+1] and regs (malloc'd by the library,
  * release with ssg_free) receive each read's mem_alnreg_t list in upstream order. */

@@ -219,6 +219,45 @@ int64_t orc_api_regions(const orc_opt_t *opt, const uint8_t *pac, int64_t l_pac,
 	return tot;
 }
 
+/* The record stage on regions and requests given by the caller (tests/test_record_reference.py; the library's twin is ssg_dbg_reg2aln): orc_mem_reg2aln for every
+ * request, no change of behaviour.  req: 8 int32 a request (read, reg, kind, owner, flag, mapq, 0, 0: the library's ssg_alnreq_t; reg < 0: the unmapped record).
+ * out: records in the library's ssg_aln_t layout, zeroed first; POS, rid, strand, CIGAR, NM, MD, score and sub are upstream's, flag = the request's | 0x100 for a
+ * secondary region, mapq = the request's (mem_reg2sam overwrites mem_reg2aln's), reg_idx = owner, _pad = kind.  Upstream's record has no capacity: a CIGAR of more
+ * than 64 operations or an MD of more than 319 characters is cut to the layout and counted in the return value; over[k] (may be NULL) = 1 for such a record.
+ * The caller validates as ssg_dbg_reg2aln does: orc_mem_reg2aln trusts its region. */
+typedef struct { int64_t pos; int32_t rid, flag, mapq, NM, score, sub, n_cigar, is_rev, l_md, reg_idx, xa_cnt, _pad; uint32_t cigar[64]; char md[320]; } orc_flataln_t;
+int64_t orc_api_reg2aln(const orc_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq,
+                        const int64_t *off, int64_t n_regs, const orc_flatreg_t *regs, int64_t n_req, const int32_t *req, orc_flataln_t *out, uint8_t *over)
+{
+	orc_bns_t bns; orc_idx_t idx;
+	int64_t n_over = 0;
+	memset(&bns, 0, sizeof(bns)); memset(&idx, 0, sizeof(idx));
+	bns.l_pac = l_pac; bns.n_seqs = n_ctg; bns.anns = calloc((size_t)n_ctg, sizeof(orc_ann_t));
+	for (int c = 0; c < n_ctg; ++c) { bns.anns[c].offset = ctg_off[c]; bns.anns[c].len = ctg_len[c]; }
+	idx.bns = &bns; idx.pac = (uint8_t*)pac;
+	for (int64_t k = 0; k < n_req; ++k) {
+		const int32_t *q = req + 8 * k;
+		orc_flataln_t *o = &out[k];
+		memset(o, 0, sizeof(*o));
+		if (over) over[k] = 0;
+		if (q[1] < 0) { o->pos = -1; o->rid = -1; o->flag = q[4] | 0x4; o->reg_idx = -1; continue; }
+		orc_alnreg_t ar;
+		unflatten(&regs[q[1]], &ar);
+		const int len = (int)(off[q[0] + 1] - off[q[0]]);
+		orc_aln_t a = orc_mem_reg2aln(opt, &idx, len, seq + off[q[0]], &ar);
+		const char *md = (const char*)(a.cigar + a.n_cigar);
+		const int l_md = (int)strlen(md);
+		o->pos = a.pos; o->rid = a.rid; o->flag = q[4] | (a.flag & 0x100); o->mapq = q[5]; o->NM = (int32_t)a.NM; o->score = a.score; o->sub = a.sub;
+		o->n_cigar = a.n_cigar; o->is_rev = a.is_rev; o->l_md = l_md; o->reg_idx = q[3]; o->xa_cnt = 0; o->_pad = q[2];
+		memcpy(o->cigar, a.cigar, 4 * (size_t)(a.n_cigar < 64 ? a.n_cigar : 64));
+		memcpy(o->md, md, (size_t)(l_md < 319 ? l_md : 319));
+		if (a.n_cigar > 64 || l_md > 319) { ++n_over; if (over) over[k] = 1; }
+		free(a.cigar);
+	}
+	free(bns.anns);
+	return n_over;
+}
+
 /* ksw_global2 with the CIGAR copied out */
 int orc_api_global2(const orc_opt_t *opt, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int w, int *n_cigar, uint32_t *cigar, int cap)
 {

@@ -35,6 +35,8 @@ CHAIN_FORM_WAVE256, CHAIN_FORM_WAVE512, CHAIN_FORM_WAVE1024, CHAIN_FORM_WAVE2048
 CHAIN_FORM_TREE = 0x10
 # ssg_dbg_regions' route[] bits (include/ssgpu.h SSG_REG_ROUTE_*)
 REG_ROUTE_WAVE, REG_ROUTE_PATCH = 1, 2
+# ssg_dbg_reg2aln's route[] bits (include/ssgpu.h SSG_R2A_ROUTE_*)
+R2A_ROUTE_LANE, R2A_ROUTE_DP0, R2A_ROUTE_DP1, R2A_ROUTE_DP2, R2A_ROUTE_WAVE = 1, 2, 4, 8, 16
 EXT_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("w", "i4"), ("end_bonus", "i4"), ("zdrop", "i4"), ("h0", "i4")])
 EXT_RES_DT = np.dtype([("score", "i4"), ("qle", "i4"), ("tle", "i4"), ("gtle", "i4"), ("gscore", "i4"), ("max_off", "i4")])
 SW_JOB_DT = np.dtype([("qoff", "i4"), ("qlen", "i4"), ("toff", "i4"), ("tlen", "i4"), ("xtra", "i4"), ("_pad", "i4")])
@@ -229,6 +231,25 @@ class Lib:
         regs = np.frombuffer((C.c_char * (tot * ALNREG_DT.itemsize)).from_address(rp.value), dtype=ALNREG_DT, count=tot).copy() if tot else np.zeros(0, ALNREG_DT)
         self.l.ssg_free(rp)
         return reg_off, regs, route
+
+    def dbg_reg2aln(self, opt, pac, l_pac, ctg_off, ctg_len, seq, off, regs, req):
+        """the record stage on given regions and requests (ssg_dbg_reg2aln): (return code, records [ALN_DT], route per request [R2A_ROUTE_* bits], the stage's device
+        error code).  The return code is 0 or SSG_EOVERFLOW (-75: the device error code is not 0); every other code raises."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        ctg_off = np.ascontiguousarray(ctg_off, dtype=np.int64)
+        ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        req = np.ascontiguousarray(req, dtype=ALNREQ_DT)
+        n = len(off) - 1
+        assert len(pac) >= l_pac // 4 + 1 and len(ctg_off) == len(ctg_len) and n >= 0 and (n == 0 or len(seq) >= off[-1])
+        alns, route, err = np.zeros(len(req) + 1, dtype=ALN_DT), np.zeros(len(req) + 1, dtype=np.int32), C.c_int32(0)
+        rc = self.l.ssg_dbg_reg2aln(_ptr(opt), _ptr(pac), C.c_int64(l_pac), C.c_int(len(ctg_off)), _ptr(ctg_off), _ptr(ctg_len), C.c_int(n), _ptr(seq), _ptr(off),
+                                    C.c_int64(len(regs)), _ptr(regs), C.c_int64(len(req)), _ptr(req), _ptr(alns), _ptr(route), C.byref(err))
+        if rc != -75:
+            self._chk(rc)
+        return rc, alns[:len(req)], route[:len(req)], int(err.value)
 
     def dbg_pestat(self, idx, opt, reg_off, regs, pair_batch, n_batches):
         """mem_pestat on given region lists (ssg_dbg_pestat): n_batches x 4 insert-size models"""

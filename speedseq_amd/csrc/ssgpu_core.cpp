@@ -873,6 +873,24 @@ static int check_band(const ssg_mem_opt_t *opt)
 	if (opt->w < 0 || opt->w > 65535) { ssg_err_msg = "band width (-w) outside 0 .. 65535: beyond the 16-bit band field of the region keys"; return SSG_EINVAL; }
 	return 0;
 }
+/* The CIGAR stage's wave kernel (k_aln.h, k_sw.h) keeps its cells in 32 bits with minus infinity at -2^30: a gap as long as the longest window (SSG_TWIN_GLB rows) must
+ * stay far above it.  An extension penalty of 0 is refused with it: upstream divides by it (the band's cap).  Checked before the seeding stage of a pipeline call
+ * (run_align1), and in run_reg2aln for callers that enter there. */
+static int check_gap_penalties(const ssg_mem_opt_t *opt)
+{
+	if (opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 1 || opt->e_ins < 1 || std::max((long)opt->o_del, (long)opt->o_ins) + (long)std::max(opt->e_del, opt->e_ins) * (SSG_TWIN_GLB + 1) >= 1L << 27) {
+		ssg_err_msg = "gap penalties outside the range of the CIGAR kernels: need open >= 0, extend >= 1, open + 32769 x extend < 2^27"; return SSG_EINVAL; }
+	return 0;
+}
+/* The scoring limits of the extension kernels for reads of up to max_len bases: the 13-bit cells (the product in 64 bits, so that no a overflows it), then the 6-bit
+ * score table -- in that order, the order of the messages callers have always met (-A 40 is told of the DP cells).  run_regions, where there is a job, and the test
+ * entries, whatever their input. */
+static int check_scores(const ssg_mem_opt_t *opt, int max_len)
+{
+	if ((long)opt->a * 2 * max_len + 64 >= 8191) { ssg_err_msg = "match score x read length beyond the 13-bit DP cells of the extension kernel"; return SSG_EINVAL; }
+	if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
+	return 0;
+}
 
 /* The region stage (upstream mem_chain2aln per chain, then mem_sort_dedup_patch with mem_patch_reg; rows a6-a8) of a batch whose chains are laid out as run_chain
  * leaves them: per read a slice that starts at seed_off[r] in d_chains / d_order (the surviving chains' ids, n_chain[r] of them) and in d_cseeds (the chains' seed
@@ -899,10 +917,9 @@ static int run_regions(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int
 	dbuf<uint64_t> d_kl((size_t)n_jobs + 1), d_kr((size_t)n_jobs + 1), d_sl((size_t)n_jobs + 1), d_sr((size_t)n_jobs + 1);
 	CHKA(d_xjobs); CHKA(d_xl); CHKA(d_xr); CHKA(d_kl); CHKA(d_kr); CHKA(d_sl); CHKA(d_sr);
 	if (n_jobs > 0) {
-		if (opt->a * 2 * max_len + 64 >= 8191) { ssg_err_msg = "match score x read length beyond the 13-bit DP cells of the extension kernel"; return SSG_EINVAL; }
+		CHK(check_scores(opt, max_len));
 		if (opt->min_chain_weight > 0 && 2.8f * (float)opt->min_chain_weight <= 0.05f * (float)max_len) {   /* upstream mem_flt_chained_seeds would run (MEM_HSP_COEF x W <= MEM_SEEDSW_COEF x l): its seed-level SW is not built */
 			ssg_err_msg = "-W this small against this read length turns on upstream's chained-seed filter (long-read path), which this build does not have"; return SSG_EINVAL; }
-		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
 		SSG_LAUNCH(ssg_k_ext_prep, (n_jobs + 255) / 256, 256, 0, ix, *opt, n_reads, n_jobs, d_off, o.seed_off.p, d_seeds_p, d_chains_p, d_order_p, d_cseeds_p,
 		           d_choff.p, d_seq, (int)SSG_TWIN_GLB, d_xjobs.p, d_kl.p, d_kr.p);
 		CHK(prim_sort_keys(d_kl.p, d_sl.p, n_jobs, 32, 50)); CHK(prim_sort_keys(d_kr.p, d_sr.p, n_jobs, 32, 50));   /* 9 + 9 bits: 511 - side length, 511 - expected rows */
@@ -985,7 +1002,7 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	 * read length: at len / 2 (until round 6) one batch in three or four of the 1 M-pair bench met a read beyond it and paid the one-lane kernel of
 	 * the slow path (24-36 ms with the chip idle) plus a second run of the whole seeding stage (44-52 ms) -- profiles/r05_kernel_stats.csv shows the
 	 * fourth ssg_k_smem2 launch in three steps; only the entries a read has are ever touched, so the width costs HBM (12 GB per million pairs), not time */
-	CHK(check_band(opt));   /* (refused before the seeding stage runs, not after it) */
+	CHK(check_band(opt)); CHK(check_gap_penalties(opt));   /* (refused before the seeding stage runs, not after it) */
 	static std::atomic<int> learned_cap(0);
 	int cap = std::max(std::max(96, (max_len * 5 / 4 + 31) / 32 * 32), learned_cap.load());
 	{ const int e = env_int("SSG_SMEM_CAP", 0); if (e > 0) cap = e; }   /* tests: a narrow layout walks the widening path */
@@ -1217,8 +1234,7 @@ int ssg_dbg_regions(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac,
 		}
 	}
 	if (!bad) {   /* the scoring limits of the pipeline, whatever the chains: run_regions checks them only where there is a job */
-		if (opt->a * 2 * max_len + 64 >= 8191) { ssg_err_msg = "match score x read length beyond the 13-bit DP cells of the extension kernel"; return SSG_EINVAL; }
-		if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
+		CHK(check_scores(opt, max_len));
 		if (opt->e_del < 1 || opt->e_ins < 1) { ssg_err_msg = "ssg_dbg_regions: gap extension penalties must be positive"; return SSG_EINVAL; }
 	}
 	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_regions: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
@@ -1363,9 +1379,23 @@ static thread_local unsigned int ssg_r2a_last[1 + SSG_R2D_CLASSES];   /* of this
 /* CIGAR / NM / MD of the compacted requests (k_aln.h): gap-free records one lane each; records whose band is narrow one lane each through the DP (three classes of
  * band width, a launch each with the LDS that class needs, side by side); the rest -- wide bands, and records whose first alignment does not end upstream's
  * loop -- one wave each.  SSG_R2A_DPLANE=0: no lane DP (A/B, tests). */
-static int run_reg2aln(const ssg_index *idx, const ssg_mem_opt_t *opt, int64_t nreq, const ssg_alnreq_t *d_creq, const ssg_alnreg_t *d_regs, const uint8_t *d_seq, const int64_t *d_off,
-                       ssg_aln_t *d_alns, int32_t *d_gerr, unsigned long long *d_cnt, int max_len)
+struct r2a_lists_t { std::vector<int32_t> dp[SSG_R2D_CLASSES], todo; };   /* what the kernels left of one call: the lane DP's lists by class, the wave kernel's list */
+/* The lane DP keeps h and e in 16 bits with "minus infinity" at SSG_R2D_NEG.  Its comparisons come out as upstream's while every value of a reachable cell, and every
+ * gap-opening candidate made of one, lies above everything derived from minus infinity (at most SSG_R2D_NEG + a); what is stored then stays above -32768 as well.  A
+ * reachable in-band H is at least the score of the path "down the main diagonal, then one gap of |i - j| <= 33": -(b' min(i, j) + o + 33 e) with b' = max(b, 1) (an N
+ * scores -1); M is one b' lower; a gap cell is an M one opening and at most 65 extensions lower (a column stays in the band for 2 w + 1 <= 65 rows), a candidate one
+ * opening below an M.  Scoring outside this bound goes to the wave kernel, whose cells are 32 bits: the same records (tests/test_record_reference.py, cell_range). */
+static bool r2a_dplane_in_range(const ssg_mem_opt_t *opt, int max_len)
 {
+	const long bm = std::max(opt->b, 1), n = (long)max_len + 32 + 1, om = std::max(opt->o_del, opt->o_ins), em = std::max(opt->e_del, opt->e_ins);
+	const long oe = std::max((long)opt->o_del + opt->e_del, (long)opt->o_ins + opt->e_ins);
+	if (opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 0 || opt->e_ins < 0 || opt->a < 0 || opt->b < 0) return false;
+	return bm * n + om + 33 * em + 2 * oe + 66 * em + opt->a < -(long)SSG_R2D_NEG && (long)opt->a * n < 32767;
+}
+static int run_reg2aln(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int64_t nreq, const ssg_alnreq_t *d_creq, const ssg_alnreg_t *d_regs, const uint8_t *d_seq, const int64_t *d_off,
+                       ssg_aln_t *d_alns, int32_t *d_gerr, unsigned long long *d_cnt, int max_len, r2a_lists_t *lists = 0)
+{
+	CHK(check_gap_penalties(opt));
 	const int wpb = SSG_WAVES_PER_WG;
 	long nwg = std::min<long>(((long)nreq + wpb - 1) / wpb, SSG_MAX_RESIDENT_WG);
 	long nw = nwg * wpb;
@@ -1373,10 +1403,10 @@ static int run_reg2aln(const ssg_index *idx, const ssg_mem_opt_t *opt, int64_t n
 	CHKA(d_tglb); CHKA(d_z);
 	dbuf<int32_t> d_rtodo((size_t)nreq + 1); dbuf<unsigned int> d_nrtodo(1 + SSG_R2D_CLASSES);
 	CHKA(d_rtodo); CHKA(d_nrtodo); CHK(d_nrtodo.zero());
-	const bool dplane = env_int("SSG_R2A_DPLANE", 1) != 0 && max_len <= SSG_ALN_QLDS;
+	const bool dplane = env_int("SSG_R2A_DPLANE", 1) != 0 && max_len <= SSG_ALN_QLDS && r2a_dplane_in_range(opt, max_len);
 	dbuf<int32_t> d_dpl(dplane ? (size_t)nreq * SSG_R2D_CLASSES + 1 : 1);
 	CHKA(d_dpl);
-	SSG_LAUNCH(ssg_k_reg2aln_lane, (nreq + 63) / 64, 64, 0, idx->v, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_gerr, d_rtodo.p, d_nrtodo.p,
+	SSG_LAUNCH(ssg_k_reg2aln_lane, (nreq + 63) / 64, 64, 0, ix, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_gerr, d_rtodo.p, d_nrtodo.p,
 	           dplane ? d_dpl.p : (int32_t*)0, d_nrtodo.p + 1);
 	if (dplane) {
 		const int qwords = (max_len + 7) / 8, zrows = max_len + 32;
@@ -1389,24 +1419,102 @@ static int run_reg2aln(const ssg_index *idx, const ssg_mem_opt_t *opt, int64_t n
 		for (int c = SSG_R2D_CLASSES - 1; c >= 0; --c) {   /* widest class first */
 			const int wm = c == 0 ? 8 : c == 1 ? 16 : 32, zw = (2 * wm + 1 + 7) / 8;
 			const size_t lds = (size_t)(2 * wm + 2 + qwords) * 256;
-#define SSG_R2D_GO(LAUNCH, ...) LAUNCH(__VA_ARGS__ ssg_k_reg2aln_dplane, G, 64, lds, idx->v, *opt, d_dpl.p + (size_t)c * nreq, d_nrtodo.p + 1 + c, d_creq, d_regs, d_seq, d_off, d_alns, \
+#define SSG_R2D_GO(LAUNCH, ...) LAUNCH(__VA_ARGS__ ssg_k_reg2aln_dplane, G, 64, lds, ix, *opt, d_dpl.p + (size_t)c * nreq, d_nrtodo.p + 1 + c, d_creq, d_regs, d_seq, d_off, d_alns, \
                                        d_zs.p + zoff[c], wm, qwords, zw, zrows, d_gerr, d_cnt, d_rtodo.p, d_nrtodo.p)
 			if (c == 2) SSG_R2D_GO(SSG_LAUNCH); else if (c == 1) SSG_R2D_GO(SSG_LAUNCH_ON, 0,); else SSG_R2D_GO(SSG_LAUNCH_ON, 1,);
 #undef SSG_R2D_GO
 		}
 		ssg_join(2);
-		SSG_LAUNCH_W(max_len > 255, ssg_k_reg2aln, nwg, wpb * 64, 0, idx->v, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_tglb.p, d_z.p, d_gerr, d_cnt, d_rtodo.p, d_nrtodo.p);
+		SSG_LAUNCH_W(max_len > 255, ssg_k_reg2aln, nwg, wpb * 64, 0, ix, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_tglb.p, d_z.p, d_gerr, d_cnt, d_rtodo.p, d_nrtodo.p);
 		CHK(rt_sync());   /* (before the slabs go back to the arena) */
 		CHK(d_nrtodo.down(ssg_r2a_last, 1 + SSG_R2D_CLASSES));
 		if (ssg_debug()) fprintf(stderr, "[ssgpu] reg2aln: %lld requests; lane DP by band class %u / %u / %u, wave kernel %u\n", (long long)nreq, ssg_r2a_last[1], ssg_r2a_last[2], ssg_r2a_last[3], ssg_r2a_last[0]);
+		if (lists) {
+			for (int c = 0; c < SSG_R2D_CLASSES; ++c) { lists->dp[c].resize(ssg_r2a_last[1 + c]); if (ssg_r2a_last[1 + c]) CHK(rt_d2h(lists->dp[c].data(), d_dpl.p + (size_t)c * nreq, (size_t)ssg_r2a_last[1 + c] * sizeof(int32_t))); }
+			lists->todo.resize(ssg_r2a_last[0]); if (ssg_r2a_last[0]) CHK(d_rtodo.down(lists->todo.data(), ssg_r2a_last[0]));
+		}
 		return 0;
 	}
-	SSG_LAUNCH_W(max_len > 255, ssg_k_reg2aln, nwg, wpb * 64, 0, idx->v, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_tglb.p, d_z.p, d_gerr, d_cnt, d_rtodo.p, d_nrtodo.p);
+	SSG_LAUNCH_W(max_len > 255, ssg_k_reg2aln, nwg, wpb * 64, 0, ix, *opt, (long)nreq, d_creq, d_regs, d_seq, d_off, d_alns, d_tglb.p, d_z.p, d_gerr, d_cnt, d_rtodo.p, d_nrtodo.p);
 	CHK(rt_sync());
+	if (lists) {
+		unsigned int nt = 0;
+		CHK(d_nrtodo.down(&nt, 1));
+		for (int c = 0; c < SSG_R2D_CLASSES; ++c) lists->dp[c].clear();
+		lists->todo.resize(nt); if (nt) CHK(d_rtodo.down(lists->todo.data(), nt));
+	}
 	return 0;
 }
 
 extern "C" void ssg_dbg_reg2aln_counts(unsigned int out[4]) { for (int k = 0; k < 1 + SSG_R2D_CLASSES; ++k) out[k] = ssg_r2a_last[k]; }
+
+/* test entry: CIGAR / POS / NM / MD of the caller's requests on the caller's regions (include/ssgpu.h), through run_reg2aln as run_req_tail goes through it */
+extern "C" int ssg_dbg_reg2aln(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
+                               int64_t n_regs, const ssg_alnreg_t *regs, int64_t n_req, const ssg_alnreq_t *req, ssg_aln_t *alns, int32_t *route, int32_t *dev_err)
+{
+	static thread_local char msg[200];
+	CHK(ssg_need_device());
+	if (dev_err) *dev_err = 0;
+	if (n_reads < 0 || n_regs < 0 || n_req < 0 || n_req >= (int64_t)1 << 31 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) {
+		ssg_err_msg = "ssg_dbg_reg2aln: need n_reads, n_regs >= 0, 0 <= n_req < 2^31, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
+	for (int c = 0; c < n_ctg; ++c)
+		if (ctg_len[c] < 1 || ctg_off[c] != (c ? ctg_off[c - 1] + ctg_len[c - 1] : 0) || ctg_off[c] + ctg_len[c] > l_pac || (c == n_ctg - 1 && ctg_off[c] + ctg_len[c] != l_pac)) {
+			ssg_err_msg = "ssg_dbg_reg2aln: the contigs must tile [0, l_pac) in order"; return SSG_EINVAL; }
+	if (n_req == 0) return SSG_OK;
+	const char *bad = 0; long at = 0;
+	int max_len = 0;
+	if (n_reads < 1) bad = "requests need reads: request";
+	else if (off[0] != 0) bad = "offsets start at 0: read";
+	for (int r = 0; !bad && r < n_reads; ++r) {
+		at = r;
+		if (off[r + 1] < off[r]) { bad = "offsets must not decrease: read"; break; }
+		const int64_t len64 = off[r + 1] - off[r];
+		if (len64 < 1 || len64 > SSG_MAX_READ_LEN) { bad = "need 1 <= read length <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
+		max_len = std::max(max_len, (int)len64);
+		for (int64_t k = off[r]; k < off[r + 1]; ++k) if (seq[k] > 4) { bad = "read codes are 0 .. 4: read"; break; }
+	}
+	for (int64_t k = 0; !bad && k < n_regs; ++k) {
+		const ssg_alnreg_t &a = regs[k];
+		at = (long)k;
+		if (!(0 <= a.rb && a.rb < a.re && a.re <= 2 * l_pac)) bad = "need 0 <= rb < re <= 2 l_pac: region";
+		else if (a.rb < l_pac && a.re > l_pac) bad = "a region must not cross the forward / reverse boundary l_pac: region";
+		else if (a.re - a.rb > SSG_TWIN_GLB) bad = "need re - rb <= 32768: region";
+		else if (!(0 <= a.qb && a.qb < a.qe && a.qe <= SSG_MAX_READ_LEN)) bad = "need 0 <= qb < qe <= read length: region";
+	}
+	for (int64_t k = 0; !bad && k < n_req; ++k) {
+		const ssg_alnreq_t &q = req[k];
+		at = (long)k;
+		if (q.read < 0 || q.read >= n_reads) bad = "read index out of range: request";
+		else if (q.reg >= n_regs) bad = "region index out of range: request";
+		else if (q.kind != SSG_REQ_MAIN && q.kind != SSG_REQ_XA) bad = "kind is SSG_REQ_MAIN or SSG_REQ_XA: request";
+		else if (q.reg >= 0 && regs[q.reg].qe > off[q.read + 1] - off[q.read]) bad = "need 0 <= qb < qe <= read length for the request's region and read: request";
+	}
+	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_reg2aln: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
+	/* the scoring limits of the pipeline (the functions run_align1, run_regions and run_reg2aln call), whatever the requests */
+	CHK(check_band(opt)); CHK(check_scores(opt, max_len)); CHK(check_gap_penalties(opt));
+	const size_t pac_bytes = (size_t)(l_pac / 4 + 1);
+	dbuf<uint8_t> d_pac(pac_bytes), d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_coff((size_t)n_ctg), d_off((size_t)n_reads + 1); dbuf<int32_t> d_clen((size_t)n_ctg), d_gerr(1);
+	dbuf<ssg_alnreg_t> d_regs((size_t)n_regs + 1); dbuf<ssg_alnreq_t> d_req((size_t)n_req + 1); dbuf<ssg_aln_t> d_alns((size_t)n_req + 1); dbuf<unsigned long long> d_cnt(3);
+	CHKA(d_pac); CHKA(d_seq); CHKA(d_coff); CHKA(d_off); CHKA(d_clen); CHKA(d_gerr); CHKA(d_regs); CHKA(d_req); CHKA(d_alns); CHKA(d_cnt);
+	CHK(d_pac.up(pac, pac_bytes)); CHK(d_seq.up(seq, (size_t)off[n_reads])); CHK(d_coff.up(ctg_off, (size_t)n_ctg)); CHK(d_clen.up(ctg_len, (size_t)n_ctg)); CHK(d_off.up(off, (size_t)n_reads + 1));
+	if (n_regs) CHK(d_regs.up(regs, (size_t)n_regs));
+	CHK(d_req.up(req, (size_t)n_req)); CHK(d_alns.zero()); CHK(d_gerr.zero()); CHK(d_cnt.zero());
+	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
+	ix.pac = d_pac.p; ix.ctg_off = d_coff.p; ix.ctg_len = d_clen.p; ix.l_pac = l_pac; ix.n_ctg = n_ctg;
+	r2a_lists_t lists;
+	CHK(run_reg2aln(ix, opt, n_req, d_req.p, d_regs.p, d_seq.p, d_off.p, d_alns.p, d_gerr.p, d_cnt.p, max_len, &lists));
+	int32_t ge = 0;
+	CHK(d_gerr.down(&ge, 1));
+	if (dev_err) *dev_err = ge;
+	CHK(d_alns.down(alns, (size_t)n_req));
+	if (route) {
+		for (int64_t k = 0; k < n_req; ++k) route[k] = req[k].reg >= 0 ? SSG_R2A_ROUTE_LANE : 0;
+		for (int c = 0; c < SSG_R2D_CLASSES; ++c) for (int32_t g : lists.dp[c]) if (g >= 0 && g < n_req) route[g] = SSG_R2A_ROUTE_DP0 << c;
+		for (int32_t g : lists.todo) if (g >= 0 && g < n_req) route[g] = (route[g] & ~SSG_R2A_ROUTE_LANE) | SSG_R2A_ROUTE_WAVE;
+	}
+	if (ge) { snprintf(msg, sizeof(msg), "CIGAR generation exceeded an on-device capacity (code %d)", ge); ssg_err_msg = msg; return SSG_EOVERFLOW; }
+	return SSG_OK;
+}
 
 /* mem_sam_pe after mate rescue, for all pairs: primary marking, pairing, MAPQ, record selection (k_pair.h, k_pairw.h), on the region slices reg_off (t2 slots in
  * all) and request slices req_off that ssg_k_pair_caps sized; pair_key = the pairs' region counts, pair_order = the pairs heaviest first, err zeroed by the caller.
@@ -1581,7 +1689,7 @@ static int run_req_tail(int n_reads, const int64_t *d_reqoff, const ssg_alnreq_t
 	if (!a) return 0;
 	dbuf<int32_t> d_gerr(1);
 	CHKA(d_gerr); CHK(d_gerr.zero());
-	CHK(run_reg2aln(a->idx, a->opt, t.n_req, t.req.p, a->d_regs, a->d_seq, a->d_off, t.alns.p, d_gerr.p, a->d_cnt, a->max_len));
+	CHK(run_reg2aln(a->idx->v, a->opt, t.n_req, t.req.p, a->d_regs, a->d_seq, a->d_off, t.alns.p, d_gerr.p, a->d_cnt, a->max_len));
 	STAGE("reg2aln");
 	{ int32_t ge; CHK(d_gerr.down(&ge, 1)); if (ge) { char b[96]; snprintf(b, sizeof(b), "CIGAR generation exceeded an on-device capacity (code %d)", ge); ssg_err_msg = b; return SSG_EOVERFLOW; } }
 	{ unsigned long long c[2]; CHK(rt_d2h(c, a->d_cnt, sizeof(c))); a->stats[2] = c[0]; a->stats[3] = c[1]; a->stats[4] = (uint64_t)t.n_req; }

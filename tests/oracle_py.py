@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from speedseq_amd.capi import ALNREG_DT, INTV_DT
+from speedseq_amd.capi import ALN_DT, ALNREG_DT, ALNREQ_DT, INTV_DT
 
 
 def _ptr(a):
@@ -163,6 +163,24 @@ class Oracle:
         pes = np.zeros(4 * n_batches, dtype=PESTAT_DT)
         self.l.orc_api_pestat(opt or self.opt, idx, C.c_int((len(reg_off) - 1) // 2), _ptr(reg_off), _ptr(regs), _ptr(pair_batch), C.c_int(n_batches), _ptr(pes))
         return pes
+
+    def reg2aln(self, pac, l_pac, ctg_off, ctg_len, seq, off, regs, req, opt=None):
+        """the record stage on given regions [ALNREG_DT] and requests [ALNREQ_DT] (orc_api_reg2aln): (records [ALN_DT], per record 1 where upstream's CIGAR or MD
+        is beyond the layout's capacity and was cut).  The caller validates: orc_mem_reg2aln trusts its region."""
+        pac = np.ascontiguousarray(pac, dtype=np.uint8)
+        ctg_off = np.ascontiguousarray(ctg_off, dtype=np.int64)
+        ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        req = np.ascontiguousarray(req, dtype=ALNREQ_DT)
+        assert len(pac) >= l_pac // 4 + 1 and len(seq) >= off[-1]
+        assert all(0 <= int(r["read"]) < len(off) - 1 and int(r["reg"]) < len(regs) for r in req)
+        out, over = np.zeros(len(req) + 1, dtype=ALN_DT), np.zeros(len(req) + 1, dtype=np.uint8)
+        self.l.orc_api_reg2aln.restype = C.c_int64
+        self.l.orc_api_reg2aln(opt or self.opt, _ptr(pac), C.c_int64(l_pac), C.c_int(len(ctg_off)), _ptr(ctg_off), _ptr(ctg_len), C.c_int(len(off) - 1), _ptr(seq), _ptr(off),
+                               C.c_int64(len(regs)), _ptr(regs), C.c_int64(len(req)), _ptr(req), _ptr(out), _ptr(over))
+        return out[:len(req)], over[:len(req)]
 
     def pair_final(self, idx, id0, reg_off, regs, pes, opt=None):
         """primary marking, pairing and mem_sam_pe's decision on given region lists: (regions as the stage leaves them, req_off, records as
