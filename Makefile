@@ -13,7 +13,7 @@ lib: speedseq_amd/libssgpu.so
 # Every object's prerequisites come from the compiler (-MMD): no hand-kept header lists, so no object can be stale against a shared
 # declaration (round 3 shipped variant libraries linked from objects of different ages).
 # the translation units hipcc compiles (sam_format.cpp is plain C++)
-UNITS   = ssgpu_core ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_msw_replay ssg_bam ssg_coll
+UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_msw_replay ssg_bam ssg_coll
 HIPOBJS = $(UNITS:%=$(CSRC)/%.o)
 HIPSRCS = $(UNITS:%=$(CSRC)/%.cpp)
 $(HIPOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp

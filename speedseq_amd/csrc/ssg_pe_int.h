@@ -1,6 +1,7 @@
 /*
  * ssg_pe_int.h -- what the translation units of libssgpu share about a call of the paired-end hot path: the host result, the result kept in
- * HBM, and the entry points of ssgpu_core.cpp that ssg_bam.cpp (k_bam.h: FASTQ text in, BAM record bytes out) builds on.
+ * HBM, and the entry points of ssgpu_core.cpp that ssg_bam.cpp (k_bam.h: FASTQ text in, BAM record bytes out) builds on.  (What the stage test entries of
+ * ssg_dbg.cpp need of the core on top of this -- the stage runners and their types -- is in ssg_stage_int.h.)
  */
 #ifndef SSG_PE_INT_H
 #define SSG_PE_INT_H

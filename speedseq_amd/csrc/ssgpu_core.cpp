@@ -7,6 +7,8 @@
  * Per-read variable-length outputs are placed by prefix sums over per-read counts; fixed-capacity
  * stages report overflow and the affected reads are re-run with a larger capacity -- nothing is
  * dropped silently and nothing falls back to the CPU.
+ * The test entries that feed one stage the caller's lists (ssg_dbg_chain ... ssg_dbg_matesw) are in ssg_dbg.cpp; they come through the stage runners here
+ * (ssg_stage_int.h).  No kernel leaves or joins this unit with them: its kernels' machine code is pinned (tools/isa_pin.py).
  */
 #include <vector>
 #include <memory>
@@ -30,6 +32,7 @@
 #include "../../include/ssgpu.h"
 #include "ssg_index_int.h"
 #include "ssg_pe_int.h"
+#include "ssg_stage_int.h"
 #include "ssg_prim.h"
 
 thread_local std::string ssg_err_msg;
@@ -46,9 +49,7 @@ thread_local std::vector<ssg_prof_rec> ssg_prof_pending;
 /* wave-per-item kernels are grid-strided over at most this many 4-wave workgroups (256 CUs x 4),
  * so per-wave scratch slabs are sized by residency, not by batch size */
 #define SSG_MAX_RESIDENT_WG 1024
-/* longest read the DP kernels are laid out for (LDS rows, 8-bit columns): SSG_MAX_READ_LEN, ssg_pe_int.h */
-#define SSG_STR_(x) #x
-#define SSG_STR(x) SSG_STR_(x)
+/* longest read the DP kernels are laid out for (LDS rows, 8-bit columns): SSG_MAX_READ_LEN, ssg_pe_int.h (SSG_STR, for the messages: ssg_stage_int.h) */
 
 
 /* the instance of a kernel templated on WIDE (k_sw.h): the one with the fifth register column only for a batch that has a read above 255 bases */
@@ -59,13 +60,13 @@ static double ssg_stage_ms() { static thread_local std::chrono::steady_clock::ti
 #define STAGE(name) do { if (ssg_debug()) { int rc_ = rt_sync(); fprintf(stderr, "[ssgpu] stage %s done rc=%d  +%.1f ms\n", name, rc_, ssg_stage_ms()); fflush(stderr); if (rc_) return rc_; } } while (0)
 
 SSG_ABI_FP_DEFINE(core)
-extern "C" void ssg_abi_fp_index_build(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_seed(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_sam_format(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bam(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_coll(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf_frame(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_rec_gather(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_msw_replay(ssg_abi_fp_t*);
+extern "C" void ssg_abi_fp_index_build(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_seed(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_sam_format(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bam(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_coll(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_bgzf_frame(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_rec_gather(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_msw_replay(ssg_abi_fp_t*); extern "C" void ssg_abi_fp_dbg(ssg_abi_fp_t*);
 extern "C" int ssg_abi_selfcheck(void)
 {	/* every translation unit of the library was compiled against the same shared declarations (ssg_index_int.h) */
 	static const char *const field[20] = { "sizeof(ssg_index_view_t)", "sizeof(ssg_mem_opt_t)", "sizeof(ssg_index)", "sizeof(ssg_intv_t)", "ssg_index_view_t.primary", "ssg_index_view_t.L2",
 		"ssg_index_view_t.l_pac", "ssg_index_view_t.sa_intv", "ssg_mem_opt_t.min_seed_len", "ssg_mem_opt_t.split_width", "ssg_mem_opt_t.max_mem_intv", "ssg_mem_opt_t.split_factor", "ssg_mem_opt_t.mat",
 		"ssg_index.bwt", "ssg_index.ktab", "ssg_index.bwt_words", "ssg_index.names", "sizeof(ssg_seed_t)", "sizeof(ssg_alnreg_t)", "sizeof(ssg_aln_t)" };
-	struct { const char *unit; void (*fn)(ssg_abi_fp_t*); } const units[] = { { "ssg_index_build", ssg_abi_fp_index_build }, { "ssg_seed", ssg_abi_fp_seed }, { "ssg_bgzf", ssg_abi_fp_bgzf }, { "sam_format", ssg_abi_fp_sam_format }, { "ssg_bam", ssg_abi_fp_bam }, { "ssg_coll", ssg_abi_fp_coll }, { "ssg_bgzf_frame", ssg_abi_fp_bgzf_frame }, { "ssg_rec_gather", ssg_abi_fp_rec_gather }, { "ssg_msw_replay", ssg_abi_fp_msw_replay } };
+	struct { const char *unit; void (*fn)(ssg_abi_fp_t*); } const units[] = { { "ssg_index_build", ssg_abi_fp_index_build }, { "ssg_seed", ssg_abi_fp_seed }, { "ssg_bgzf", ssg_abi_fp_bgzf }, { "sam_format", ssg_abi_fp_sam_format }, { "ssg_bam", ssg_abi_fp_bam }, { "ssg_coll", ssg_abi_fp_coll }, { "ssg_bgzf_frame", ssg_abi_fp_bgzf_frame }, { "ssg_rec_gather", ssg_abi_fp_rec_gather }, { "ssg_msw_replay", ssg_abi_fp_msw_replay }, { "ssg_dbg", ssg_abi_fp_dbg } };
 	ssg_abi_fp_t mine; ssg_abi_fp_core(&mine);
 	for (const auto &u : units) {
 		ssg_abi_fp_t o; u.fn(&o);
@@ -92,7 +93,7 @@ int ssg_dev_exclusive_scan(const int32_t *d_in, int64_t *d_out, long n, int64_t 
 	return rt_d2h(total, d_out + n, 8);
 }
 /* order[] = indices 0..n-1 by descending key (heaviest-first work lists; equal keys in index order), on the device */
-static int dev_order_desc(const int32_t *d_key, int32_t *d_order, long n)
+int dev_order_desc(const int32_t *d_key, int32_t *d_order, long n)
 {
 	if (n <= 0) return 0;
 	dbuf<int32_t> iota(n), kout(n);
@@ -376,20 +377,7 @@ void ssg_prof_reset(void) {}
 int ssg_prof_get(int, const char **, double *, long *) { return 0; }
 #endif
 
-/* tuning aid: device phase counters (cycles) accumulated by instrumented kernels; reset on read */
-int ssg_dbg_cycles(unsigned long long out[32])
-{
-#ifdef SSG_EMU
-	memcpy(out, ssg_dbg_cyc, 256); memset(ssg_dbg_cyc, 0, 256);
-	return 0;
-#else
-	unsigned long long z[32]; memset(z, 0, sizeof z);
-	if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ssg_dbg_cyc), 256) != hipSuccess) return SSG_EHIP;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(ssg_dbg_cyc), z, 256) != hipSuccess) return SSG_EHIP;
-	return 0;
-#endif
-}
-/* any stretch of the counters (tuning builds) */
+/* tuning aid: device phase counters (cycles) accumulated by instrumented kernels; reset on read: any stretch of the counters (tuning builds) ... */
 int ssg_dbg_cycles_at(int first, int n, unsigned long long *out)
 {
 	if (first < 0 || n < 0 || first + n > 96) return SSG_EINVAL;
@@ -403,21 +391,9 @@ int ssg_dbg_cycles_at(int first, int n, unsigned long long *out)
 	return 0;
 #endif
 }
-/* test hook: how the last call of this thread split its CIGAR requests (wave kernel, lane DP classes 0..2) */
-void ssg_dbg_reg2aln_counts(unsigned int out[4]);
-/* slots 32..63 (32..47: the lane-per-extension kernel's lane utilisation, k_extlane.h; 48..63: band widths of the requests that need a DP, k_aln.h) */
-int ssg_dbg_cycles_hi(unsigned long long out[32])
-{
-#ifdef SSG_EMU
-	memcpy(out, ssg_dbg_cyc + 32, 256); memset(ssg_dbg_cyc + 32, 0, 256);
-	return 0;
-#else
-	unsigned long long z[32]; memset(z, 0, sizeof z);
-	if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ssg_dbg_cyc), 256, 256) != hipSuccess) return SSG_EHIP;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(ssg_dbg_cyc), z, 256, 256) != hipSuccess) return SSG_EHIP;
-	return 0;
-#endif
-}
+/* ... slots 0..31, and slots 32..63 (32..47: the lane-per-extension kernel's lane utilisation, k_extlane.h; 48..63: band widths of the requests that need a DP, k_aln.h) */
+int ssg_dbg_cycles(unsigned long long out[32]) { return ssg_dbg_cycles_at(0, 32, out); }
+int ssg_dbg_cycles_hi(unsigned long long out[32]) { return ssg_dbg_cycles_at(32, 32, out); }
 
 int64_t ssg_index_l_pac(const ssg_index_t *ix) { return ix->v.l_pac; }
 int ssg_index_n_ctg(const ssg_index_t *ix) { return ix->v.n_ctg; }
@@ -697,12 +673,8 @@ int ssg_smem_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads
 	return d_n.down(out_n, n_reads);
 }
 
-/* ------------------------------- mem_align1_core for a batch ------------------------------- */
-struct align1_dev_t {	/* device-resident result of stages 1-4 */
-	dbuf<int64_t> seed_off; dbuf<ssg_alnreg_t> regs; dbuf<int32_t> n_reg;
-	dbuf<uint8_t> sdp_fixed;   /* per read: its region list is a fixed point of the redundancy scan (no patch alignment was involved) */
-	std::vector<int64_t> h_seed_off; int64_t tot_seeds;
-};
+/* ------------------------------- mem_align1_core for a batch (its device-resident result: align1_dev_t, ssg_stage_int.h) ------------------------------- */
+} /* extern "C": the stage runners that ssg_dbg.cpp calls are C++ functions */
 
 /* The locate stage (upstream mem_chain's walk over the sampled occurrences of every interval): per read its seed count, and per interval the occurrences of
  * the read's earlier ones (d_pre); the seeds placed by a scan into seed_off (n_reads + 1, the caller's); every seed's read by a running maximum over marks at the
@@ -735,9 +707,9 @@ static int sort_pairs_u64(uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint3
  * given by the caller (ssg_dbg_chain), which hands over a view with l_pac and n_ctg alone: the kernels read nothing else of the index.  d_work: the reads heaviest
  * first (seed count), d_queue: 8 zeroed counters.  n_tree (may be NULL): reads chained again on the tree.  form (may be NULL, host, n_reads): the kernel form that
  * took each read, SSG_CHAIN_FORM_* of ssgpu.h. */
-static int run_chain(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const int64_t *d_off, int max_len, const ssg_intv_t *d_intv, const int32_t *d_nintv, int cap,
-                     const int32_t *d_nseed, const int64_t *seed_off, ssg_seed_t *d_seeds, const int32_t *d_srid, ssg_chain_t *d_chains, int32_t *d_order, int32_t *d_kept,
-                     int32_t *d_cseeds, int32_t *d_nchain, const int32_t *d_work, unsigned int *d_queue, uint64_t *n_tree, int32_t *form)
+int run_chain(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const int64_t *d_off, int max_len, const ssg_intv_t *d_intv, const int32_t *d_nintv, int cap,
+              const int32_t *d_nseed, const int64_t *seed_off, ssg_seed_t *d_seeds, const int32_t *d_srid, ssg_chain_t *d_chains, int32_t *d_order, int32_t *d_kept,
+              int32_t *d_cseeds, int32_t *d_nchain, const int32_t *d_work, unsigned int *d_queue, uint64_t *n_tree, int32_t *form)
 {
 	/* d_work is heaviest first.  Reads with >= T seeds chain one wave each with their state in LDS, in four size classes that run
 	 * concurrently (up to 5120, 2048, 1024, 512, 256 seeds = chains: 155 / 62 / 31 / 16 / 8 KB); the light rest one lane per read; the (very
@@ -868,7 +840,7 @@ static int run_chain(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n
  * opt.w, or opt.w << 1 after a band retry; a retry needs max_off >= 3/4 of the band, and max_off is below the sides of the DP matrix -- the read and its window, at
  * most 310 + cal_max_gap < 310 + 4064 with the scores the DP cells allow (a x 2 x length + 64 < 8191) --, so no band above 5900 is ever doubled and opt.w up to
  * 65535 is stored whole.  Above it the low 16 bits would stand for the band (0 at -w 65536: no seed is ever "contained"). */
-static int check_band(const ssg_mem_opt_t *opt)
+int check_band(const ssg_mem_opt_t *opt)
 {
 	if (opt->w < 0 || opt->w > 65535) { ssg_err_msg = "band width (-w) outside 0 .. 65535: beyond the 16-bit band field of the region keys"; return SSG_EINVAL; }
 	return 0;
@@ -876,7 +848,7 @@ static int check_band(const ssg_mem_opt_t *opt)
 /* The CIGAR stage's wave kernel (k_aln.h, k_sw.h) keeps its cells in 32 bits with minus infinity at -2^30: a gap as long as the longest window (SSG_TWIN_GLB rows) must
  * stay far above it.  An extension penalty of 0 is refused with it: upstream divides by it (the band's cap).  Checked before the seeding stage of a pipeline call
  * (run_align1), and in run_reg2aln for callers that enter there. */
-static int check_gap_penalties(const ssg_mem_opt_t *opt)
+int check_gap_penalties(const ssg_mem_opt_t *opt)
 {
 	if (opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 1 || opt->e_ins < 1 || std::max((long)opt->o_del, (long)opt->o_ins) + (long)std::max(opt->e_del, opt->e_ins) * (SSG_TWIN_GLB + 1) >= 1L << 27) {
 		ssg_err_msg = "gap penalties outside the range of the CIGAR kernels: need open >= 0, extend >= 1, open + 32769 x extend < 2^27"; return SSG_EINVAL; }
@@ -885,7 +857,7 @@ static int check_gap_penalties(const ssg_mem_opt_t *opt)
 /* The scoring limits of the extension kernels for reads of up to max_len bases: the 13-bit cells (the product in 64 bits, so that no a overflows it), then the 6-bit
  * score table -- in that order, the order of the messages callers have always met (-A 40 is told of the DP cells).  run_regions, where there is a job, and the test
  * entries, whatever their input. */
-static int check_scores(const ssg_mem_opt_t *opt, int max_len)
+int check_scores(const ssg_mem_opt_t *opt, int max_len)
 {
 	if ((long)opt->a * 2 * max_len + 64 >= 8191) { ssg_err_msg = "match score x read length beyond the 13-bit DP cells of the extension kernel"; return SSG_EINVAL; }
 	if (opt->a > 31 || opt->a < 0 || opt->b > 32 || opt->b < 0) { ssg_err_msg = "match score above 31 or mismatch penalty above 32: beyond the 6-bit score table of the extension kernel"; return SSG_EINVAL; }
@@ -898,9 +870,9 @@ static int check_scores(const ssg_mem_opt_t *opt, int max_len)
  * given by the caller (ssg_dbg_regions), which hands over a view with pac, l_pac and the contig table alone: the kernels read nothing else of the index.  ts: entries of
  * the per-seed arrays (seeds + 1).  d_work: the reads heaviest first, d_queue: a zeroed counter.  o.seed_off, o.regs (ts) and o.n_reg are the caller's; o.sdp_fixed is
  * made here.  cells / n_jobs_out (may be NULL): SW cells and extension jobs.  todo (may be NULL, host): the reads the lane kernel left to the wave kernel. */
-static int run_regions(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, size_t ts,
-                       const ssg_seed_t *d_seeds_p, const ssg_chain_t *d_chains_p, const int32_t *d_order_p, const int32_t *d_cseeds_p, const int32_t *d_nchain_p,
-                       const int32_t *d_work_p, unsigned int *d_queue_p, align1_dev_t &o, uint64_t *cells, uint64_t *n_jobs_out, std::vector<int32_t> *todo)
+int run_regions(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, size_t ts,
+                const ssg_seed_t *d_seeds_p, const ssg_chain_t *d_chains_p, const int32_t *d_order_p, const int32_t *d_cseeds_p, const int32_t *d_nchain_p,
+                const int32_t *d_work_p, unsigned int *d_queue_p, align1_dev_t &o, uint64_t *cells, uint64_t *n_jobs_out, std::vector<int32_t> *todo)
 {
 	CHK(check_band(opt));
 	dbuf<int32_t> d_err(n_reads); dbuf<uint64_t> d_srt(ts); dbuf<unsigned long long> d_cells(1);
@@ -1053,6 +1025,8 @@ static int run_align1(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_re
 	return 0;
 }
 
+extern "C" {
+
 int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
                     int64_t *seed_off, ssg_seed_t **seeds, int32_t **rids)
 {
@@ -1082,213 +1056,6 @@ int ssg_seeds_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_read
 	if (!*seeds || !*rids) { free(*seeds); free(*rids); *seeds = 0; *rids = 0; ssg_err_msg = "host allocation failed"; return SSG_ENOMEM; }
 	CHK(d_seeds.down(*seeds, (size_t)tot)); CHK(d_srid.down(*rids, (size_t)tot));
 	return 0;
-}
-
-/* test entry: the chaining stage on the caller's seeds and intervals (include/ssgpu.h), through run_chain as stage 1 goes through it */
-int ssg_dbg_chain(const ssg_mem_opt_t *opt, int64_t l_pac, int n_ctg, int n_reads, const int32_t *read_len, const int64_t *seed_off, const ssg_seed_t *seeds, const int32_t *rids,
-                  const int64_t *intv_off, const ssg_intv_t *intv, int64_t *chain_off, ssg_chain_t **chains, int32_t **chain_seeds, int32_t *form)
-{
-	static thread_local char msg[160];
-	CHK(ssg_need_device());
-	*chains = 0; *chain_seeds = 0;
-	if (n_reads < 0 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) { ssg_err_msg = "ssg_dbg_chain: need n_reads >= 0, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
-	if (n_reads == 0) { chain_off[0] = 0; return SSG_OK; }
-	const char *bad = 0; long at = 0;
-	if (seed_off[0] != 0 || intv_off[0] != 0) bad = "offsets start at 0: read";
-	int max_len = 0, cap = 1;
-	for (int r = 0; !bad && r < n_reads; ++r) {
-		const int len = read_len[r];
-		at = r;
-		if (seed_off[r + 1] < seed_off[r] || intv_off[r + 1] < intv_off[r]) { bad = "offsets must not decrease: read"; break; }
-		if (seed_off[r + 1] - seed_off[r] >= (int64_t)1 << 24 || intv_off[r + 1] - intv_off[r] >= (int64_t)1 << 24) { bad = "more than 2^24 seeds or intervals: read"; break; }
-		if (len < 1 || len > SSG_MAX_READ_LEN) { bad = "need 1 <= read_len <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
-		max_len = std::max(max_len, len); cap = std::max(cap, (int)(intv_off[r + 1] - intv_off[r]));
-		for (int64_t k = seed_off[r]; !bad && k < seed_off[r + 1]; ++k) {
-			const ssg_seed_t &s = seeds[k];
-			if (!(0 <= s.qbeg && 1 <= s.len && s.qbeg <= len - s.len)) bad = "need 0 <= qbeg, 1 <= len, qbeg + len <= read_len: seed";
-			else if (!(0 <= s.rbeg && s.rbeg <= 2 * l_pac - s.len)) bad = "need 0 <= rbeg, rbeg + len <= 2 l_pac: seed";
-			else if (rids[k] >= n_ctg) bad = "rid beyond the contigs: seed";
-			if (bad) at = (long)k;
-		}
-		int64_t prev = 0;
-		for (int64_t k = intv_off[r]; !bad && k < intv_off[r + 1]; ++k) {
-			const int64_t sb = (int64_t)(intv[k].info >> 32), se = (int64_t)(uint32_t)intv[k].info;
-			if (!(sb < se && se <= len)) bad = "need 0 <= start < end <= read_len: interval";
-			else if (sb < prev) bad = "intervals must be sorted by start: interval";
-			prev = sb;
-			if (bad) at = (long)k;
-		}
-	}
-	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_chain: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
-	const int64_t tot = seed_off[n_reads];
-	if (tot >= (int64_t)1 << 31) { ssg_err_msg = "ssg_dbg_chain: more than 2^31 seeds"; return SSG_EINVAL; }
-	/* the stage's inputs as the seeding stage leaves them: read offsets, the dense interval layout (cap entries a read), seeds with score = len */
-	const size_t ts = (size_t)tot + 1;
-	std::vector<int64_t> h_off((size_t)n_reads + 1, 0); std::vector<int32_t> h_ni((size_t)n_reads), h_ns((size_t)n_reads);
-	std::vector<ssg_intv_t> h_iv((size_t)n_reads * cap); std::vector<ssg_seed_t> h_sd(ts);
-	memset(h_iv.data(), 0, h_iv.size() * sizeof(ssg_intv_t));
-	for (int r = 0; r < n_reads; ++r) {
-		h_off[r + 1] = h_off[r] + read_len[r]; h_ni[r] = (int32_t)(intv_off[r + 1] - intv_off[r]); h_ns[r] = (int32_t)(seed_off[r + 1] - seed_off[r]);
-		for (int k = 0; k < h_ni[r]; ++k) h_iv[(size_t)r * cap + k] = intv[intv_off[r] + k];
-	}
-	for (int64_t k = 0; k < tot; ++k) { h_sd[k] = seeds[k]; h_sd[k].score = seeds[k].len; h_sd[k].next = -1; }
-	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
-	ix.l_pac = l_pac; ix.n_ctg = n_ctg;
-	dbuf<int64_t> d_off((size_t)n_reads + 1), d_soff((size_t)n_reads + 1); dbuf<ssg_intv_t> d_intv((size_t)n_reads * cap); dbuf<int32_t> d_nintv(n_reads), d_nseed(n_reads);
-	dbuf<ssg_seed_t> d_seeds(ts); dbuf<int32_t> d_srid(ts), d_order(ts), d_kept(ts), d_cseeds(ts), d_nchain(n_reads), d_work(n_reads); dbuf<ssg_chain_t> d_chains(ts); dbuf<unsigned int> d_queue(8);
-	CHKA(d_off); CHKA(d_soff); CHKA(d_intv); CHKA(d_nintv); CHKA(d_nseed); CHKA(d_seeds); CHKA(d_srid); CHKA(d_order); CHKA(d_kept); CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_work); CHKA(d_chains); CHKA(d_queue);
-	CHK(d_off.up(h_off.data(), (size_t)n_reads + 1)); CHK(d_soff.up(seed_off, (size_t)n_reads + 1)); CHK(d_intv.up(h_iv.data(), h_iv.size())); CHK(d_nintv.up(h_ni.data(), n_reads));
-	CHK(d_nseed.up(h_ns.data(), n_reads)); CHK(d_seeds.up(h_sd.data(), (size_t)tot)); CHK(d_srid.up(rids, (size_t)tot)); CHK(d_nchain.zero());
-	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());   /* (as run_align1 makes the work order) */
-	CHK(run_chain(ix, opt, n_reads, d_off.p, max_len, d_intv.p, d_nintv.p, cap, d_nseed.p, d_soff.p, d_seeds.p, d_srid.p, d_chains.p, d_order.p, d_kept.p, d_cseeds.p, d_nchain.p,
-	              d_work.p, d_queue.p, (uint64_t*)0, form));
-	CHK(rt_sync());
-	std::vector<int32_t> h_nc((size_t)n_reads), h_ord(ts), h_cs(ts); std::vector<ssg_chain_t> h_ch(ts);
-	CHK(d_nchain.down(h_nc.data(), n_reads)); CHK(d_order.down(h_ord.data(), (size_t)tot)); CHK(d_cseeds.down(h_cs.data(), (size_t)tot)); CHK(d_chains.down(h_ch.data(), (size_t)tot));
-	/* the survivors in the stage's order; what the kernels left is checked against the slices before it is followed */
-	int64_t n_out = 0, n_sd = 0;
-	for (int r = 0; r < n_reads; ++r) {
-		if (h_nc[r] < 0 || h_nc[r] > h_ns[r]) { ssg_err_msg = "ssg_dbg_chain: a read's chain count is outside its slice"; return SSG_EOVERFLOW; }
-		for (int i = 0; i < h_nc[r]; ++i) {
-			const int32_t id = h_ord[seed_off[r] + i];
-			if (id < 0 || id >= h_ns[r]) { ssg_err_msg = "ssg_dbg_chain: a chain id is outside its read's slice"; return SSG_EOVERFLOW; }
-			const ssg_chain_t &c = h_ch[seed_off[r] + id];
-			if (c.n < 1 || c.first_seed < seed_off[r] || (int64_t)c.first_seed + c.n > seed_off[r + 1]) { ssg_err_msg = "ssg_dbg_chain: a chain's seed list is outside its read's slice"; return SSG_EOVERFLOW; }
-			++n_out; n_sd += c.n;
-		}
-	}
-	ssg_chain_t *oc = (ssg_chain_t*)calloc((size_t)n_out + 1, sizeof(ssg_chain_t)); int32_t *os = (int32_t*)calloc((size_t)n_sd + 1, sizeof(int32_t));
-	if (!oc || !os) { free(oc); free(os); ssg_err_msg = "host allocation failed: chains"; return SSG_ENOMEM; }
-	int64_t k = 0, q = 0;
-	for (int r = 0; r < n_reads; ++r) {
-		chain_off[r] = k;
-		for (int i = 0; i < h_nc[r]; ++i) {
-			const ssg_chain_t &c = h_ch[seed_off[r] + h_ord[seed_off[r] + i]];
-			ssg_chain_t &o = oc[k++];
-			o.pos = c.pos; o.rid = c.rid; o.n = c.n; o.w = c.w; o.kept = c.kept; o.frac_rep = c.frac_rep; o.first_seed = (int32_t)q;
-			for (int j = 0; j < c.n; ++j) os[q++] = (int32_t)(h_cs[c.first_seed + j] - seed_off[r]);
-		}
-	}
-	chain_off[n_reads] = k;
-	*chains = oc; *chain_seeds = os;
-	return SSG_OK;
-}
-
-/* test entry: the region stage on the caller's chains (include/ssgpu.h), through run_regions as stage 1 goes through it */
-int ssg_dbg_regions(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
-                    const int64_t *seed_off, const ssg_seed_t *seeds, const int64_t *chain_off, const ssg_chain_t *chains, const int32_t *chain_seeds,
-                    int64_t *reg_off, ssg_alnreg_t **regs, int32_t *route)
-{
-	static thread_local char msg[200];
-	CHK(ssg_need_device());
-	*regs = 0;
-	if (n_reads < 0 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) { ssg_err_msg = "ssg_dbg_regions: need n_reads >= 0, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
-	for (int c = 0; c < n_ctg; ++c)
-		if (ctg_len[c] < 1 || ctg_off[c] != (c ? ctg_off[c - 1] + ctg_len[c - 1] : 0) || ctg_off[c] + ctg_len[c] > l_pac || (c == n_ctg - 1 && ctg_off[c] + ctg_len[c] != l_pac)) {
-			ssg_err_msg = "ssg_dbg_regions: the contigs must tile [0, l_pac) in order"; return SSG_EINVAL; }
-	if (n_reads == 0) { reg_off[0] = 0; return SSG_OK; }
-	const char *bad = 0; long at = 0;
-	if (off[0] != 0 || seed_off[0] != 0 || chain_off[0] != 0) bad = "offsets start at 0: read";
-	int max_len = 0;
-	auto ctg_of = [&](int64_t p) { const int64_t f = p < l_pac ? p : 2 * l_pac - 1 - p; int lo = 0, hi = n_ctg - 1; while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ctg_off[mid] <= f) lo = mid; else hi = mid - 1; } return lo; };
-	std::vector<uint8_t> used;
-	for (int r = 0; !bad && r < n_reads; ++r) {
-		at = r;
-		if (off[r + 1] < off[r] || seed_off[r + 1] < seed_off[r] || chain_off[r + 1] < chain_off[r]) { bad = "offsets must not decrease: read"; break; }
-		const int64_t len64 = off[r + 1] - off[r], ns = seed_off[r + 1] - seed_off[r], nc = chain_off[r + 1] - chain_off[r];
-		if (len64 < 1 || len64 > SSG_MAX_READ_LEN) { bad = "need 1 <= read length <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
-		if (ns >= (int64_t)1 << 24) { bad = "more than 2^24 seeds: read"; break; }
-		if (nc > ns) { bad = "more chains than seeds: read"; break; }
-		const int len = (int)len64;
-		max_len = std::max(max_len, len);
-		for (int64_t k = off[r]; k < off[r + 1]; ++k) if (seq[k] > 4) { bad = "read codes are 0 .. 4: read"; break; }
-		for (int64_t k = seed_off[r]; !bad && k < seed_off[r + 1]; ++k) {
-			const ssg_seed_t &sd = seeds[k];
-			if (!(0 <= sd.qbeg && 1 <= sd.len && sd.qbeg <= len - sd.len)) bad = "need 0 <= qbeg, 1 <= len, qbeg + len <= read length: seed";
-			else if (!(0 <= sd.rbeg && sd.rbeg <= 2 * l_pac - sd.len)) bad = "need 0 <= rbeg, rbeg + len <= 2 l_pac: seed";
-			if (bad) at = (long)k;
-		}
-		used.assign((size_t)ns, 0);
-		for (int64_t k = chain_off[r]; !bad && k < chain_off[r + 1]; ++k) {
-			const ssg_chain_t &c = chains[k];
-			at = (long)k;
-			if (c.n < 1) { bad = "a chain has at least 1 seed: chain"; break; }
-			if (c.first_seed < 0 || (k > 0 && c.first_seed != chains[k - 1].first_seed + chains[k - 1].n) || (k == 0 && c.first_seed != 0)) { bad = "first_seed must run on from the chain before: chain"; break; }
-			for (int j = 0; j < c.n; ++j) {
-				const int32_t id = chain_seeds[c.first_seed + j];
-				if (id < 0 || id >= ns) { bad = "a seed index outside the read's seeds: chain"; break; }
-				if (used[(size_t)id]) { bad = "a seed in two chains: chain"; break; }
-				used[(size_t)id] = 1;
-			}
-			if (bad) break;
-			const int64_t first = seeds[seed_off[r] + chain_seeds[c.first_seed]].rbeg;
-			if (c.rid != ctg_of(first)) { bad = "rid must be the contig of the chain's first seed: chain"; break; }
-			/* the window is cut to the first seed's contig and strand (ssg_k_ext_prep): a seed outside it would index the window out of range */
-			int64_t cb = ctg_off[c.rid], ce = cb + ctg_len[c.rid];
-			if (first >= l_pac) { const int64_t t = cb; cb = 2 * l_pac - ce; ce = 2 * l_pac - t; }
-			for (int j = 0; j < c.n; ++j) {
-				const ssg_seed_t &sd = seeds[seed_off[r] + chain_seeds[c.first_seed + j]];
-				if (sd.rbeg < cb || sd.rbeg + sd.len > ce) { bad = "every seed of a chain must lie inside the contig and strand of its first seed: chain"; break; }
-			}
-			if (bad) break;
-		}
-	}
-	if (!bad) {   /* the scoring limits of the pipeline, whatever the chains: run_regions checks them only where there is a job */
-		CHK(check_scores(opt, max_len));
-		if (opt->e_del < 1 || opt->e_ins < 1) { ssg_err_msg = "ssg_dbg_regions: gap extension penalties must be positive"; return SSG_EINVAL; }
-	}
-	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_regions: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
-	const int64_t tot = seed_off[n_reads];
-	if (tot >= (int64_t)1 << 31) { ssg_err_msg = "ssg_dbg_regions: more than 2^31 seeds"; return SSG_EINVAL; }
-	/* the stage's inputs as the chaining stage leaves them: per read a slice at seed_off[r] of chain records, their order and their seed lists (absolute indices) */
-	const size_t ts = (size_t)tot + 1;
-	std::vector<ssg_seed_t> h_sd(ts); std::vector<ssg_chain_t> h_ch(ts); std::vector<int32_t> h_ord(ts, 0), h_cs(ts, 0), h_nc((size_t)n_reads), h_ns((size_t)n_reads);
-	memset(h_ch.data(), 0, ts * sizeof(ssg_chain_t)); memset(h_sd.data(), 0, ts * sizeof(ssg_seed_t));
-	for (int64_t k = 0; k < tot; ++k) { h_sd[k] = seeds[k]; h_sd[k].score = seeds[k].len; h_sd[k].next = -1; }
-	for (int r = 0; r < n_reads; ++r) {
-		const int64_t s0 = seed_off[r];
-		int64_t q = s0;
-		h_nc[r] = (int32_t)(chain_off[r + 1] - chain_off[r]); h_ns[r] = (int32_t)(seed_off[r + 1] - s0);
-		for (int i = 0; i < h_nc[r]; ++i) {
-			const ssg_chain_t &c = chains[chain_off[r] + i];
-			ssg_chain_t &d = h_ch[s0 + i];
-			d = c; d.first_seed = (int32_t)q; d.last_seed = -1;
-			h_ord[s0 + i] = i;
-			for (int j = 0; j < c.n; ++j) h_cs[q++] = (int32_t)(s0 + chain_seeds[c.first_seed + j]);
-		}
-	}
-	const size_t pac_bytes = (size_t)(l_pac / 4 + 1);
-	dbuf<uint8_t> d_pac(pac_bytes), d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_coff((size_t)n_ctg), d_off((size_t)n_reads + 1); dbuf<int32_t> d_clen((size_t)n_ctg);
-	dbuf<ssg_seed_t> d_seeds(ts); dbuf<ssg_chain_t> d_chains(ts); dbuf<int32_t> d_order(ts), d_cseeds(ts), d_nchain(n_reads), d_nseed(n_reads), d_work(n_reads); dbuf<unsigned int> d_queue(8);
-	CHKA(d_pac); CHKA(d_seq); CHKA(d_coff); CHKA(d_off); CHKA(d_clen); CHKA(d_seeds); CHKA(d_chains); CHKA(d_order); CHKA(d_cseeds); CHKA(d_nchain); CHKA(d_nseed); CHKA(d_work); CHKA(d_queue);
-	CHK(d_pac.up(pac, pac_bytes)); CHK(d_seq.up(seq, (size_t)off[n_reads])); CHK(d_coff.up(ctg_off, (size_t)n_ctg)); CHK(d_clen.up(ctg_len, (size_t)n_ctg)); CHK(d_off.up(off, (size_t)n_reads + 1));
-	CHK(d_seeds.up(h_sd.data(), ts)); CHK(d_chains.up(h_ch.data(), ts)); CHK(d_order.up(h_ord.data(), ts)); CHK(d_cseeds.up(h_cs.data(), ts));
-	CHK(d_nchain.up(h_nc.data(), n_reads)); CHK(d_nseed.up(h_ns.data(), n_reads));
-	CHK(dev_order_desc(d_nseed.p, d_work.p, n_reads)); CHK(rt_sync()); CHK(d_queue.zero());   /* (as run_align1 makes the work order) */
-	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
-	ix.pac = d_pac.p; ix.ctg_off = d_coff.p; ix.ctg_len = d_clen.p; ix.l_pac = l_pac; ix.n_ctg = n_ctg;
-	align1_dev_t o;
-	if (!o.seed_off.alloc((size_t)n_reads + 1) || !o.regs.alloc(ts) || !o.n_reg.alloc(n_reads)) { ssg_err_msg = "device allocation failed: regs"; return SSG_ENOMEM; }
-	CHK(o.seed_off.up(seed_off, (size_t)n_reads + 1));
-	std::vector<int32_t> todo;
-	CHK(run_regions(ix, opt, n_reads, d_seq.p, d_off.p, max_len, ts, d_seeds.p, d_chains.p, d_order.p, d_cseeds.p, d_nchain.p, d_work.p, d_queue.p, o, (uint64_t*)0, (uint64_t*)0, &todo));
-	std::vector<int32_t> hn((size_t)n_reads); std::vector<uint8_t> hf((size_t)n_reads); std::vector<ssg_alnreg_t> all(ts);
-	CHK(o.n_reg.down(hn.data(), n_reads)); CHK(o.sdp_fixed.down(hf.data(), n_reads)); CHK(o.regs.down(all.data(), (size_t)tot));
-	int64_t n_out = 0;
-	for (int r = 0; r < n_reads; ++r) {
-		if (hn[r] < 0 || hn[r] > h_ns[r]) { ssg_err_msg = "ssg_dbg_regions: a read's region count is outside its slice"; return SSG_EOVERFLOW; }
-		reg_off[r] = n_out; n_out += hn[r];
-	}
-	reg_off[n_reads] = n_out;
-	ssg_alnreg_t *out = (ssg_alnreg_t*)malloc(sizeof(ssg_alnreg_t) * (size_t)(n_out + 1));
-	if (!out) { ssg_err_msg = "host allocation failed: regions"; return SSG_ENOMEM; }
-	for (int r = 0; r < n_reads; ++r) memcpy(out + reg_off[r], all.data() + seed_off[r], sizeof(ssg_alnreg_t) * (size_t)hn[r]);
-	if (route) {
-		for (int r = 0; r < n_reads; ++r) route[r] = hf[r] == 0 ? SSG_REG_ROUTE_PATCH : 0;
-		for (size_t k = 0; k < todo.size(); ++k) if (todo[k] >= 0 && todo[k] < n_reads) route[todo[k]] |= SSG_REG_ROUTE_WAVE;
-	}
-	*regs = out;
-	return SSG_OK;
 }
 
 int ssg_align1_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off,
@@ -1359,7 +1126,7 @@ static void host_pestat(const ssg_mem_opt_t *opt, const uint32_t *hist /* [4][SS
 
 /* upstream mem_pestat for every batch of the call: candidate selection and the insert-size histograms on the device (ssg_k_pestat_hist), quartiles, mean, std
  * and the fences on the host (host_pestat).  The pipeline (ssg_pe_core) and the test entry ssg_dbg_pestat both come through here. */
-static int run_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg,
+int run_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg,
                       const int32_t *d_pb, int n_batches, ssg_pestat_t *pes /* n_batches x 4 */)
 {
 	const int block = 256;
@@ -1379,7 +1146,7 @@ static thread_local unsigned int ssg_r2a_last[1 + SSG_R2D_CLASSES];   /* of this
 /* CIGAR / NM / MD of the compacted requests (k_aln.h): gap-free records one lane each; records whose band is narrow one lane each through the DP (three classes of
  * band width, a launch each with the LDS that class needs, side by side); the rest -- wide bands, and records whose first alignment does not end upstream's
  * loop -- one wave each.  SSG_R2A_DPLANE=0: no lane DP (A/B, tests). */
-struct r2a_lists_t { std::vector<int32_t> dp[SSG_R2D_CLASSES], todo; };   /* what the kernels left of one call: the lane DP's lists by class, the wave kernel's list */
+static_assert(SSG_STAGE_R2D_CLASSES == SSG_R2D_CLASSES && SSG_STAGE_TWIN_GLB == SSG_TWIN_GLB, "ssg_stage_int.h disagrees with k_aln.h or k_extend.h about a constant");
 /* The lane DP keeps h and e in 16 bits with "minus infinity" at SSG_R2D_NEG.  Its comparisons come out as upstream's while every value of a reachable cell, and every
  * gap-opening candidate made of one, lies above everything derived from minus infinity (at most SSG_R2D_NEG + a); what is stored then stays above -32768 as well.  A
  * reachable in-band H is at least the score of the path "down the main diagonal, then one gap of |i - j| <= 33": -(b' min(i, j) + o + 33 e) with b' = max(b, 1) (an N
@@ -1392,8 +1159,8 @@ static bool r2a_dplane_in_range(const ssg_mem_opt_t *opt, int max_len)
 	if (opt->o_del < 0 || opt->o_ins < 0 || opt->e_del < 0 || opt->e_ins < 0 || opt->a < 0 || opt->b < 0) return false;
 	return bm * n + om + 33 * em + 2 * oe + 66 * em + opt->a < -(long)SSG_R2D_NEG && (long)opt->a * n < 32767;
 }
-static int run_reg2aln(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int64_t nreq, const ssg_alnreq_t *d_creq, const ssg_alnreg_t *d_regs, const uint8_t *d_seq, const int64_t *d_off,
-                       ssg_aln_t *d_alns, int32_t *d_gerr, unsigned long long *d_cnt, int max_len, r2a_lists_t *lists = 0)
+int run_reg2aln(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int64_t nreq, const ssg_alnreq_t *d_creq, const ssg_alnreg_t *d_regs, const uint8_t *d_seq, const int64_t *d_off,
+                ssg_aln_t *d_alns, int32_t *d_gerr, unsigned long long *d_cnt, int max_len, r2a_lists_t *lists)
 {
 	CHK(check_gap_penalties(opt));
 	const int wpb = SSG_WAVES_PER_WG;
@@ -1446,81 +1213,14 @@ static int run_reg2aln(const ssg_index_view_t &ix, const ssg_mem_opt_t *opt, int
 	return 0;
 }
 
+/* test hook: how the last call of this thread split its CIGAR requests (wave kernel, lane DP classes 0..2) */
 extern "C" void ssg_dbg_reg2aln_counts(unsigned int out[4]) { for (int k = 0; k < 1 + SSG_R2D_CLASSES; ++k) out[k] = ssg_r2a_last[k]; }
-
-/* test entry: CIGAR / POS / NM / MD of the caller's requests on the caller's regions (include/ssgpu.h), through run_reg2aln as run_req_tail goes through it */
-extern "C" int ssg_dbg_reg2aln(const ssg_mem_opt_t *opt, const uint8_t *pac, int64_t l_pac, int n_ctg, const int64_t *ctg_off, const int32_t *ctg_len, int n_reads, const uint8_t *seq, const int64_t *off,
-                               int64_t n_regs, const ssg_alnreg_t *regs, int64_t n_req, const ssg_alnreq_t *req, ssg_aln_t *alns, int32_t *route, int32_t *dev_err)
-{
-	static thread_local char msg[200];
-	CHK(ssg_need_device());
-	if (dev_err) *dev_err = 0;
-	if (n_reads < 0 || n_regs < 0 || n_req < 0 || n_req >= (int64_t)1 << 31 || l_pac < 1 || l_pac >= (int64_t)1 << 33 || n_ctg < 1) {
-		ssg_err_msg = "ssg_dbg_reg2aln: need n_reads, n_regs >= 0, 0 <= n_req < 2^31, 1 <= l_pac < 2^33, n_ctg >= 1"; return SSG_EINVAL; }
-	for (int c = 0; c < n_ctg; ++c)
-		if (ctg_len[c] < 1 || ctg_off[c] != (c ? ctg_off[c - 1] + ctg_len[c - 1] : 0) || ctg_off[c] + ctg_len[c] > l_pac || (c == n_ctg - 1 && ctg_off[c] + ctg_len[c] != l_pac)) {
-			ssg_err_msg = "ssg_dbg_reg2aln: the contigs must tile [0, l_pac) in order"; return SSG_EINVAL; }
-	if (n_req == 0) return SSG_OK;
-	const char *bad = 0; long at = 0;
-	int max_len = 0;
-	if (n_reads < 1) bad = "requests need reads: request";
-	else if (off[0] != 0) bad = "offsets start at 0: read";
-	for (int r = 0; !bad && r < n_reads; ++r) {
-		at = r;
-		if (off[r + 1] < off[r]) { bad = "offsets must not decrease: read"; break; }
-		const int64_t len64 = off[r + 1] - off[r];
-		if (len64 < 1 || len64 > SSG_MAX_READ_LEN) { bad = "need 1 <= read length <= " SSG_STR(SSG_MAX_READ_LEN) ": read"; break; }
-		max_len = std::max(max_len, (int)len64);
-		for (int64_t k = off[r]; k < off[r + 1]; ++k) if (seq[k] > 4) { bad = "read codes are 0 .. 4: read"; break; }
-	}
-	for (int64_t k = 0; !bad && k < n_regs; ++k) {
-		const ssg_alnreg_t &a = regs[k];
-		at = (long)k;
-		if (!(0 <= a.rb && a.rb < a.re && a.re <= 2 * l_pac)) bad = "need 0 <= rb < re <= 2 l_pac: region";
-		else if (a.rb < l_pac && a.re > l_pac) bad = "a region must not cross the forward / reverse boundary l_pac: region";
-		else if (a.re - a.rb > SSG_TWIN_GLB) bad = "need re - rb <= 32768: region";
-		else if (!(0 <= a.qb && a.qb < a.qe && a.qe <= SSG_MAX_READ_LEN)) bad = "need 0 <= qb < qe <= read length: region";
-	}
-	for (int64_t k = 0; !bad && k < n_req; ++k) {
-		const ssg_alnreq_t &q = req[k];
-		at = (long)k;
-		if (q.read < 0 || q.read >= n_reads) bad = "read index out of range: request";
-		else if (q.reg >= n_regs) bad = "region index out of range: request";
-		else if (q.kind != SSG_REQ_MAIN && q.kind != SSG_REQ_XA) bad = "kind is SSG_REQ_MAIN or SSG_REQ_XA: request";
-		else if (q.reg >= 0 && regs[q.reg].qe > off[q.read + 1] - off[q.read]) bad = "need 0 <= qb < qe <= read length for the request's region and read: request";
-	}
-	if (bad) { snprintf(msg, sizeof(msg), "ssg_dbg_reg2aln: %s %ld", bad, at); ssg_err_msg = msg; return SSG_EINVAL; }
-	/* the scoring limits of the pipeline (the functions run_align1, run_regions and run_reg2aln call), whatever the requests */
-	CHK(check_band(opt)); CHK(check_scores(opt, max_len)); CHK(check_gap_penalties(opt));
-	const size_t pac_bytes = (size_t)(l_pac / 4 + 1);
-	dbuf<uint8_t> d_pac(pac_bytes), d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_coff((size_t)n_ctg), d_off((size_t)n_reads + 1); dbuf<int32_t> d_clen((size_t)n_ctg), d_gerr(1);
-	dbuf<ssg_alnreg_t> d_regs((size_t)n_regs + 1); dbuf<ssg_alnreq_t> d_req((size_t)n_req + 1); dbuf<ssg_aln_t> d_alns((size_t)n_req + 1); dbuf<unsigned long long> d_cnt(3);
-	CHKA(d_pac); CHKA(d_seq); CHKA(d_coff); CHKA(d_off); CHKA(d_clen); CHKA(d_gerr); CHKA(d_regs); CHKA(d_req); CHKA(d_alns); CHKA(d_cnt);
-	CHK(d_pac.up(pac, pac_bytes)); CHK(d_seq.up(seq, (size_t)off[n_reads])); CHK(d_coff.up(ctg_off, (size_t)n_ctg)); CHK(d_clen.up(ctg_len, (size_t)n_ctg)); CHK(d_off.up(off, (size_t)n_reads + 1));
-	if (n_regs) CHK(d_regs.up(regs, (size_t)n_regs));
-	CHK(d_req.up(req, (size_t)n_req)); CHK(d_alns.zero()); CHK(d_gerr.zero()); CHK(d_cnt.zero());
-	ssg_index_view_t ix; memset(&ix, 0, sizeof(ix));
-	ix.pac = d_pac.p; ix.ctg_off = d_coff.p; ix.ctg_len = d_clen.p; ix.l_pac = l_pac; ix.n_ctg = n_ctg;
-	r2a_lists_t lists;
-	CHK(run_reg2aln(ix, opt, n_req, d_req.p, d_regs.p, d_seq.p, d_off.p, d_alns.p, d_gerr.p, d_cnt.p, max_len, &lists));
-	int32_t ge = 0;
-	CHK(d_gerr.down(&ge, 1));
-	if (dev_err) *dev_err = ge;
-	CHK(d_alns.down(alns, (size_t)n_req));
-	if (route) {
-		for (int64_t k = 0; k < n_req; ++k) route[k] = req[k].reg >= 0 ? SSG_R2A_ROUTE_LANE : 0;
-		for (int c = 0; c < SSG_R2D_CLASSES; ++c) for (int32_t g : lists.dp[c]) if (g >= 0 && g < n_req) route[g] = SSG_R2A_ROUTE_DP0 << c;
-		for (int32_t g : lists.todo) if (g >= 0 && g < n_req) route[g] = (route[g] & ~SSG_R2A_ROUTE_LANE) | SSG_R2A_ROUTE_WAVE;
-	}
-	if (ge) { snprintf(msg, sizeof(msg), "CIGAR generation exceeded an on-device capacity (code %d)", ge); ssg_err_msg = msg; return SSG_EOVERFLOW; }
-	return SSG_OK;
-}
 
 /* mem_sam_pe after mate rescue, for all pairs: primary marking, pairing, MAPQ, record selection (k_pair.h, k_pairw.h), on the region slices reg_off (t2 slots in
  * all) and request slices req_off that ssg_k_pair_caps sized; pair_key = the pairs' region counts, pair_order = the pairs heaviest first, err zeroed by the caller.
  * Which kernel form takes which pair is decided here and nowhere else (SSG_PAIR_WAVE_MIN, SSG_PAIR_LDS); a pair beyond an on-device capacity ends the call with
  * SSG_EOVERFLOW.  The pipeline (ssg_pe_core) and the test entry ssg_dbg_pair_final both come through here. */
-static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, int64_t t2, const int64_t *d_r2off, ssg_alnreg_t *d_regs2, const int32_t *d_nreg,
+int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, int64_t t2, const int64_t *d_r2off, ssg_alnreg_t *d_regs2, const int32_t *d_nreg,
                           const int32_t *d_pb, const ssg_pestat_t *d_pes, const int32_t *d_pkey, const int32_t *d_pw, int32_t *d_zbuf,
                           const int64_t *d_reqoff, ssg_alnreq_t *d_req, int32_t *d_nreq, int32_t *d_perr, unsigned int *d_q)
 {
@@ -1574,9 +1274,8 @@ static int run_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 /* upstream mem_matesw for all pairs, on the pairing-stage slices (d_r2off, head-room included) with n_reg updated in place: which pairs need it (ssg_k_matesw_need), their
  * windows ahead of the decision (k_mswlane.h), the list logic (k_mswkeys.h, and ssg_k_matesw for what that kernel leaves).  d_cnt: SW cells, windows, windows taken from
  * slots; d_perr: ssg_k_matesw's error codes.  The pipeline (ssg_pe_core) and the test entry ssg_dbg_matesw both come through here. */
-struct msw_stage_t { unsigned long long cells, windows, from_slots, left_windows; unsigned int listed, taken, left; };
 static thread_local msw_stage_t ssg_msw_last;   /* of this thread's last rescue stage (ssg_dbg_matesw_last) */
-static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq, const int64_t *d_off, int max_len, const int64_t *d_r2off, ssg_alnreg_t *d_regs2,
+int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *d_seq, const int64_t *d_off, int max_len, const int64_t *d_r2off, ssg_alnreg_t *d_regs2,
                       int32_t *d_nreg, const int32_t *d_pb, const ssg_pestat_t *d_pes, const int32_t *d_pw, const uint8_t *d_fixed, int32_t *d_perr, unsigned long long *d_cnt,
                       unsigned int *d_q, msw_stage_t *ms)
 {
@@ -1655,13 +1354,15 @@ static int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pa
 	return 0;
 }
 
-/* The pairing stage's slices, for the pipeline (ssg_pe_core) and the test entry ssg_dbg_pair_final alike: per read a region slice with head-room for rescued
- * hits (d_r2off, t2 slots in all) and a request slice (d_reqoff, tq slots), as ssg_k_pair_caps sizes them (d_cap2, d_capq); d_pkey = the pairs' region counts,
- * d_pw = the pairs heaviest first (key: candidate regions of both ends); d_regs2 = the regions (d_regoff, d_regs, d_nreg) copied into their slices. */
-struct pair_slices_t {
-	dbuf<int32_t> d_cap2, d_capq, d_pkey, d_pw; dbuf<int64_t> d_r2off, d_reqoff; dbuf<ssg_alnreg_t> d_regs2; int64_t t2, tq;
-};
-static int make_pair_slices(int n_reads, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg, int max_matesw, pair_slices_t &s)
+/* a read's regions from one layout into another: d_to[d_to_off[r] + i] = d_from[d_from_off[r] + i] for i < d_nreg[r] (ssg_k_copy_regs); does not wait */
+int dev_copy_regs(int n_reads, const int64_t *d_from_off, const ssg_alnreg_t *d_from, const int32_t *d_nreg, const int64_t *d_to_off, ssg_alnreg_t *d_to)
+{
+	const int block = 256;
+	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_from_off, d_from, d_nreg, d_to_off, d_to);
+	return 0;
+}
+/* The pairing stage's slices (pair_slices_t, ssg_stage_int.h), made as the pipeline makes them: for ssg_pe_core and the test entry ssg_dbg_pair_final alike */
+int make_pair_slices(int n_reads, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg, int max_matesw, pair_slices_t &s)
 {
 	const int n_pairs = n_reads / 2, block = 256;
 	if (!s.d_cap2.alloc(n_reads) || !s.d_capq.alloc(n_reads) || !s.d_pkey.alloc(n_pairs) || !s.d_pw.alloc(n_pairs) || !s.d_r2off.alloc(n_reads + 1) || !s.d_reqoff.alloc(n_reads + 1)) {
@@ -1670,15 +1371,13 @@ static int make_pair_slices(int n_reads, const int64_t *d_regoff, const ssg_alnr
 	CHK(ssg_dev_exclusive_scan(s.d_cap2.p, s.d_r2off.p, n_reads, &s.t2)); CHK(ssg_dev_exclusive_scan(s.d_capq.p, s.d_reqoff.p, n_reads, &s.tq));
 	CHK(dev_order_desc(s.d_pkey.p, s.d_pw.p, n_pairs)); CHK(rt_sync());
 	if (!s.d_regs2.alloc((size_t)s.t2 + 1)) { ssg_err_msg = "device allocation failed: pairing-stage regions"; return SSG_ENOMEM; }
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_regoff, d_regs, d_nreg, s.d_r2off.p, s.d_regs2.p);
-	return 0;
+	return dev_copy_regs(n_reads, d_regoff, d_regs, d_nreg, s.d_r2off.p, s.d_regs2.p);
 }
 
 /* The request tail of ssg_pe_core, se_core and ssg_dbg_pair_final: the requests that the final stage left in the reads' slices (d_reqoff, d_req, d_nreq) compacted into
  * t.req, the reads' offsets (n_reads + 1) in t.req_off and, where the caller wants them on the host at once, in h_off.  With `a`, on through CIGAR / NM / MD of every
  * request (run_reg2aln, on the regions a->d_regs) into t.alns, and a->stats[2 .. 4] = what a->d_cnt counted (rescue SW cells, rescues) and the number of records. */
-struct reg2aln_in_t { const ssg_index_t *idx; const ssg_mem_opt_t *opt; const ssg_alnreg_t *d_regs; const uint8_t *d_seq; const int64_t *d_off; int max_len; unsigned long long *d_cnt; uint64_t *stats; };
-static int run_req_tail(int n_reads, const int64_t *d_reqoff, const ssg_alnreq_t *d_req, const int32_t *d_nreq, int64_t *h_off, const reg2aln_in_t *a, pe_dev_t &t)
+int run_req_tail(int n_reads, const int64_t *d_reqoff, const ssg_alnreq_t *d_req, const int32_t *d_nreq, int64_t *h_off, const reg2aln_in_t *a, pe_dev_t &t)
 {
 	const int block = 256;
 	if (!t.req_off.alloc((size_t)n_reads + 1)) { ssg_err_msg = "device allocation failed: request offsets"; return SSG_ENOMEM; }
@@ -1741,147 +1440,13 @@ int ssg_pe_core(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_pairs, con
 	return keep ? 0 : download_records(t, res);
 }
 
-
-/* ---- test entries of the paired-end decision stage: region lists in, the stage's own results out (include/ssgpu.h) ---- */
-static int dbg_check_regs(const ssg_index_t *idx, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs, const char *who)
-{	/* the kernels index by what the lists say: nothing out of range may reach them */
-	static thread_local char msg[160];
-	const int n_reads = 2 * n_pairs;
-	const char *bad = 0; long at = -1;
-	if (n_pairs < 0 || n_pairs > (1 << 24)) { bad = "n_pairs out of range"; at = n_pairs; }
-	else if (reg_off[0] != 0) { bad = "reg_off[0] != 0"; at = 0; }
-	for (int r = 0; r < n_reads && !bad; ++r) {
-		if (reg_off[r + 1] < reg_off[r] || reg_off[r + 1] - reg_off[r] > 4096) { bad = "reg_off not monotone, or more than 4096 regions in a read: read"; at = r; }
-		else if (reg_off[r + 1] > (1LL << 28)) { bad = "too many regions in all: read"; at = r; }
-	}
-	for (int64_t k = 0; !bad && k < reg_off[n_reads]; ++k) {
-		const ssg_alnreg_t &e = regs[k];
-		if (e.rid < 0 || e.rid >= idx->v.n_ctg) bad = "rid out of range: region";
-		else if (!(0 <= e.qb && e.qb < e.qe && e.qe <= 310)) bad = "need 0 <= qb < qe <= 310: region";
-		else if (!(0 <= e.rb && e.rb < e.re && e.re <= 2 * idx->v.l_pac)) bad = "need 0 <= rb < re <= 2 l_pac: region";
-		else if (e.score < 0 || e.score > (1 << 20) || e.csub < 0 || e.csub > (1 << 20)) bad = "score / csub out of range: region";
-		else if (!(e.frac_rep >= 0 && e.frac_rep <= 1)) bad = "frac_rep outside [0, 1]: region";
-		if (bad) at = (long)k;
-	}
-	if (!bad) return 0;
-	snprintf(msg, sizeof(msg), "%s: %s %ld", who, bad, at);
-	ssg_err_msg = msg;
-	return SSG_EINVAL;
-}
-
-extern "C" {
-
-int ssg_dbg_pestat(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const int64_t *reg_off, const ssg_alnreg_t *regs,
-                   const int32_t *pair_batch, int n_batches, ssg_pestat_t *pes)
+/* the rescue stage's counts as the test entries report them (include/ssgpu.h): ssg_dbg_matesw of its own stage (ssg_dbg.cpp), ssg_dbg_matesw_last of this thread's last */
+void msw_counts(const msw_stage_t &m, uint64_t counts[8])
 {
-	CHK(ssg_need_device());
-	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pestat"));
-	if (n_batches < 1 || n_batches > 64) { ssg_err_msg = "ssg_dbg_pestat: 1 <= n_batches <= 64"; return SSG_EINVAL; }
-	for (int p = 0; p < n_pairs; ++p) if (pair_batch[p] < 0 || pair_batch[p] >= n_batches) { ssg_err_msg = "ssg_dbg_pestat: pair_batch out of range"; return SSG_EINVAL; }
-	const int n_reads = 2 * n_pairs;
-	const int64_t tot = reg_off[n_reads];
-	std::vector<int32_t> hn((size_t)n_reads + 1);
-	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
-	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1); dbuf<int32_t> d_n((size_t)n_reads + 1), d_pb((size_t)n_pairs + 1);
-	CHKA(d_off); CHKA(d_regs); CHKA(d_n); CHKA(d_pb);
-	CHK(d_off.up(reg_off, (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.up(pair_batch, (size_t)n_pairs));
-	return run_pestat(idx, opt, n_pairs, d_off.p, d_regs.p, d_n.p, d_pb.p, n_batches, pes);
-}
-
-int ssg_dbg_pair_final(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, int64_t id0, const int64_t *reg_off, const ssg_alnreg_t *regs,
-                       const ssg_pestat_t pes[4], ssg_alnreg_t *regs_out, int64_t *req_off, ssg_alnreq_t **req)
-{
-	CHK(ssg_need_device());
-	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_pair_final"));
-	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].std > 0 && pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_pair_final: an orientation that has not failed needs std > 0 and 0 <= low <= high"; return SSG_EINVAL; }
-	const int n_reads = 2 * n_pairs, block = 256;
-	const int64_t tot = reg_off[n_reads];
-	*req = 0;
-	if (n_pairs == 0) { req_off[0] = 0; return SSG_OK; }
-	std::vector<int32_t> hn((size_t)n_reads);
-	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
-	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1); dbuf<int32_t> d_n((size_t)n_reads), d_pb((size_t)n_pairs); dbuf<ssg_pestat_t> d_pes(4);
-	CHKA(d_off); CHKA(d_regs); CHKA(d_n); CHKA(d_pb); CHKA(d_pes);
-	CHK(d_off.up(reg_off, (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pes.up(pes, 4));
-	/* slices, request capacities and the heaviest-first order: the pipeline's own (make_pair_slices) */
-	pair_slices_t s;
-	CHK(make_pair_slices(n_reads, d_off.p, d_regs.p, d_n.p, opt->max_matesw, s));
-	dbuf<int32_t> d_perr(n_pairs), d_zbuf((size_t)s.t2 + 1), d_nreq(n_reads); dbuf<unsigned int> d_q(1); dbuf<ssg_alnreq_t> d_req((size_t)s.tq + 1);
-	CHKA(d_perr); CHKA(d_zbuf); CHKA(d_nreq); CHKA(d_q); CHKA(d_req);
-	CHK(d_perr.zero()); CHK(d_nreq.zero());
-	CHK(run_pair_final(idx, opt, n_pairs, id0, s.t2, s.d_r2off.p, s.d_regs2.p, d_n.p, d_pb.p, d_pes.p, s.d_pkey.p, s.d_pw.p, d_zbuf.p, s.d_reqoff.p, d_req.p, d_nreq.p, d_perr.p, d_q.p));
-	/* the regions back into the caller's layout, the requests compacted by the pipeline's own tail (without its CIGAR step) */
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, s.d_r2off.p, s.d_regs2.p, d_n.p, d_off.p, d_regs.p);
-	pe_dev_t t;
-	CHK(run_req_tail(n_reads, s.d_reqoff.p, d_req.p, d_nreq.p, 0, 0, t));
-	CHK(rt_sync());
-	const int64_t nreq = t.n_req;
-	std::vector<int64_t> r2off((size_t)n_reads + 1);
-	CHK(s.d_r2off.down(r2off.data(), (size_t)n_reads + 1)); CHK(t.req_off.down(req_off, (size_t)n_reads + 1)); CHK(d_regs.down(regs_out, (size_t)tot));
-	ssg_alnreq_t *out = (ssg_alnreq_t*)malloc(sizeof(ssg_alnreq_t) * (size_t)(nreq + 1));
-	if (!out) { ssg_err_msg = "host allocation failed: requests"; return SSG_ENOMEM; }
-	int rc = t.req.down(out, (size_t)nreq);
-	if (rc) { free(out); return rc; }
-	for (int64_t k = 0; k < nreq; ++k) if (out[k].reg >= 0) out[k].reg = (int32_t)(out[k].reg - r2off[out[k].read] + reg_off[out[k].read]);   /* slice index -> the caller's index */
-	*req = out;
-	return SSG_OK;
-}
-
-void ssg_dbg_matesw_last(uint64_t counts[8])
-{
-	const msw_stage_t &m = ssg_msw_last;
 	memset(counts, 0, 8 * sizeof(uint64_t));
 	counts[0] = m.windows; counts[1] = m.from_slots; counts[2] = m.taken; counts[3] = m.left; counts[4] = m.listed; counts[5] = m.cells; counts[6] = m.left_windows;
 }
-
-int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *read_off, const int64_t *reg_off, const ssg_alnreg_t *regs,
-                   const uint8_t *fixed, const ssg_pestat_t pes[4], int headroom, int64_t *out_off, ssg_alnreg_t **regs_out, int32_t *n_out, int32_t *err, uint64_t counts[8])
-{
-	CHK(ssg_need_device());
-	CHK(dbg_check_regs(idx, n_pairs, reg_off, regs, "ssg_dbg_matesw"));
-	for (int d = 0; d < 4; ++d) if (!pes[d].failed && !(pes[d].low >= 0 && pes[d].low <= pes[d].high)) { ssg_err_msg = "ssg_dbg_matesw: an orientation that has not failed needs 0 <= low <= high"; return SSG_EINVAL; }
-	const int n_reads = 2 * n_pairs, block = 256;
-	*regs_out = 0; memset(counts, 0, 8 * sizeof(uint64_t));
-	if (n_pairs == 0) { out_off[0] = 0; return SSG_OK; }
-	int max_len = 0;
-	for (int r = 0; r < n_reads; ++r) {
-		if (read_off[r + 1] <= read_off[r] || (r == 0 && read_off[0] != 0)) { ssg_err_msg = "ssg_dbg_matesw: read_off must start at 0 and increase"; return SSG_EINVAL; }
-		max_len = std::max<int>(max_len, (int)std::min<int64_t>(read_off[r + 1] - read_off[r], 1 << 20));
-	}
-	if (max_len > SSG_MAX_READ_LEN) { ssg_err_msg = "reads longer than " SSG_STR(SSG_MAX_READ_LEN) " bases are outside this build's scope"; return SSG_EINVAL; }
-	for (int64_t k = 0; k < read_off[n_reads]; ++k) if (seq[k] > 4) { ssg_err_msg = "ssg_dbg_matesw: bases are codes 0 .. 4"; return SSG_EINVAL; }
-	for (int r = 0; r < n_reads; ++r) for (int64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) if (regs[k].qe > (int)(read_off[r + 1] - read_off[r])) { ssg_err_msg = "ssg_dbg_matesw: a region ends beyond its read"; return SSG_EINVAL; }
-	/* the slices as ssg_k_pair_caps sizes them (own regions + 4 rescued hits per anchor of the mate + 4), or own regions + headroom */
-	std::vector<int32_t> hn((size_t)n_reads), hkey((size_t)n_pairs); std::vector<int64_t> r2off((size_t)n_reads + 1, 0); std::vector<uint8_t> hfix((size_t)n_reads, 0);
-	for (int r = 0; r < n_reads; ++r) hn[r] = (int32_t)(reg_off[r + 1] - reg_off[r]);
-	for (int r = 0; r < n_reads; ++r) { const int m = hn[r ^ 1]; r2off[r + 1] = r2off[r] + hn[r] + (headroom >= 0 ? headroom : 4 * std::min(m, opt->max_matesw) + 4); if (fixed) hfix[r] = fixed[r] ? 1 : 0; }
-	for (int p = 0; p < n_pairs; ++p) hkey[p] = hn[2 * p] + hn[2 * p + 1];
-	const int64_t tot = reg_off[n_reads], t2 = r2off[n_reads];
-	dbuf<uint8_t> d_seq((size_t)read_off[n_reads] + 1), d_fixed((size_t)n_reads); dbuf<int64_t> d_roff((size_t)n_reads + 1), d_off((size_t)n_reads + 1), d_r2off((size_t)n_reads + 1);
-	dbuf<ssg_alnreg_t> d_regs((size_t)tot + 1), d_regs2((size_t)t2 + 1); dbuf<int32_t> d_n((size_t)n_reads), d_pb((size_t)n_pairs), d_pkey((size_t)n_pairs), d_pw((size_t)n_pairs), d_perr((size_t)n_pairs);
-	dbuf<ssg_pestat_t> d_pes(4); dbuf<unsigned long long> d_cnt(3); dbuf<unsigned int> d_q(1);
-	CHKA(d_seq); CHKA(d_fixed); CHKA(d_roff); CHKA(d_off); CHKA(d_r2off); CHKA(d_regs); CHKA(d_regs2); CHKA(d_n); CHKA(d_pb); CHKA(d_pkey); CHKA(d_pw); CHKA(d_perr); CHKA(d_pes); CHKA(d_cnt); CHKA(d_q);
-	CHK(d_seq.up(seq, (size_t)read_off[n_reads])); CHK(d_fixed.up(hfix.data(), (size_t)n_reads)); CHK(d_roff.up(read_off, (size_t)n_reads + 1)); CHK(d_off.up(reg_off, (size_t)n_reads + 1));
-	CHK(d_r2off.up(r2off.data(), (size_t)n_reads + 1)); CHK(d_regs.up(regs, (size_t)tot)); CHK(d_regs2.zero()); CHK(d_n.up(hn.data(), (size_t)n_reads)); CHK(d_pb.zero()); CHK(d_pkey.up(hkey.data(), (size_t)n_pairs));
-	CHK(d_perr.zero()); CHK(d_pes.up(pes, 4)); CHK(d_cnt.zero()); CHK(d_q.zero());
-	CHK(dev_order_desc(d_pkey.p, d_pw.p, n_pairs)); CHK(rt_sync());
-	SSG_LAUNCH(ssg_k_copy_regs, (n_reads + block - 1) / block, block, 0, n_reads, d_off.p, d_regs.p, d_n.p, d_r2off.p, d_regs2.p);
-	msw_stage_t ms;
-	CHK(run_matesw(idx, opt, n_pairs, d_seq.p, d_roff.p, max_len, d_r2off.p, d_regs2.p, d_n.p, d_pb.p, d_pes.p, d_pw.p, d_fixed.p, d_perr.p, d_cnt.p, d_q.p, &ms));
-	ssg_alnreg_t *out = (ssg_alnreg_t*)malloc(sizeof(ssg_alnreg_t) * (size_t)(t2 + 1));
-	if (!out) { ssg_err_msg = "host allocation failed: regions"; return SSG_ENOMEM; }
-	int rc = d_regs2.down(out, (size_t)t2);
-	if (!rc) rc = d_n.down(n_out, (size_t)n_reads);
-	if (!rc) rc = d_perr.down(err, (size_t)n_pairs);
-	if (rc) { free(out); return rc; }
-	memcpy(out_off, r2off.data(), ((size_t)n_reads + 1) * sizeof(int64_t));
-	counts[0] = ms.windows; counts[1] = ms.from_slots; counts[2] = ms.taken; counts[3] = ms.left; counts[4] = ms.listed; counts[5] = ms.cells; counts[6] = ms.left_windows;
-	*regs_out = out;
-	return SSG_OK;
-}
-
-} /* extern "C" */
-
+extern "C" void ssg_dbg_matesw_last(uint64_t counts[8]) { msw_counts(ssg_msw_last, counts); }
 
 /* single-end reads (upstream mem_process_seqs without MEM_F_PE): stage 1 as for pairs, then every read on its own -- primary marking with
  * id = id0 + r (upstream's n_processed + i), the list of records (ssg_k_se_final), CIGAR / NM / MD.  No insert-size model, no mate rescue, no pairing. */
