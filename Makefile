@@ -13,7 +13,7 @@ lib: speedseq_amd/libssgpu.so
 # Every object's prerequisites come from the compiler (-MMD): no hand-kept header lists, so no object can be stale against a shared
 # declaration (round 3 shipped variant libraries linked from objects of different ages).
 # the translation units hipcc compiles (sam_format.cpp is plain C++)
-UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_msw_replay ssg_bam ssg_coll
+UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_bam_select ssg_msw_replay ssg_bam ssg_coll
 HIPOBJS = $(UNITS:%=$(CSRC)/%.o)
 HIPSRCS = $(UNITS:%=$(CSRC)/%.cpp)
 $(HIPOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp
@@ -103,6 +103,15 @@ tests/emu/bam_scan_fuzz: tools/dbg/bam_scan_fuzz.cpp $(CSRC)/ssg_bam_scan.cpp $(
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
 		tools/dbg/bam_scan_fuzz.cpp $(CSRC)/ssg_bam_scan.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp tests/emu/emu.cpp -o $@ -lpthread -lz
 
+# memory safety and exactness of the selection behind the scan (k_bam_select.h): the emulated kernels under AddressSanitizer and UndefinedBehaviorSanitizer on 3000
+# seeded streams, region lists and filter programs, every refusal among them, and the .bai reader (host/bamio.h) on seeded truncations and mutations of a real index (tools/dbg/bam_select_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
+SELFUZZ_SRCS = $(CSRC)/ssg_bam_select.cpp $(CSRC)/ssg_bam_scan.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp
+fuzz-bam-select: tests/emu/bam_select_fuzz
+	tests/emu/bam_select_fuzz
+tests/emu/bam_select_fuzz: tools/dbg/bam_select_fuzz.cpp $(HOST)/bamio.h $(SELFUZZ_SRCS) tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
+		tools/dbg/bam_select_fuzz.cpp $(SELFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
+
 # memory safety of the chained match finder of levels 7-9 (k_bgzf_deep.h): the emulated kernel under AddressSanitizer and UndefinedBehaviorSanitizer on the
 # kernel's edge payloads and 3000 seeded ones, every stream inflated with zlib (tools/dbg/deflate_deep_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
 DEEPFUZZ_SRCS = $(CSRC)/ssg_bgzf.cpp $(CSRC)/ssg_bgzf_deep.cpp $(CSRC)/ssg_bgzf_frame.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_bgzf_inflate.cpp
@@ -113,9 +122,9 @@ tests/emu/deflate_deep_fuzz: tools/dbg/deflate_deep_fuzz.cpp $(DEEPFUZZ_SRCS) te
 		tools/dbg/deflate_deep_fuzz.cpp $(DEEPFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
 
 clean:
-	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/deflate_deep_fuzz $(CSRC)/*.o
+	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz $(CSRC)/*.o
 	$(MAKE) -C oracle clean
-.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-deflate-deep
+.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep
 
 # A/B builds of the device library with other compile-time parameters (bench / tests: SSGPU_LIB=speedseq_amd/libssgpu_$(NAME).so); never the
 # default.  The units named in VUNITS (default: all) are compiled with VFLAGS into build/$(NAME)/; the others are the product build's

@@ -467,12 +467,33 @@ void ssg_recs_free(ssg_recs_t *r);
  *                    on it.  A property of the file (a writer that splits records over blocks), not an error of the call: callers fall back on it.
  *   Nothing is valid in loc / key / ent unless 0 is returned; the store is unchanged by every outcome.  SSG_EINVAL for a chunk that does not exist or is released,
  *   or hints that do not ascend inside the chunk.
+ * ssg_recs_select: ssg_recs_scan with the decision behind it, taken on the device (k_bam_select.h): the same walk, the same states, SSG_EIO, SSG_EALIGN and
+ *   SSG_EINVAL with the same words in ssg_last_error() (under this entry's name).  *n_rec: the records scanned.  A record is kept when it overlaps a region and
+ *   the filter program leaves 1; *n_sel: the records kept, and only their loc / key / ent come back, in stream order (host arrays of `cap' elements).
+ *     reg[0 .. n_reg): 0-based, half-open (tid, beg, end), sorted by (tid, beg), disjoint and not adjacent (the caller has merged them).  A record overlaps a
+ *       region when the tid is equal, pos < reg.end and rec.end > reg.beg, rec.end as in ent (bam_endpos); a record with tid < 0 overlaps nothing.
+ *       n_reg == 0: no region test.
+ *     prog[0 .. n_prog): a postfix program over a stack of booleans, at most SSG_FOP_MAX operations.  SSG_FOP_FLAG pushes (flag & value) != 0; SSG_FOP_EQ ..
+ *       SSG_FOP_GE push `field <cmp> value' with the field named by arg (SSG_FLD_*: MAPQ, tid, mate tid, isize, l_seq, flag; signed 32-bit comparisons);
+ *       SSG_FOP_AND / SSG_FOP_OR replace the two topmost values, SSG_FOP_NOT the topmost.  n_prog == 0: every record passes.
+ *     SSG_EOVERFLOW  cap < *n_sel: *n_rec and *n_sel are set, nothing is written to loc / key / ent.  cap == 0 with loc, key and ent all NULL is the counting
+ *                    form: it returns 0 and nothing but the two numbers.
+ *     SSG_EINVAL     also for regions that are unsorted, overlap, touch, or have beg >= end, beg < 0 or tid < 0; a program of more than SSG_FOP_MAX operations, one
+ *                    that underflows the stack or does not leave exactly one value, an unknown operation or field (each named in ssg_last_error()); and while
+ *                    an order is declared (ssg_recs_reopen first).  The store is unchanged by every outcome.
  * ssg_recs_reopen: drops a declared order: the store takes appends again, and a later ssg_recs_order declares a new stream.
  * ssg_recs_release: frees a chunk's device memory and returns its bytes to the capacity.  The id stays taken (later chunks keep theirs); ssg_recs_order refuses
  *   a location in a released chunk with SSG_EINVAL.  Refused (SSG_EINVAL) while an order is declared: ssg_recs_reopen first. */
 typedef struct { int32_t tid, pos, end; uint32_t flag, len, pad; } ssg_bam_ent_t;
 int ssg_recs_append_bgzf(ssg_recs_t *r, const uint8_t *members, const uint64_t *moff, long n_blocks, uint32_t *chunk_id, uint64_t *out_off, int32_t *status);
 int ssg_recs_scan(ssg_recs_t *r, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t cap, uint64_t *n_rec, uint64_t *loc, uint64_t *key, ssg_bam_ent_t *ent);
+typedef struct { int32_t tid, beg, end; } ssg_bam_region_t;
+typedef struct { uint8_t op, arg; uint16_t pad; int32_t value; } ssg_bam_fop_t;
+#define SSG_FOP_MAX 64
+enum { SSG_FOP_FLAG = 0, SSG_FOP_AND = 1, SSG_FOP_OR = 2, SSG_FOP_NOT = 3, SSG_FOP_EQ = 4, SSG_FOP_NE = 5, SSG_FOP_LT = 6, SSG_FOP_LE = 7, SSG_FOP_GT = 8, SSG_FOP_GE = 9 };
+enum { SSG_FLD_MAPQ = 0, SSG_FLD_REF_ID = 1, SSG_FLD_MATE_REF_ID = 2, SSG_FLD_TLEN = 3, SSG_FLD_SEQ_LEN = 4, SSG_FLD_FLAG = 5 };
+int ssg_recs_select(ssg_recs_t *r, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, const ssg_bam_region_t *reg, int64_t n_reg, const ssg_bam_fop_t *prog, int n_prog,
+                    uint64_t cap, uint64_t *n_rec, uint64_t *n_sel, uint64_t *loc, uint64_t *key, ssg_bam_ent_t *ent);
 int ssg_recs_reopen(ssg_recs_t *r);
 int ssg_recs_release(ssg_recs_t *r, uint32_t chunk_id);
 /* bytes of device memory that are free / that the calling thread's device has: what a caller sizes a store from */

@@ -641,6 +641,45 @@ def recs_scan(lib, recs, chunk_id, hint, first=0, cap=None):
     return rc, n, loc, key, ent
 
 
+BAM_REGION_DT = np.dtype([("tid", "i4"), ("beg", "i4"), ("end", "i4")])
+BAM_FOP_DT = np.dtype([("op", "u1"), ("arg", "u1"), ("pad", "u2"), ("value", "i4")])
+FOP_MAX = 64
+FOP_FLAG, FOP_AND, FOP_OR, FOP_NOT, FOP_EQ, FOP_NE, FOP_LT, FOP_LE, FOP_GT, FOP_GE = range(10)
+FLD_MAPQ, FLD_REF_ID, FLD_MATE_REF_ID, FLD_TLEN, FLD_SEQ_LEN, FLD_FLAG = range(6)
+
+
+def recs_select(lib, recs, chunk_id, hint, first=0, regions=(), prog=(), cap=None, counting=False):
+    """ssg_recs_select: ssg_recs_scan with the decision taken on the device.  regions: (tid, beg, end) triples, 0-based half-open, sorted and disjoint; prog:
+    (op, arg, value) triples of the postfix filter program.  Returns (rc, n_rec, n_sel, loc, key, ent) as recs_scan does, the arrays holding the kept records;
+    counting=True is the counting form (cap 0, no arrays: loc, key and ent are None).  rc 0, SSG_EOVERFLOW (-75), SSG_EIO (-5), SSG_EALIGN (-71) or
+    SSG_EINVAL (-22: the message is in ssg_last_error()); every other return code raises."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_hints = len(hint) - 1
+    reg = np.array([tuple(x) for x in regions], dtype=BAM_REGION_DT)
+    fop = np.array([(op, arg, 0, value) for op, arg, value in prog], dtype=BAM_FOP_DT)
+    n_rec, n_sel = C.c_uint64(0), C.c_uint64(0)
+    head = (recs.h, C.c_uint32(chunk_id), _ptr(hint), C.c_int64(n_hints), C.c_uint64(first), _ptr(reg) if len(reg) else None, C.c_int64(len(reg)),
+            _ptr(fop) if len(fop) else None, C.c_int(len(fop)))
+    if counting:
+        rc = lib.l.ssg_recs_select(*head, C.c_uint64(0), C.byref(n_rec), C.byref(n_sel), None, None, None)
+        if rc not in (0, -5, -22, -75, SSG_EALIGN):
+            lib._chk(rc)
+        return rc, int(n_rec.value), int(n_sel.value), None, None, None
+    if cap is None:
+        cap = int(hint[-1]) // 36 if n_hints >= 0 and len(hint) else 0
+    loc = np.full(cap + 1, 0xABABABABABABABAB, dtype=np.uint64)
+    key = np.full(cap + 1, 0xABABABABABABABAB, dtype=np.uint64)
+    ent = np.frombuffer(np.full((cap + 1) * BAM_ENT_DT.itemsize, 0xAB, dtype=np.uint8).tobytes(), dtype=BAM_ENT_DT).copy()
+    rc = lib.l.ssg_recs_select(*head, C.c_uint64(cap), C.byref(n_rec), C.byref(n_sel), _ptr(loc), _ptr(key), _ptr(ent))
+    if rc not in (0, -5, -22, -75, SSG_EALIGN):
+        lib._chk(rc)
+    n = int(n_sel.value)
+    if rc == 0:
+        assert int(loc[cap]) == 0xABABABABABABABAB and int(key[cap]) == 0xABABABABABABABAB and ent[cap:].tobytes() == b"\xab" * BAM_ENT_DT.itemsize   # nothing behind cap
+        return rc, int(n_rec.value), n, loc[:n], key[:n], ent[:n]
+    return rc, int(n_rec.value), n, loc, key, ent
+
+
 def device_memory(lib):
     """ssg_device_memory: (free, total) bytes of the calling thread's device."""
     f, t = C.c_uint64(0), C.c_uint64(0)

@@ -17,6 +17,64 @@
 
 static inline uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
+/* the scan with its results left in device memory (ssg_recs_int.h): ssg_recs_scan copies them out, ssg_recs_select (ssg_bam_select.cpp) decides on them there */
+int recs_scan_dev(ssg_recs *r, const char *who_, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t cap, bool arrays, uint64_t *n_rec, recs_scan_dev_t &o)
+{
+	const std::string who(who_);
+	CHK(recs_usable(r, who_));
+	if (!n_rec) { ssg_err_msg = who + ": no place for the number of records"; return SSG_EINVAL; }
+	*n_rec = 0;
+	if (chunk_id >= r->d_chunk.size() || !r->d_chunk[chunk_id]) { ssg_err_msg = who + ": chunk " + std::to_string(chunk_id) + " does not exist or is released"; return SSG_EINVAL; }
+	if (n_hints < 0 || (n_hints > 0 && !hint)) { ssg_err_msg = who + ": n_hints < 0, or no hint[]"; return SSG_EINVAL; }
+	if (n_hints == 0) return 0;
+	/* everything the walk compares its offsets with is checked here */
+	const uint64_t clen = r->len[chunk_id], total = hint[n_hints];
+	for (int64_t b = 0; b < n_hints; ++b) if (hint[b + 1] < hint[b]) { ssg_err_msg = who + ": hint[] decreases at " + std::to_string(b); return SSG_EINVAL; }
+	if (total > clen) { ssg_err_msg = who + ": hint[n_hints] lies behind the chunk's " + std::to_string(clen) + " bytes"; return SSG_EINVAL; }
+	if (first > total) { ssg_err_msg = who + ": `first' lies behind hint[n_hints]"; return SSG_EINVAL; }
+	const uint64_t grid = ((uint64_t)n_hints + 255) / 256;
+	if (grid > 0x7fffffffu) { ssg_err_msg = who + ": more than 2^31 hints in one call"; return SSG_EINVAL; }
+	const uint8_t *const d_chunk = r->d_chunk[chunk_id];
+	const uint64_t tag = (uint64_t)chunk_id << 40;
+	dbuf<uint64_t> d_hint((size_t)n_hints + 1), d_cnt((size_t)n_hints + 1), d_base((size_t)n_hints + 1), d_stop((size_t)n_hints);
+	dbuf<uint32_t> d_state((size_t)n_hints);
+	if (!d_hint.ok() || !d_cnt.ok() || !d_base.ok() || !d_stop.ok() || !d_state.ok()) { ssg_err_msg = "device allocation failed: the hints of a record scan"; return SSG_ENOMEM; }
+	CHK(d_hint.up(hint, (size_t)n_hints + 1));
+	CHK(rt_memset(d_cnt.p + n_hints, 0, 8));   /* (one count more: the scan's last value is the total) */
+	SSG_LAUNCH(ssg_k_bam_walk, grid, 256, 0, d_chunk, total, (const uint64_t*)d_hint.p, n_hints, first, d_cnt.p, d_stop.p, d_state.p, (const uint64_t*)0, tag, (uint64_t)0, (uint64_t*)0);
+	CHK((prim_exsum<uint64_t, uint64_t>(d_cnt.p, d_base.p, n_hints + 1)));
+	CHK(rt_sync());
+	std::vector<uint32_t> state((size_t)n_hints);
+	CHK(d_state.down(state.data(), (size_t)n_hints));
+	for (int64_t b = 0; b < n_hints; ++b) {
+		if (state[(size_t)b] == BS_OK) continue;
+		uint64_t stop = 0; CHK(rt_d2h(&stop, d_stop.p + b, 8));
+		if (state[(size_t)b] == BS_SKEW) {
+			ssg_err_msg = who + ": not record-aligned at hint " + std::to_string(b) + ": the walk that entered at offset " + std::to_string(std::max(hint[b], first)) + " passed hint " + std::to_string(b + 1) +
+			              " (offset " + std::to_string(hint[b + 1]) + ") and stopped at offset " + std::to_string(stop) + ": no record begins there";
+			return SSG_EALIGN;
+		}
+		ssg_err_msg = who + ": malformed record at offset " + std::to_string(stop) + (state[(size_t)b] == BS_SMALL ? ": a block_size below 32" : ": it runs past the end of the stream (offset " + std::to_string(total) + ")");
+		return SSG_EIO;
+	}
+	uint64_t n = 0; CHK(rt_d2h(&n, d_base.p + n_hints, 8));
+	*n_rec = n;
+	if (n > cap) { ssg_err_msg = who + ": " + std::to_string(n) + " records, room for " + std::to_string(cap); return SSG_EOVERFLOW; }
+	if (n == 0) return 0;
+	if (!arrays) { ssg_err_msg = who + ": no loc[] / key[] / ent[]"; return SSG_EINVAL; }
+	const uint64_t rgrid = (n + 255) / 256;
+	if (rgrid > 0x7fffffffu) { ssg_err_msg = who + ": more than 2^39 records in one call"; return SSG_EINVAL; }
+	dbuf<uint64_t> &d_loc = o.loc, &d_key = o.key; dbuf<ssg_bam_ent_t> &d_ent = o.ent; dbuf<unsigned long long> d_bad(1);
+	if (!d_loc.alloc((size_t)n) || !d_key.alloc((size_t)n) || !d_ent.alloc((size_t)n) || !d_bad.ok()) { ssg_err_msg = "device allocation failed: the records of a scan"; return SSG_ENOMEM; }
+	CHK(rt_memset(d_bad.p, 0xff, 8));
+	SSG_LAUNCH(ssg_k_bam_walk, grid, 256, 0, d_chunk, total, (const uint64_t*)d_hint.p, n_hints, first, d_cnt.p, d_stop.p, d_state.p, (const uint64_t*)d_base.p, tag, n, d_loc.p);
+	SSG_LAUNCH(ssg_k_bam_fields, rgrid, 256, 0, d_chunk, (const uint64_t*)d_loc.p, (int64_t)n, d_key.p, d_ent.p, d_bad.p);
+	CHK(rt_sync());
+	unsigned long long bad = 0; CHK(d_bad.down(&bad, 1));
+	if (bad != ~0ull) { ssg_err_msg = who + ": malformed record at offset " + std::to_string(bad) + ": l_qname + 4 n_cigar exceeds block_size - 32"; return SSG_EIO; }
+	return 0;
+}
+
 extern "C" {
 
 int ssg_device_memory(uint64_t *free_bytes, uint64_t *total_bytes)
@@ -85,58 +143,10 @@ int ssg_recs_append_bgzf(ssg_recs_t *r, const uint8_t *members, const uint64_t *
 
 int ssg_recs_scan(ssg_recs_t *r, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t cap, uint64_t *n_rec, uint64_t *loc, uint64_t *key, ssg_bam_ent_t *ent)
 {
-	CHK(recs_usable(r, "ssg_recs_scan"));
-	if (!n_rec) { ssg_err_msg = "ssg_recs_scan: no place for the number of records"; return SSG_EINVAL; }
-	*n_rec = 0;
-	if (chunk_id >= r->d_chunk.size() || !r->d_chunk[chunk_id]) { ssg_err_msg = "ssg_recs_scan: chunk " + std::to_string(chunk_id) + " does not exist or is released"; return SSG_EINVAL; }
-	if (n_hints < 0 || (n_hints > 0 && !hint)) { ssg_err_msg = "ssg_recs_scan: n_hints < 0, or no hint[]"; return SSG_EINVAL; }
-	if (n_hints == 0) return 0;
-	/* everything the walk compares its offsets with is checked here */
-	const uint64_t clen = r->len[chunk_id], total = hint[n_hints];
-	for (int64_t b = 0; b < n_hints; ++b) if (hint[b + 1] < hint[b]) { ssg_err_msg = "ssg_recs_scan: hint[] decreases at " + std::to_string(b); return SSG_EINVAL; }
-	if (total > clen) { ssg_err_msg = "ssg_recs_scan: hint[n_hints] lies behind the chunk's " + std::to_string(clen) + " bytes"; return SSG_EINVAL; }
-	if (first > total) { ssg_err_msg = "ssg_recs_scan: `first' lies behind hint[n_hints]"; return SSG_EINVAL; }
-	const uint64_t grid = ((uint64_t)n_hints + 255) / 256;
-	if (grid > 0x7fffffffu) { ssg_err_msg = "ssg_recs_scan: more than 2^31 hints in one call"; return SSG_EINVAL; }
-	const uint8_t *const d_chunk = r->d_chunk[chunk_id];
-	const uint64_t tag = (uint64_t)chunk_id << 40;
-	dbuf<uint64_t> d_hint((size_t)n_hints + 1), d_cnt((size_t)n_hints + 1), d_base((size_t)n_hints + 1), d_stop((size_t)n_hints);
-	dbuf<uint32_t> d_state((size_t)n_hints);
-	if (!d_hint.ok() || !d_cnt.ok() || !d_base.ok() || !d_stop.ok() || !d_state.ok()) { ssg_err_msg = "device allocation failed: the hints of a record scan"; return SSG_ENOMEM; }
-	CHK(d_hint.up(hint, (size_t)n_hints + 1));
-	CHK(rt_memset(d_cnt.p + n_hints, 0, 8));   /* (one count more: the scan's last value is the total) */
-	SSG_LAUNCH(ssg_k_bam_walk, grid, 256, 0, d_chunk, total, (const uint64_t*)d_hint.p, n_hints, first, d_cnt.p, d_stop.p, d_state.p, (const uint64_t*)0, tag, (uint64_t)0, (uint64_t*)0);
-	CHK((prim_exsum<uint64_t, uint64_t>(d_cnt.p, d_base.p, n_hints + 1)));
-	CHK(rt_sync());
-	std::vector<uint32_t> state((size_t)n_hints);
-	CHK(d_state.down(state.data(), (size_t)n_hints));
-	for (int64_t b = 0; b < n_hints; ++b) {
-		if (state[(size_t)b] == BS_OK) continue;
-		uint64_t stop = 0; CHK(rt_d2h(&stop, d_stop.p + b, 8));
-		if (state[(size_t)b] == BS_SKEW) {
-			ssg_err_msg = "ssg_recs_scan: not record-aligned at hint " + std::to_string(b) + ": the walk that entered at offset " + std::to_string(std::max(hint[b], first)) + " passed hint " + std::to_string(b + 1) +
-			              " (offset " + std::to_string(hint[b + 1]) + ") and stopped at offset " + std::to_string(stop) + ": no record begins there";
-			return SSG_EALIGN;
-		}
-		ssg_err_msg = std::string("ssg_recs_scan: malformed record at offset ") + std::to_string(stop) + (state[(size_t)b] == BS_SMALL ? ": a block_size below 32" : ": it runs past the end of the stream (offset " + std::to_string(total) + ")");
-		return SSG_EIO;
-	}
-	uint64_t n = 0; CHK(rt_d2h(&n, d_base.p + n_hints, 8));
-	*n_rec = n;
-	if (n > cap) { ssg_err_msg = "ssg_recs_scan: " + std::to_string(n) + " records, room for " + std::to_string(cap); return SSG_EOVERFLOW; }
-	if (n == 0) return 0;
-	if (!loc || !key || !ent) { ssg_err_msg = "ssg_recs_scan: no loc[] / key[] / ent[]"; return SSG_EINVAL; }
-	const uint64_t rgrid = (n + 255) / 256;
-	if (rgrid > 0x7fffffffu) { ssg_err_msg = "ssg_recs_scan: more than 2^39 records in one call"; return SSG_EINVAL; }
-	dbuf<uint64_t> d_loc((size_t)n), d_key((size_t)n); dbuf<ssg_bam_ent_t> d_ent((size_t)n); dbuf<unsigned long long> d_bad(1);
-	if (!d_loc.ok() || !d_key.ok() || !d_ent.ok() || !d_bad.ok()) { ssg_err_msg = "device allocation failed: the records of a scan"; return SSG_ENOMEM; }
-	CHK(rt_memset(d_bad.p, 0xff, 8));
-	SSG_LAUNCH(ssg_k_bam_walk, grid, 256, 0, d_chunk, total, (const uint64_t*)d_hint.p, n_hints, first, d_cnt.p, d_stop.p, d_state.p, (const uint64_t*)d_base.p, tag, n, d_loc.p);
-	SSG_LAUNCH(ssg_k_bam_fields, rgrid, 256, 0, d_chunk, (const uint64_t*)d_loc.p, (int64_t)n, d_key.p, d_ent.p, d_bad.p);
-	CHK(rt_sync());
-	unsigned long long bad = 0; CHK(d_bad.down(&bad, 1));
-	if (bad != ~0ull) { ssg_err_msg = "ssg_recs_scan: malformed record at offset " + std::to_string(bad) + ": l_qname + 4 n_cigar exceeds block_size - 32"; return SSG_EIO; }
-	CHK(d_loc.down(loc, (size_t)n)); CHK(d_key.down(key, (size_t)n)); CHK(d_ent.down(ent, (size_t)n));
+	recs_scan_dev_t o;
+	CHK(recs_scan_dev(r, "ssg_recs_scan", chunk_id, hint, n_hints, first, cap, loc && key && ent, n_rec, o));
+	const size_t n = (size_t)*n_rec;
+	if (n) { CHK(o.loc.down(loc, n)); CHK(o.key.down(key, n)); CHK(o.ent.down(ent, n)); }
 	return 0;
 }
 

@@ -32,4 +32,9 @@ static inline int recs_usable(const ssg_recs *r, const char *who)
 	if (r->dev != ssg_cur_dev) { ssg_err_msg = std::string(who) + ": the record store lives on device " + std::to_string(r->dev) + ", the calling thread drives device " + std::to_string(ssg_cur_dev); return SSG_EINVAL; }
 	return 0;
 }
+/* ssg_recs_scan with loc, key and ent of the chunk's records left in device memory (ssg_bam_scan.cpp): every check, state and message of the scan, the messages
+ * under the caller's name `who'.  `arrays': the caller has a place for records (without one, a chunk that holds records is SSG_EINVAL, as the scan says it).
+ * o.loc / o.key / o.ent hold *n_rec elements when 0 is returned and *n_rec > 0. */
+struct recs_scan_dev_t { dbuf<uint64_t> loc, key; dbuf<ssg_bam_ent_t> ent; };
+int recs_scan_dev(ssg_recs *r, const char *who, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t cap, bool arrays, uint64_t *n_rec, recs_scan_dev_t &o);
 #endif

@@ -564,4 +564,85 @@ struct bai_t {
 		fclose(fp);
 	}
 };
+
+/* A .bai read back (hts_idx_load / hts_itr_query, htslib hts.c): parse() takes the file's bytes and checks every count and offset against their length before
+ * anything is sized from it -- a huge n_bin, n_chunk or n_intv ends in a refusal, not in an allocation; query() gives the candidate chunks of a region as
+ * hts_itr_query does: the bins of reg2bins, without the chunks that end at or below the linear index's offset of the region's first 16 kb window.
+ * bai_chunks_merge sorts chunks and merges those that overlap, touch or meet in one block. */
+struct bai_reader_t {
+	struct chunk_t { uint64_t u, v; };
+	struct bin_t { uint32_t bin; size_t first, n; };                   /* chunks[first .. first + n) */
+	struct ref_t { std::vector<bin_t> bins; std::vector<chunk_t> chunks; std::vector<uint64_t> lin; };
+	std::vector<ref_t> refs;
+	bool parse(const uint8_t *p, size_t n, std::string &err)
+	{
+		refs.clear();
+		size_t o = 0;
+		auto room = [&](uint64_t count, uint64_t each) { return count <= (n - o) / each; };
+		auto r32 = [&](int32_t &v) { if (n - o < 4) return false; memcpy(&v, p + o, 4); o += 4; return true; };
+		if (n < 8 || memcmp(p, "BAI\1", 4)) { err = "not a BAI file (wrong magic)"; return false; }
+		o = 4;
+		int32_t n_ref = 0; r32(n_ref);
+		if (n_ref < 0 || !room((uint64_t)n_ref, 8)) { err = "the reference count " + std::to_string(n_ref) + " does not fit the file"; return false; }
+		refs.resize((size_t)n_ref);
+		for (int32_t t = 0; t < n_ref; ++t) {
+			ref_t &R = refs[(size_t)t];
+			int32_t n_bin = 0, n_intv = 0;
+			if (!r32(n_bin) || n_bin < 0 || !room((uint64_t)n_bin, 8)) { err = "truncated, or a bin count that does not fit the file (reference " + std::to_string(t) + ")"; return false; }
+			R.bins.reserve((size_t)n_bin);
+			for (int32_t b = 0; b < n_bin; ++b) {
+				int32_t bin = 0, n_chunk = 0;
+				if (!r32(bin) || !r32(n_chunk) || n_chunk < 0 || !room((uint64_t)n_chunk, 16)) { err = "truncated, or a chunk count that does not fit the file (reference " + std::to_string(t) + ")"; return false; }
+				bin_t B; B.bin = (uint32_t)bin; B.first = R.chunks.size(); B.n = (size_t)n_chunk;
+				R.chunks.resize(B.first + B.n);
+				if (B.n) memcpy(R.chunks.data() + B.first, p + o, 16 * B.n);
+				o += 16 * B.n; R.bins.push_back(B);
+			}
+			if (!r32(n_intv) || n_intv < 0 || !room((uint64_t)n_intv, 8)) { err = "truncated, or an interval count that does not fit the file (reference " + std::to_string(t) + ")"; return false; }
+			R.lin.resize((size_t)n_intv);
+			if (n_intv) memcpy(R.lin.data(), p + o, 8 * (size_t)n_intv);
+			o += 8 * (size_t)n_intv;
+		}
+		if (n - o != 0 && n - o != 8) { err = "bytes behind the last reference that are not the count of unplaced reads"; return false; }
+		return true;
+	}
+	bool load(const char *fn, std::string &err)
+	{
+		FILE *fp = fopen(fn, "rb");
+		if (!fp) { err = "cannot be opened"; return false; }
+		std::vector<uint8_t> b; uint8_t tmp[65536]; size_t k;
+		while ((k = fread(tmp, 1, sizeof(tmp), fp)) > 0) b.insert(b.end(), tmp, tmp + k);
+		fclose(fp);
+		return parse(b.data(), b.size(), err);
+	}
+	/* the candidate chunks of [beg, end) on tid (0-based, half-open), appended to out */
+	void query(int tid, int64_t beg, int64_t end, std::vector<chunk_t> &out) const
+	{
+		if (tid < 0 || (size_t)tid >= refs.size() || beg >= end) return;
+		const ref_t &R = refs[(size_t)tid];
+		if (end > ((int64_t)1 << 29)) end = (int64_t)1 << 29;
+		if (beg >= end) return;
+		uint64_t min_off = 0;
+		if (!R.lin.empty()) min_off = (size_t)(beg >> 14) >= R.lin.size() ? R.lin.back() : R.lin[(size_t)(beg >> 14)];
+		for (const bin_t &B : R.bins) {
+			if (B.bin >= 37449) continue;                                  /* (the pseudo-bin of the counts) */
+			int l = 0; uint32_t t = 0;                                     /* the bin's level and first bin of that level: 0, 1, 9, 73, 585, 4681 */
+			while (l < 5 && B.bin >= t + (1u << (3 * l))) { t += 1u << (3 * l); ++l; }
+			const int s = 29 - 3 * l;                                       /* a bin of level l spans 2^s bases */
+			const uint32_t k = B.bin - t;
+			if (k < (uint32_t)(beg >> s) || k > (uint32_t)((end - 1) >> s)) continue;   /* reg2bins */
+			for (size_t c = 0; c < B.n; ++c) { const chunk_t &ch = R.chunks[B.first + c]; if (ch.v > min_off && ch.u < ch.v) out.push_back(ch); }
+		}
+	}
+};
+static inline void bai_chunks_merge(std::vector<bai_reader_t::chunk_t> &c)
+{
+	std::sort(c.begin(), c.end(), [](const bai_reader_t::chunk_t &a, const bai_reader_t::chunk_t &b) { return a.u != b.u ? a.u < b.u : a.v < b.v; });
+	size_t m = 0;
+	for (size_t k = 0; k < c.size(); ++k) {
+		if (m && (c[m - 1].v >= c[k].u || c[m - 1].v >> 16 >= c[k].u >> 16)) { if (c[m - 1].v < c[k].v) c[m - 1].v = c[k].v; }
+		else c[m++] = c[k];
+	}
+	c.resize(m);
+}
 #endif

@@ -31,7 +31,8 @@
 static double wall() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 static bool dbg() { static int d = -1; if (d < 0) d = (getenv("SSG_DEBUG") || getenv("SSG_SORT_LOG")) ? 1 : 0; return d != 0; }
 static int hw_threads() { unsigned n = std::thread::hardware_concurrency(); return n ? (int)std::min(n, 32u) : 4; }
-static void die(const std::string &m) { fprintf(stderr, "[sambamba] %s\n", m.c_str()); rk_mark_failed("sambamba"); exit(1); }   /* rank mode: the other ranks must not wait for this one */
+static const char *g_partial_out = 0;   /* `view -o': the file being written; a command that ends in die() does not leave a part of it behind */
+static void die(const std::string &m) { fprintf(stderr, "[sambamba] %s\n", m.c_str()); if (g_partial_out) unlink(g_partial_out); rk_mark_failed("sambamba"); exit(1); }   /* rank mode: the other ranks must not wait for this one */
 static int open_in(const char *p) { if (!strcmp(p, "/dev/stdin") || !strcmp(p, "-")) return 0; int fd = open(p, O_RDONLY); if (fd < 0) die(std::string("cannot open ") + p); return fd; }
 
 /* SSG_BGZF_INFLATE_DEVICE=1 and a visible device: every reader of this process inflates its batches through ssg_bgzf_inflate (bamio.h's hook; off by
@@ -44,27 +45,215 @@ static void inflate_hook_setup()
 	if (e && !strcmp(e, "1") && ssg_device_count() > 0) { bgzf_inflate_hook = ssg_bgzf_inflate; bgzf_hook_alloc = ssg_host_alloc; bgzf_hook_free = ssg_host_free; }
 }
 
+/* ---------------- view: regions ----------------
+ * `name', `name:beg' and `name:beg-end' behind the file name, 1-based and inclusive, commas allowed in the numbers, as hts_parse_reg reads them: the whole string
+ * is tried as a contig name first, then split at its last colon.  -L reads BED: columns 1-3, 0-based half-open; `#', `track' and `browser' lines are skipped.
+ * Both become 0-based half-open (tid, beg, end); merged into one sorted list of disjoint, non-adjacent regions they are what ssg_recs_select takes, and the
+ * output is their union: every record that overlaps one of them, once, in file order. */
+static int view_contig(const bam_hdr_t &h, const std::string &name) { for (size_t t = 0; t < h.names.size(); ++t) if (h.names[t] == name) return (int)t; return -1; }
+static bool view_number(std::string v, int64_t &x)
+{
+	v.erase(std::remove(v.begin(), v.end(), ','), v.end());
+	if (v.empty() || v.size() > 10) return false;
+	for (char c : v) if (!isdigit((unsigned char)c)) return false;
+	x = strtoll(v.c_str(), 0, 10); return true;
+}
+static void view_region_add(const bam_hdr_t &h, const std::string &s, std::vector<ssg_bam_region_t> &out)
+{
+	if (s == "*") die("view: the region `*' (the reads without a contig) is not supported");
+	ssg_bam_region_t r; r.beg = 0; r.end = INT32_MAX;
+	r.tid = view_contig(h, s);
+	if (r.tid < 0) {
+		const size_t c = s.rfind(':');
+		const std::string name = c == std::string::npos ? s : s.substr(0, c);
+		r.tid = view_contig(h, name);
+		if (r.tid < 0) die("view: unknown contig `" + name + "' in the region `" + s + "'");
+		const std::string span = s.substr(c + 1); const size_t d = span.find('-');
+		int64_t b = 0, e = INT32_MAX;
+		if (!view_number(span.substr(0, d), b) || b < 1 || (d != std::string::npos && (!view_number(span.substr(d + 1), e) || e < b))) die("view: malformed region `" + s + "'");
+		if (b > INT32_MAX) b = INT32_MAX;
+		r.beg = (int32_t)(b - 1); r.end = (int32_t)std::min<int64_t>(e, INT32_MAX);
+	}
+	if (r.beg < r.end) out.push_back(r);
+}
+static void view_bed_read(const bam_hdr_t &h, const char *path, std::vector<ssg_bam_region_t> &out)
+{
+	FILE *f = fopen(path, "r");
+	if (!f) die(std::string("cannot open ") + path);
+	char line[4096]; long n = 0;
+	while (fgets(line, sizeof(line), f)) {
+		++n;
+		char name[4096]; long long b, e;
+		if (line[0] == '#' || !strncmp(line, "track", 5) || !strncmp(line, "browser", 7) || line[strspn(line, " \t\r\n")] == 0) continue;
+		if (sscanf(line, "%s %lld %lld", name, &b, &e) != 3 || b < 0 || e <= b || e > INT32_MAX) die(std::string("view: malformed line ") + std::to_string(n) + " of " + path);
+		ssg_bam_region_t r; r.tid = view_contig(h, name); r.beg = (int32_t)b; r.end = (int32_t)e;
+		if (r.tid < 0) die(std::string("view: unknown contig `") + name + "' in line " + std::to_string(n) + " of " + path);
+		out.push_back(r);
+	}
+	fclose(f);
+}
+static void view_regions_merge(std::vector<ssg_bam_region_t> &r)
+{
+	std::sort(r.begin(), r.end(), [](const ssg_bam_region_t &a, const ssg_bam_region_t &b) { return a.tid != b.tid ? a.tid < b.tid : a.beg != b.beg ? a.beg < b.beg : a.end < b.end; });
+	size_t m = 0;
+	for (size_t k = 0; k < r.size(); ++k) {
+		if (m && r[m - 1].tid == r[k].tid && r[k].beg <= r[m - 1].end) r[m - 1].end = std::max(r[m - 1].end, r[k].end);   /* overlapping or adjacent */
+		else r[m++] = r[k];
+	}
+	r.resize(m);
+}
+/* the region test on one record (its block_size word in front), as the kernel takes it: the last region that begins at or before the record, and its successor */
+static bool view_region_keeps(const std::vector<ssg_bam_region_t> &reg, const uint8_t *rec)
+{
+	if (reg.empty()) return true;
+	int32_t tid, pos; memcpy(&tid, rec + 4, 4); memcpy(&pos, rec + 8, 4);
+	if (tid < 0) return false;
+	const int32_t end = bam_endpos(rec + 4);
+	size_t lo = 0, hi = reg.size();
+	while (lo < hi) { const size_t mid = (lo + hi) / 2; if (reg[mid].tid < tid || (reg[mid].tid == tid && reg[mid].beg <= pos)) lo = mid + 1; else hi = mid; }
+	for (size_t k = lo ? lo - 1 : 0; k < reg.size() && k <= lo; ++k) if (reg[k].tid == tid && pos < reg[k].end && end > reg[k].beg) return true;
+	return false;
+}
+
+/* ---------------- view: the filter (-F) ----------------
+ * A subset of sambamba's filter language, compiled by recursive descent to the postfix program of ssg_recs_select (include/ssgpu.h): the twelve flag names, six
+ * integer fields with == != < <= > >= and a decimal constant, `and', `or', `not' and parentheses; `not' binds tighter than `and', `and' tighter than `or'.
+ * Everything else of the language (tag filters, read_name, cigar, sequence, position, =~ ...) is refused by its token: nothing is ignored silently.  The host
+ * path runs the same program with view_filter_keeps. */
+struct view_filter_t {
+	std::vector<std::string> tok; size_t at; std::vector<ssg_bam_fop_t> prog;
+	static void refuse(const std::string &t) { die("view: filter: `" + t + "' is not supported by this filter"); }
+	void tokens(const char *e)
+	{
+		for (const char *p = e; *p; ) {
+			if (isspace((unsigned char)*p)) { ++p; continue; }
+			const char *q = p;
+			if (isalpha((unsigned char)*p) || *p == '_') { while (isalnum((unsigned char)*q) || *q == '_') ++q; }
+			else if (isdigit((unsigned char)*p) || (*p == '-' && isdigit((unsigned char)p[1]))) { ++q; while (isdigit((unsigned char)*q)) ++q; }
+			else if ((p[0] == '=' && p[1] == '=') || (p[0] == '!' && p[1] == '=') || (p[0] == '<' && p[1] == '=') || (p[0] == '>' && p[1] == '=')) q = p + 2;
+			else if (*p == '<' || *p == '>' || *p == '(' || *p == ')') q = p + 1;
+			else {   /* not of the subset: kept with a mark, and refused where the parser comes to it (an unsupported name in front of it is named first) */
+				if (*p == '[') { while (*q && *q != ']') ++q; if (*q) ++q; }
+				else q = p + ((p[0] == '=' || p[0] == '!') && p[1] == '~' ? 2 : 1);
+				tok.push_back("\1" + std::string(p, q)); p = q; continue;
+			}
+			tok.push_back(std::string(p, q)); p = q;
+		}
+	}
+	void emit(int op, int arg, int32_t value)
+	{
+		ssg_bam_fop_t f; f.op = (uint8_t)op; f.arg = (uint8_t)arg; f.pad = 0; f.value = value; prog.push_back(f);
+		if (prog.size() > SSG_FOP_MAX) die("view: filter: more than " + std::to_string(SSG_FOP_MAX) + " operations");
+	}
+	void syntax() { if (at < tok.size() && tok[at][0] == 1) refuse(tok[at].substr(1)); die("view: filter: syntax error " + (at < tok.size() ? "at `" + tok[at] + "'" : std::string("at the end of the expression"))); }
+	void primary()
+	{
+		static const char *const flags[12] = { "paired", "proper_pair", "unmapped", "mate_is_unmapped", "reverse_strand", "mate_is_reverse_strand", "first_of_pair", "second_of_pair",
+		                                       "secondary_alignment", "failed_quality_control", "duplicate", "supplementary" };
+		static const char *const fields[6] = { "mapping_quality", "ref_id", "mate_ref_id", "template_length", "sequence_length", "flag" };   /* SSG_FLD_* */
+		static const char *const cmps[6] = { "==", "!=", "<", "<=", ">", ">=" };                                                              /* SSG_FOP_EQ .. */
+		if (at >= tok.size()) syntax();
+		const std::string t = tok[at++];
+		if (t[0] == 1) refuse(t.substr(1));
+		if (t == "(") { either(); if (at >= tok.size() || tok[at] != ")") die("view: filter: unbalanced parenthesis"); ++at; return; }
+		if (t == "not") { primary(); emit(SSG_FOP_NOT, 0, 0); return; }
+		for (int k = 0; k < 12; ++k) if (t == flags[k]) { emit(SSG_FOP_FLAG, 0, 1 << k); return; }
+		for (int k = 0; k < 6; ++k) if (t == fields[k]) {
+			int c = 0;
+			if (at >= tok.size()) syntax();
+			while (c < 6 && tok[at] != cmps[c]) ++c;
+			if (c == 6) { if (tok[at][0] == 1) refuse(tok[at].substr(1)); if (tok[at] == ")" || tok[at] == "and" || tok[at] == "or") syntax(); refuse(tok[at]); }
+			++at;
+			if (at >= tok.size()) syntax();
+			const std::string &v = tok[at];
+			if (!(isdigit((unsigned char)v[0]) || v[0] == '-')) { if (isalpha((unsigned char)v[0]) || v[0] == '_') refuse(v); syntax(); }
+			errno = 0; const long long x = strtoll(v.c_str(), 0, 10);
+			if (errno || x < INT32_MIN || x > INT32_MAX) die("view: filter: the constant " + v + " does not fit 32 bits");
+			++at; emit(SSG_FOP_EQ + c, k, (int32_t)x); return;
+		}
+		if (t == ")") die("view: filter: unbalanced parenthesis");
+		if (t == "and" || t == "or" || !(isalpha((unsigned char)t[0]) || t[0] == '_')) { --at; syntax(); }
+		refuse(t);
+	}
+	void both() { primary(); while (at < tok.size() && tok[at] == "and") { ++at; primary(); emit(SSG_FOP_AND, 0, 0); } }
+	void either() { both(); while (at < tok.size() && tok[at] == "or") { ++at; both(); emit(SSG_FOP_OR, 0, 0); } }
+	void compile(const char *e)
+	{
+		tokens(e); at = 0;
+		if (tok.empty()) die("view: filter: an empty expression");
+		either();
+		if (at < tok.size()) { if (tok[at] == ")") die("view: filter: unbalanced parenthesis"); syntax(); }
+	}
+	view_filter_t() : at(0) {}
+};
+/* the program on one record (its block_size word in front), by a plain interpreter: what ssg_k_bam_select computes per lane */
+static bool view_filter_keeps(const std::vector<ssg_bam_fop_t> &prog, const uint8_t *rec)
+{
+	if (prog.empty()) return true;
+	uint32_t x[9]; memcpy(x, rec, 36);
+	const int32_t field[6] = { (int32_t)(x[3] >> 8 & 0xff), (int32_t)x[1], (int32_t)x[6], (int32_t)x[8], (int32_t)x[5], (int32_t)(x[4] >> 16) };
+	bool st[SSG_FOP_MAX + 1]; int d = 0;
+	for (size_t pc = 0; pc < prog.size(); ++pc) {
+		const ssg_bam_fop_t &f = prog[pc];
+		if (f.op == SSG_FOP_FLAG) st[d++] = (field[SSG_FLD_FLAG] & f.value) != 0;
+		else if (f.op == SSG_FOP_NOT) st[d - 1] = !st[d - 1];
+		else if (f.op == SSG_FOP_AND) { st[d - 2] = st[d - 2] && st[d - 1]; --d; }
+		else if (f.op == SSG_FOP_OR) { st[d - 2] = st[d - 2] || st[d - 1]; --d; }
+		else { const int32_t v = field[f.arg], c = f.value; st[d++] = f.op == SSG_FOP_EQ ? v == c : f.op == SSG_FOP_NE ? v != c : f.op == SSG_FOP_LT ? v < c : f.op == SSG_FOP_LE ? v <= c : f.op == SSG_FOP_GT ? v > c : v >= c; }
+	}
+	return st[0];
+}
+/* the selecting form of `view' (defined behind the device read path below) */
+struct view_job_t;
+static void view_select_run(const char *in, int fd, bgzf_in_t *bi, bam_hdr_t &h, uint64_t v0, std::vector<ssg_bam_region_t> &reg, bool with_regions, const std::vector<ssg_bam_fop_t> &prog, bool count, bool with_hdr, bool bam_out, int level, int threads, int out_fd);
+
 /* ---------------- view ---------------- */
 static int cmd_view(int argc, char **argv)
 {
-	int level = -1, threads = hw_threads(); bool hdr_only = false, sam_in = false, with_hdr = false; const char *in = 0, *fmt = "sam";
+	int level = -1, threads = hw_threads(); bool hdr_only = false, sam_in = false, with_hdr = false, count = false; const char *in = 0, *fmt = "sam", *expr = 0, *out_path = 0, *bed = 0; std::vector<std::string> region;
 	for (int i = 0; i < argc; ++i) {
 		const char *a = argv[i];
 		if (!strcmp(a, "-S")) sam_in = true;
+		else if (!strcmp(a, "-F") && i + 1 < argc) expr = argv[++i];
+		else if (!strcmp(a, "-c")) count = true;
+		else if (!strcmp(a, "-o") && i + 1 < argc) out_path = argv[++i];
+		else if (!strcmp(a, "-L") && i + 1 < argc) bed = argv[++i];
 		else if (!strcmp(a, "-H")) hdr_only = true;
 		else if (!strcmp(a, "-h")) with_hdr = true;
 		else if (!strcmp(a, "-f") && i + 1 < argc) fmt = argv[++i];
 		else if (!strcmp(a, "-l") && i + 1 < argc) level = atoi(argv[++i]);
 		else if (!strcmp(a, "-t") && i + 1 < argc) threads = atoi(argv[++i]);
 		else if (a[0] == '-' && a[1] && strcmp(a, "-")) die(std::string("view: unsupported option ") + a);
-		else in = a;
+		else region.push_back(a);
 	}
-	if (!in) die("usage: sambamba view [-S] [-f bam] [-l N] [-H] <in>");
+	/* what stands behind the file name of a BAM input are regions (with -S, as ever, the last name is the input) */
+	std::string in_name;
+	if (!region.empty()) { in_name = sam_in ? region.back() : region.front(); if (sam_in) region.clear(); else region.erase(region.begin()); in = in_name.c_str(); }
+	if (!in) die("usage: sambamba view [-S] [-f bam] [-l N] [-H] [-F FILTER] [-c] [-o FILE] [-L BED] <in> [region ...]");
+	view_filter_t filter;
+	if (expr) filter.compile(expr);
+	const bool selecting = expr || count || out_path || bed || !region.empty() || (!sam_in && !hdr_only && !strcmp(fmt, "bam"));
+	if (selecting && (sam_in || hdr_only || (strcmp(fmt, "sam") && strcmp(fmt, "bam")))) die("view: -F, -c, -o, -L and regions are supported for a BAM file, as SAM text, as BAM (-f bam) or as a count");
 	const int fd = open_in(in);
 	if (hdr_only) {
 		bgzf_in_t bi(fd, 1); bam_hdr_t h;
 		if (!hdr_read(bi, h)) die("view -H: not a BAM file");
 		io_write_all(1, h.text.data(), h.text.size());
+		return 0;
+	}
+	if (selecting) {   /* the records that regions and a filter keep, as SAM text, as BAM or as their number */
+		bam_hdr_t h; bgzf_in_t bi(fd, threads);   /* (the reader goes on behind the header where the input cannot be read at offsets) */
+		if (!hdr_read(bi, h)) die("view: not a BAM file");
+		const uint64_t v0 = bi.tell();
+		std::vector<ssg_bam_region_t> reg;
+		for (const std::string &r : region) view_region_add(h, r, reg);
+		if (bed) view_bed_read(h, bed, reg);
+		view_regions_merge(reg);
+		const bool with_regions = bed || !region.empty();
+		int out_fd = 1;
+		if (out_path) { out_fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666); if (out_fd < 0) die(std::string("cannot write ") + out_path + ": " + strerror(errno)); g_partial_out = out_path; }
+		view_select_run(in, fd, &bi, h, v0, reg, with_regions, filter.prog, count, with_hdr, !strcmp(fmt, "bam"), level, threads, out_fd);
+		g_partial_out = 0; if (out_path) close(out_fd);
 		return 0;
 	}
 	if (!sam_in && !strcmp(fmt, "sam")) {   /* a BAM file as SAM text (with -h: behind its header), the lines of bam2sam.h */
@@ -1277,8 +1466,8 @@ static void dev_prof_report(const char *cmd)
 /* whole BGZF members of a file, read at offsets of its own (pread): a bgzf_in_t on the same descriptor is not disturbed */
 struct raw_members_t {
 	int fd; const char *name; uint64_t fpos, addr; bool eof; std::vector<uint8_t> buf; size_t used;   /* buf[0] lies at file offset addr; buf[0 .. used) are the members of the last next() */
-	std::vector<uint64_t> moff; uint64_t inflated; bool at_end;
-	raw_members_t() : fd(-1), name(""), fpos(0), addr(0), eof(false), used(0), inflated(0), at_end(false) {}
+	std::vector<uint64_t> moff; uint64_t inflated; bool at_end; uint64_t limit;   /* limit: no member that begins at or behind this file offset is taken (a reader of one chunk of an index) */
+	raw_members_t() : fd(-1), name(""), fpos(0), addr(0), eof(false), used(0), inflated(0), at_end(false), limit(~(uint64_t)0) {}
 	void start(int fd_, const char *name_, uint64_t file_off) { fd = fd_; name = name_; fpos = addr = file_off; eof = false; buf.clear(); used = 0; }
 	bool fill(size_t need)
 	{
@@ -1298,7 +1487,7 @@ struct raw_members_t {
 		if (used) { buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)used); addr += used; used = 0; }
 		moff.assign(1, 0); inflated = 0;
 		size_t pos = 0;
-		while (moff.size() - 1 < max_members) {
+		while (moff.size() - 1 < max_members && addr + pos < limit) {
 			if (!fill(pos + 18)) { if (buf.size() > pos) die(std::string("truncated BGZF header in ") + name); break; }
 			if (buf[pos] != 0x1f || buf[pos + 1] != 0x8b || buf[pos + 2] != 8 || !(buf[pos + 3] & 4)) die(std::string("not a BGZF block in ") + name);
 			const size_t xlen = buf[pos + 10] | (size_t)buf[pos + 11] << 8;
@@ -1311,7 +1500,7 @@ struct raw_members_t {
 			pos += bsize; moff.push_back(pos); inflated += isz;
 		}
 		used = pos;
-		at_end = !fill(pos + 1);   /* (nothing behind these members: the caller need not come back to learn it) */
+		at_end = addr + pos >= limit || !fill(pos + 1);   /* (nothing behind these members: the caller need not come back to learn it) */
 		return moff.size() > 1;
 	}
 	size_t n() const { return moff.size() - 1; }
@@ -1347,6 +1536,244 @@ static int dev_load(ssg_recs_t *recs, raw_members_t &rd, uint64_t first, const c
 	if (rc) { loc.resize(have); key.resize(have); ent.resize(have); why = rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_recs_scan: ")) : std::string(ssg_last_error()); n_new = 0; return 1; }
 	loc.resize(have + n_new); key.resize(have + n_new); ent.resize(have + n_new);
 	return 0;
+}
+
+/* ---------------- view: selection (-F, -c, -o, -L, regions, -f bam with a BAM input) ----------------
+ * What is read: without regions the whole file; with regions the chunks [u, v) of virtual offsets that the file's .bai gives for them (bai_reader_t, bamio.h:
+ * hts_itr_query's candidates of every merged region, sorted and merged), each read from u until a record begins at or behind v.  The region test and the
+ * filter decide on every record read.  The host path (the default, and the fall-back) inflates the members with zlib and runs view_region_keeps and
+ * view_filter_keeps; SSG_VIEW_DEVICE=1 sends the same chunks through the record store and ssg_recs_select. */
+typedef bai_reader_t::chunk_t view_chunk_t;
+struct view_job_t {
+	const char *in; int fd; bgzf_in_t *bi; bam_hdr_t h;   /* bi: the sequential reader, behind the header */
+	std::vector<ssg_bam_region_t> reg; std::vector<ssg_bam_fop_t> prog; std::vector<view_chunk_t> chunks;
+	bool count, with_hdr, bam_out; int level, threads, out_fd;
+};
+/* where the kept records of the host path go: SAM text, BAM blocks, or a count */
+struct view_sink_t {
+	view_job_t &J; std::string text; bgzf_out_t *bo; uint64_t n_kept;
+	view_sink_t(view_job_t &j) : J(j), bo(0), n_kept(0)
+	{
+		if (J.count) return;
+		if (J.bam_out) { bo = new bgzf_out_t(J.out_fd, J.level, J.threads); hdr_write(*bo, J.h); }
+		else if (J.with_hdr) text = J.h.text;
+	}
+	void record(const uint8_t *rec, size_t len)
+	{
+		++n_kept;
+		if (J.count) return;
+		if (bo) { bo->record(rec, len); return; }
+		if (!bam_record_to_sam(rec, [&](int32_t t) -> const char* { return t >= 0 && t < (int32_t)J.h.names.size() ? J.h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
+		if (text.size() > ((size_t)1 << 20)) { io_write_all(J.out_fd, text.data(), text.size()); text.clear(); }
+	}
+	void finish()
+	{
+		if (J.count) text = std::to_string(n_kept) + "\n";
+		if (bo) { bo->finish(); delete bo; bo = 0; }
+		else io_write_all(J.out_fd, text.data(), text.size());
+	}
+};
+static void view_host(view_job_t &J)
+{
+	view_sink_t sink(J);
+	struct stat sb;
+	if (J.chunks.size() == 1 && J.chunks[0].v == ~(uint64_t)0 && (fstat(J.fd, &sb) != 0 || !S_ISREG(sb.st_mode))) {   /* a pipe: the whole stream through the sequential reader */
+		std::vector<uint8_t> rec;
+		for (;;) {
+			uint32_t bs;
+			if (J.bi->get(&bs, 4) != 4) break;
+			if (bs < 32) die("view: malformed BAM record");
+			rec.resize(4 + (size_t)bs); memcpy(rec.data(), &bs, 4);
+			if (J.bi->get(rec.data() + 4, bs) != bs) die("view: truncated BAM");
+			if (32 + (size_t)rec[12] + 4 * ((size_t)rec[16] | (size_t)rec[17] << 8) > bs) die("view: malformed BAM record");
+			if (view_region_keeps(J.reg, rec.data()) && view_filter_keeps(J.prog, rec.data())) sink.record(rec.data(), rec.size());
+		}
+		sink.finish();
+		return;
+	}
+	raw_members_t rd; std::vector<uint8_t> stream; std::vector<uint64_t> mstart, maddr, out_off;
+	for (const view_chunk_t &c : J.chunks) {
+		const bool whole = c.v == ~(uint64_t)0;
+		rd.start(J.fd, J.in, c.u >> 16);
+		stream.clear(); mstart.clear(); maddr.clear();
+		uint64_t pos = c.u & 0xffff; size_t m = 0; bool done = false;
+		while (!done && rd.next(whole ? (uint64_t)64 << 20 : (uint64_t)2 << 20, whole ? 1024 : 32)) {
+			const size_t nm = rd.n(), base = stream.size();
+			out_off.assign(nm + 1, 0);
+			for (size_t k = 0; k < nm; ++k) { uint32_t isz; memcpy(&isz, rd.buf.data() + rd.moff[k + 1] - 4, 4); if (isz > 65536) die(std::string("view: a BGZF block that claims more than 64 KB in ") + J.in); out_off[k + 1] = out_off[k] + isz; }
+			stream.resize(base + (size_t)out_off[nm]);
+			std::vector<int> bad(nm, 0);
+			parallel_for(J.threads, nm, [&](size_t a, size_t b, int) {
+				for (size_t k = a; k < b; ++k) {
+					const uint8_t *mb = rd.buf.data() + rd.moff[k]; const size_t len = (size_t)(rd.moff[k + 1] - rd.moff[k]), xlen = mb[10] | (size_t)mb[11] << 8;
+					z_stream z; memset(&z, 0, sizeof(z));
+					if (len < 12 + xlen + 8 || inflateInit2(&z, -15) != Z_OK) { bad[k] = 1; continue; }
+					z.next_in = (Bytef*)(mb + 12 + xlen); z.avail_in = (uInt)(len - 12 - xlen - 8);
+					z.next_out = stream.data() + base + out_off[k]; z.avail_out = (uInt)(out_off[k + 1] - out_off[k]);
+					const int rc = inflate(&z, Z_FINISH);
+					if (rc != Z_STREAM_END || z.avail_out != 0) bad[k] = 1;
+					inflateEnd(&z);
+				}
+			});
+			for (size_t k = 0; k < nm; ++k) {
+				if (bad[k]) die(std::string("view: inflate failed: BGZF member at file offset ") + std::to_string(rd.addr + rd.moff[k]) + " of " + J.in);
+				mstart.push_back(base + out_off[k]); maddr.push_back(rd.addr + rd.moff[k]);
+			}
+			if (pos > stream.size()) die(std::string("view: the index of ") + J.in + " points behind a block's end");
+			while (pos + 4 <= stream.size()) {
+				uint32_t bs; memcpy(&bs, stream.data() + pos, 4);
+				if (bs < 32) die("view: malformed BAM record");
+				if (pos + 4 + (uint64_t)bs > stream.size()) break;
+				while (m + 1 < mstart.size() && mstart[m + 1] <= pos) ++m;                  /* the member that holds the record's first byte */
+				if ((maddr[m] << 16 | (pos - mstart[m])) >= c.v) { done = true; break; }
+				const uint8_t *rec = stream.data() + pos;
+				if (32 + (size_t)rec[12] + 4 * ((size_t)rec[16] | (size_t)rec[17] << 8) > bs) die("view: malformed BAM record");   /* (its end is read from its CIGAR) */
+				if (view_region_keeps(J.reg, rec) && view_filter_keeps(J.prog, rec)) sink.record(rec, 4 + (size_t)bs);
+				pos += 4 + (uint64_t)bs;
+			}
+			/* what is consumed leaves the buffer */
+			while (m + 1 < mstart.size() && mstart[m + 1] <= pos) ++m;
+			const uint64_t drop = std::min<uint64_t>(mstart[m], pos);
+			if (drop) {
+				stream.erase(stream.begin(), stream.begin() + (ptrdiff_t)drop); pos -= drop;
+				mstart.erase(mstart.begin(), mstart.begin() + (ptrdiff_t)m); maddr.erase(maddr.begin(), maddr.begin() + (ptrdiff_t)m); m = 0;
+				for (uint64_t &s : mstart) s -= drop;
+			}
+		}
+		if (!done && pos != stream.size()) die("view: truncated BAM");
+	}
+	sink.finish();
+}
+
+/* the BGZF members of a file, counted from their headers (the last line of the device path's log) */
+static uint64_t view_count_members(int fd)
+{
+	uint64_t n = 0, at = 0; uint8_t hd[18];
+	while (pread(fd, hd, 18, (off_t)at) == 18 && hd[0] == 0x1f && hd[1] == 0x8b && hd[12] == 'B' && hd[13] == 'C') { at += (uint64_t)(hd[16] | (size_t)hd[17] << 8) + 1; ++n; }
+	return n;
+}
+
+/* The device path: every chunk's whole members from u >> 16 through the member that holds v go into the store in batches of at most 4096 members or 256 MB
+ * (ssg_recs_release after each); the stream of a batch begins at `first' (u & 0xffff in a chunk's first batch) and ends, in the chunk's last member, at v's
+ * offset: both are record starts by the index's construction.  ssg_recs_select decides and compacts.  -c: the counting form, two integers a batch.  SAM text:
+ * the kept records declared as the stream (ssg_recs_order), gathered (ssg_recs_gather) and printed by bam_record_to_sam.  BAM: the header's blocks from the
+ * host, the kept records' blocks cut by bgzf_out_t::record's rule (a batch ends its last block) and gathered, deflated and framed on the device
+ * (ssg_bgzf_compress_recs_level, as the device merge writes them), the end-of-file marker last.  false with `why' while nothing is written: the host path
+ * takes over; once output has begun a failure ends the command. */
+static bool view_device(view_job_t &J, std::string &why)
+{
+	if (J.bam_out && !J.count && J.level == 0) { why = "-l 0: stored blocks are the host's"; return false; }
+	if (!dev_read_ready(J.fd, why)) return false;
+	recs_holder_t S;
+	const char *const pool = getenv("SSG_VIEW_POOL");   /* bytes the record store may hold (tests: a batch beyond it is a store failure) */
+	if (ssg_set_device(0) || ssg_recs_create(pool && *pool ? strtoull(pool, 0, 10) : ~(uint64_t)0 >> 1, &S.r)) { why = ssg_last_error(); return false; }
+	dev_prof_begin();
+	const bool bam = J.bam_out && !J.count;
+	if (bam) bgzf_dev_level_set(J.level);
+	const long BATCH = 1024;   /* blocks per device call */
+	const uint64_t out_cap = bam ? ssg_bgzf_bound((uint64_t)BATCH * BGZF_MAX_PAYLOAD, BATCH) : 0;
+	struct pinned_t { uint8_t *p; ~pinned_t() { if (p) ssg_host_free(p); } } O = { bam ? (uint8_t*)ssg_host_alloc((size_t)out_cap) : 0 };
+	if (bam && !O.p) { why = "no page-locked memory for the output blocks"; return false; }
+	raw_members_t rd;
+	uint64_t n_scanned = 0, n_kept = 0, n_members = 0, n_blocks = 0; int n_batches = 0; bool begun = false;
+	std::vector<uint64_t> out_off, hint, loc, key, cum, cut, boff((size_t)BATCH + 1); std::vector<ssg_bam_ent_t> ent; std::vector<int32_t> status; std::vector<uint8_t> buf;
+	std::string text; if (J.with_hdr && !J.count && !bam) text = J.h.text;
+	const double t0 = wall();
+	auto fail = [&](const std::string &m) -> bool { if (begun) die("view: " + m + " after output had begun (SSG_VIEW_DEVICE=0 reads the file on the host)"); why = m; return false; };
+	auto begin_bam = [&]() { if (!begun) { bgzf_out_t o(J.out_fd, J.level, J.threads); hdr_write(o, J.h); o.drain(true); begun = true; } };
+	for (const view_chunk_t &c : J.chunks) {
+		rd.start(J.fd, J.in, c.u >> 16);
+		rd.limit = c.v == ~(uint64_t)0 ? c.v : (c.v >> 16) + ((c.v & 0xffff) ? 1 : 0);
+		uint64_t first = c.u & 0xffff;
+		while (rd.next((uint64_t)256 << 20, 4096)) {
+			const size_t nm = rd.n(); uint32_t cid = 0;
+			out_off.resize(nm + 1); status.assign(nm, 0);
+			int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
+			if (rc == SSG_EIO) { size_t k = 0; while (k + 1 < nm && !status[k]) ++k; die(std::string("view: inflate failed: BGZF member at file offset ") + std::to_string(rd.addr + rd.moff[k]) + " of " + rd.name + " (device status " + std::to_string(status[k]) + ")"); }
+			if (rc) return fail(ssg_last_error());
+			hint = out_off;
+			if ((c.v & 0xffff) && rd.addr + rd.moff[nm - 1] == c.v >> 16) {   /* the chunk's last member: the stream ends at v */
+				if (out_off[nm - 1] + (c.v & 0xffff) > out_off[nm]) return fail(std::string("the index of ") + J.in + " points behind a block's end");
+				hint[nm] = out_off[nm - 1] + (c.v & 0xffff);
+			}
+			if (first > hint[nm]) return fail(std::string("the index of ") + J.in + " points behind a block's end");
+			uint64_t n_rec = 0, n_sel = 0;
+			const uint64_t cap = J.count ? 0 : hint[nm] / 36 + 1;
+			if (!J.count) { loc.resize((size_t)cap); key.resize((size_t)cap); ent.resize((size_t)cap); }
+			rc = ssg_recs_select(S.r, cid, hint.data(), (int64_t)nm, first, J.reg.empty() ? 0 : J.reg.data(), (int64_t)J.reg.size(), J.prog.empty() ? 0 : J.prog.data(), (int)J.prog.size(), cap, &n_rec, &n_sel,
+			                     J.count ? 0 : loc.data(), J.count ? 0 : key.data(), J.count ? 0 : ent.data());
+			if (rc) return fail(rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_recs_select: ")) : std::string(ssg_last_error()));
+			if (!J.count && n_sel) {
+				cum.resize((size_t)n_sel + 1); cum[0] = 0;
+				for (uint64_t i = 0; i < n_sel; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + ent[(size_t)i].len;
+				if (ssg_recs_order(S.r, loc.data(), cum.data(), (int64_t)n_sel)) return fail(ssg_last_error());
+				if (bam) {
+					/* the blocks, cut as bgzf_out_t::record cuts them: a block closes when the next record would not fit, a record longer than a block is split; a batch ends its last block */
+					cut.assign(1, 0); uint64_t open_ = 0;
+					for (uint64_t j = 0; j < n_sel; ++j) {
+						const uint64_t c0 = cum[(size_t)j], c1 = cum[(size_t)j + 1];
+						if (c0 > open_ && c1 - open_ > BGZF_MAX_PAYLOAD) { cut.push_back(c0); open_ = c0; }
+						while (c1 - open_ >= BGZF_MAX_PAYLOAD) { open_ += BGZF_MAX_PAYLOAD; cut.push_back(open_); }
+					}
+					if (cum[(size_t)n_sel] > cut.back()) cut.push_back(cum[(size_t)n_sel]);
+					const size_t nb = cut.size() - 1;
+					for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
+						const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
+						if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, O.p, out_cap, boff.data(), 0)) return fail(ssg_last_error());
+						begin_bam();
+						io_write_all(J.out_fd, O.p, (size_t)boff[(size_t)k]);
+					}
+					n_blocks += nb;
+				} else {
+					buf.resize((size_t)cum[(size_t)n_sel]);
+					if (ssg_recs_gather(S.r, 0, cum[(size_t)n_sel], buf.data())) return fail(ssg_last_error());
+					for (uint64_t i = 0; i < n_sel; ++i) {
+						if (!bam_record_to_sam(buf.data() + cum[(size_t)i], [&](int32_t t) -> const char* { return t >= 0 && t < (int32_t)J.h.names.size() ? J.h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
+						if (text.size() > ((size_t)1 << 20)) { io_write_all(J.out_fd, text.data(), text.size()); text.clear(); begun = true; }
+					}
+				}
+				if (ssg_recs_reopen(S.r)) return fail(ssg_last_error());
+			}
+			if (ssg_recs_release(S.r, cid)) return fail(ssg_last_error());
+			first = 0; n_scanned += n_rec; n_kept += n_sel; n_members += nm; ++n_batches;
+		}
+	}
+	if (J.count) text = std::to_string(n_kept) + "\n";
+	if (bam) { begin_bam(); io_write_all(J.out_fd, BGZF_EOF, 28); }
+	else io_write_all(J.out_fd, text.data(), text.size());
+	dev_prof_report("view");
+	if (dbg()) fprintf(stderr, "[sambamba] view: on the device: %llu of %llu members read, %llu records scanned, %llu kept, %d batches%s, %.2f s\n", (unsigned long long)n_members, (unsigned long long)view_count_members(J.fd),
+	                   (unsigned long long)n_scanned, (unsigned long long)n_kept, n_batches, bam ? (", " + std::to_string(n_blocks) + " blocks" + bgzf_dev_level_note()).c_str() : "", wall() - t0);
+	return true;
+}
+
+static void view_select(view_job_t &J, bool with_regions);
+static void view_select_run(const char *in, int fd, bgzf_in_t *bi, bam_hdr_t &h, uint64_t v0, std::vector<ssg_bam_region_t> &reg, bool with_regions, const std::vector<ssg_bam_fop_t> &prog, bool count, bool with_hdr, bool bam_out, int level, int threads, int out_fd)
+{
+	view_job_t J; J.in = in; J.fd = fd; J.bi = bi; J.h = h; J.reg = reg; J.prog = prog; J.count = count; J.with_hdr = with_hdr; J.bam_out = bam_out; J.level = level; J.threads = threads; J.out_fd = out_fd;
+	view_chunk_t all; all.u = v0; all.v = ~(uint64_t)0; J.chunks.assign(1, all);
+	view_select(J, with_regions);
+}
+static void view_select(view_job_t &J, bool with_regions)
+{
+	if (with_regions) {   /* the index says what to read */
+		const std::string bai = std::string(J.in) + ".bai";
+		struct stat sb, si;
+		if (stat(bai.c_str(), &si) != 0) die("view: regions need the index " + bai + ", which is not there (sambamba index)");
+		if (fstat(J.fd, &sb) == 0 && si.st_mtime < sb.st_mtime) die("view: the index " + bai + " is older than " + J.in + " (sambamba index)");
+		bai_reader_t idx; std::string err;
+		if (!idx.load(bai.c_str(), err)) die("view: the index " + bai + ": " + err);
+		if (idx.refs.size() != J.h.names.size()) die("view: the index " + bai + " has " + std::to_string(idx.refs.size()) + " references, the header of " + J.in + " has " + std::to_string(J.h.names.size()));
+		J.chunks.clear();
+		for (const ssg_bam_region_t &r : J.reg) idx.query(r.tid, r.beg, r.end, J.chunks);
+		bai_chunks_merge(J.chunks);
+	}
+	if (env_is_1("SSG_VIEW_DEVICE")) {
+		std::string why;
+		if (view_device(J, why)) return;
+		if (dbg()) fprintf(stderr, "[sambamba] view: device view off (%s): the file is read on the host\n", why.c_str());
+	}
+	view_host(J);
 }
 
 /* `sambamba index' from the device: true when the .bai is written; false with `why' -- nothing was written, the host loop takes over */
