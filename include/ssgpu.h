@@ -366,6 +366,17 @@ int ssg_dev_records_export(const ssg_dev_records_t *r, uint64_t *d_keys, void *d
 /* the kept records as a host result (release with ssg_pe_result_free; prints through ssg_sam_format) and, per SAM line in line order
  * (ssg_dev_records_n_lines entries, HOST buffers, either may be NULL), samblaster's decisions: SSG_SBL_* bits and the mate line */
 int ssg_dev_records_download(const ssg_dev_records_t *r, ssg_pe_result_t **res, uint8_t *line_bits, int64_t *mate_line);
+/* test entry: samblaster's stage of the timed step (rows a14-a17) on records given by the caller -- what ssg_hotpath_dev_ex runs after alignment, through the same
+ * host functions: the SAM lines of the records (FLAG as mem_aln2sam prints it, CIGAR sums), the primaries and their ends, duplicate marking (against st's set
+ * when st != NULL), classification, counts and the coordinate-sort keys.  req_off[2 n_pairs + 1]: read r's requests are req[req_off[r] .. req_off[r + 1]) with
+ * their records in alns at the same index (read 1 and read 2 of a pair interleaved); only SSG_REQ_MAIN requests make a line.
+ * Validated first, SSG_EINVAL with a message otherwise and before any launch: --maxSplitCount <= 16, offsets from 0 and monotone, kinds, 0 <= n_cigar <= SSG_MAX_CIGAR,
+ * a main request for every read, and a main one first.
+ * Outputs (HOST buffers of the caller): line_off[n_pairs + 1], *n_lines; per line (room for as many as there are requests) lines, line_req, bits, mate_line, keys;
+ * per pair ends[2], prim[2] (line index or -1), sig[3] (all ones = never a duplicate), dup; counts[4] as ssg_dev_records_classify. */
+int ssg_dbg_sbl_records(long n_pairs, const int64_t *req_off, const ssg_alnreq_t *req, const ssg_aln_t *alns, const ssg_sbl_opt_t *o, ssg_sbl_state_t *st,
+                        int64_t *line_off, int64_t *n_lines, ssg_sbl_line_t *lines, int64_t *line_req, ssg_sbl_end_t *ends, int64_t *prim, uint64_t *sig, uint8_t *dup,
+                        uint8_t *bits, int64_t *mate_line, uint64_t counts[4], uint64_t *keys);
 
 /* FM-index from arrays already resident in HBM (not copied; the caller keeps them alive) */
 int ssg_index_from_device(const uint32_t *d_bwt, uint64_t primary, const uint64_t L2[5], const uint64_t *d_sa, int sa_intv,

@@ -379,6 +379,94 @@ def sbl_markdup(lib, ends):
     return dup
 
 
+SBL_LINE_DT = np.dtype([("seq", "i4"), ("pos", "i4"), ("flag", "i4"), ("mapq", "i4"), ("lclip", "i4"), ("rclip", "i4"), ("qalen", "i4"), ("ralen", "i4")])
+SBL_OPT_DT = np.dtype([("exclude_dups", "i4"), ("add_mate_tags", "i4"), ("max_split_count", "i4"), ("min_non_overlap", "i4"), ("max_unmapped_bases", "i4"),
+                       ("min_indel_size", "i4")])
+
+
+def sbl_opt_init(lib, **kw):
+    """ssg_sbl_opt_t with upstream samblaster's defaults, then the fields given"""
+    o = np.zeros((), dtype=SBL_OPT_DT)
+    lib.l.ssg_sbl_opt_init(_ptr(o))
+    for k, v in kw.items():
+        o[k] = v
+    return o
+
+
+def sbl_state_new(lib):
+    lib.l.ssg_sbl_state_new.restype = C.c_void_p
+    return C.c_void_p(lib.l.ssg_sbl_state_new())
+
+
+def sbl_state_free(lib, st):
+    lib.l.ssg_sbl_state_free(st)
+
+
+def sbl_markdup_stream(lib, st, ends):
+    """ssg_sbl_markdup_stream: like sbl_markdup, against the duplicate set that st keeps between calls"""
+    ends = np.ascontiguousarray(ends, dtype=SBL_END_DT)
+    n = len(ends) // 2
+    dup = np.zeros(n, dtype=np.uint8)
+    lib._chk(lib.l.ssg_sbl_markdup_stream(st, C.c_long(n), _ptr(ends), _ptr(dup)))
+    return dup
+
+
+def _sbl_chunk(blk_off, lines):
+    off = np.ascontiguousarray(blk_off, dtype=np.int64)
+    lines = np.ascontiguousarray(lines, dtype=SBL_LINE_DT)
+    assert int(off[-1]) == len(lines), (int(off[-1]), len(lines))
+    return off, lines, len(off) - 1
+
+
+def sbl_process(lib, st, opt, blk_off, lines):
+    """ssg_sbl_process over a chunk of name-grouped blocks (st may be None): (SSG_SBL_* bits, mate line) per line"""
+    off, lines, nb = _sbl_chunk(blk_off, lines)
+    bits, mate = np.zeros(len(lines), dtype=np.uint8), np.zeros(len(lines), dtype=np.int64)
+    lib._chk(lib.l.ssg_sbl_process(st, _ptr(opt), C.c_long(nb), _ptr(off), _ptr(lines), _ptr(bits), _ptr(mate)))
+    return bits, mate
+
+
+def sbl_ends(lib, blk_off, lines):
+    """ssg_sbl_ends: the two primary ends of every block (SBL_END_DT, 2 per block)"""
+    off, lines, nb = _sbl_chunk(blk_off, lines)
+    ends = np.zeros(2 * nb, dtype=SBL_END_DT)
+    lib._chk(lib.l.ssg_sbl_ends(C.c_long(nb), _ptr(off), _ptr(lines), _ptr(ends)))
+    return ends
+
+
+def sbl_classify(lib, opt, blk_off, lines, dup):
+    """ssg_sbl_classify: the lines classified with duplicate verdicts decided elsewhere (one byte per block)"""
+    off, lines, nb = _sbl_chunk(blk_off, lines)
+    dup = np.ascontiguousarray(dup, dtype=np.uint8)
+    assert len(dup) == nb
+    bits, mate = np.zeros(len(lines), dtype=np.uint8), np.zeros(len(lines), dtype=np.int64)
+    lib._chk(lib.l.ssg_sbl_classify(_ptr(opt), C.c_long(nb), _ptr(off), _ptr(lines), _ptr(dup), _ptr(bits), _ptr(mate)))
+    return bits, mate
+
+
+def dbg_sbl_records(lib, req_off, req, alns, opt, st=None):
+    """ssg_dbg_sbl_records: samblaster's stage of the timed step on given records.  (return code, dict of line_off, lines [SBL_LINE_DT], line_req, ends
+    [SBL_END_DT], prim, sig [n_pairs x 3], dup, bits, mate, counts [4], keys); a refusal comes back as its code, the message in ssg_last_error."""
+    req_off = np.ascontiguousarray(req_off, dtype=np.int64)
+    req = np.ascontiguousarray(req, dtype=ALNREQ_DT)
+    alns = np.ascontiguousarray(alns, dtype=ALN_DT)
+    n_pairs, cap = (len(req_off) - 1) // 2, len(req) + 1
+    assert len(req_off) == 2 * n_pairs + 1 and len(req) == len(alns)
+    o = dict(line_off=np.zeros(n_pairs + 1, np.int64), lines=np.zeros(cap, SBL_LINE_DT), line_req=np.zeros(cap, np.int64), ends=np.zeros(2 * n_pairs + 1, SBL_END_DT),
+             prim=np.zeros(2 * n_pairs + 1, np.int64), sig=np.zeros((n_pairs + 1, 3), np.uint64), dup=np.zeros(n_pairs + 1, np.uint8), bits=np.zeros(cap, np.uint8),
+             mate=np.zeros(cap, np.int64), counts=np.zeros(4, np.uint64), keys=np.zeros(cap, np.uint64))
+    nl = C.c_int64(0)
+    rc = lib.l.ssg_dbg_sbl_records(C.c_long(n_pairs), _ptr(req_off), _ptr(req), _ptr(alns), _ptr(opt), st, _ptr(o["line_off"]), C.byref(nl), _ptr(o["lines"]),
+                                   _ptr(o["line_req"]), _ptr(o["ends"]), _ptr(o["prim"]), _ptr(o["sig"]), _ptr(o["dup"]), _ptr(o["bits"]), _ptr(o["mate"]),
+                                   _ptr(o["counts"]), _ptr(o["keys"]))
+    n = int(nl.value)
+    for k in ("lines", "line_req", "bits", "mate", "keys"):
+        o[k] = o[k][:n]
+    for k, m in (("ends", 2 * n_pairs), ("prim", 2 * n_pairs), ("sig", n_pairs), ("dup", n_pairs)):
+        o[k] = o[k][:m]
+    return rc, o
+
+
 def index_from_device(lib, d_bwt, primary, L2, d_sa, d_pac, l_pac, ctg_off, ctg_len, sa_intv=32):
     """d_* are integer device addresses (e.g. torch.Tensor.data_ptr()); the caller keeps the tensors alive."""
     h = C.c_void_p()

@@ -1,6 +1,6 @@
 /*
- * ssg_dbg.cpp -- the stage test entries of include/ssgpu.h: ssg_dbg_chain, ssg_dbg_regions, ssg_dbg_reg2aln, ssg_dbg_pestat, ssg_dbg_pair_final and
- * ssg_dbg_matesw.  Each checks lists built by the caller until nothing out of range can reach a kernel, lays them out as the stage before leaves them, and
+ * ssg_dbg.cpp -- the stage test entries of include/ssgpu.h: ssg_dbg_chain, ssg_dbg_regions, ssg_dbg_reg2aln, ssg_dbg_pestat, ssg_dbg_pair_final,
+ * ssg_dbg_matesw and ssg_dbg_sbl_records.  Each checks lists built by the caller until nothing out of range can reach a kernel, lays them out as the stage before leaves them, and
  * runs the pipeline's own stage function on them (ssgpu_core.cpp, through ssg_stage_int.h).  A translation unit of its own so that the stage code of the core
  * reads without them -- and one that must never include a kernel header (k_*.h) or launch a kernel: the machine code of every kernel depends on what else
  * its unit holds, and that code is pinned (tools/isa_pin.py).  Device work goes through dbuf<> and the core's host functions.
@@ -468,4 +468,47 @@ int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	msw_counts(ms, counts);
 	*regs_out = out;
 	return SSG_OK;
+}
+
+/* test entry: samblaster's stage of the timed step on the caller's records (include/ssgpu.h), through the host functions ssg_hotpath_dev_ex runs after alignment */
+int ssg_dbg_sbl_records(long n_pairs, const int64_t *req_off, const ssg_alnreq_t *req, const ssg_aln_t *alns, const ssg_sbl_opt_t *o, ssg_sbl_state_t *st,
+                        int64_t *line_off, int64_t *n_lines, ssg_sbl_line_t *lines, int64_t *line_req, ssg_sbl_end_t *ends, int64_t *prim, uint64_t *sig, uint8_t *dup,
+                        uint8_t *bits, int64_t *mate_line, uint64_t counts[4], uint64_t *keys)
+{
+	const char *who = "ssg_dbg_sbl_records";
+	CHK(ssg_need_device());
+	*n_lines = 0; memset(counts, 0, 4 * sizeof(uint64_t));
+	if (n_pairs < 0 || n_pairs >= (1L << 31)) { ssg_err_msg = "ssg_dbg_sbl_records: need 0 <= n_pairs < 2^31"; return SSG_EINVAL; }
+	if (o->max_split_count > SSG_STAGE_SBL_MAX_SPLIT) { ssg_err_msg = "samblaster: --maxSplitCount above 16 is not supported"; return SSG_EINVAL; }
+	if (n_pairs == 0) { line_off[0] = 0; return SSG_OK; }
+	if (req_off[0] != 0) return dbg_refuse(who, "offsets start at 0: read", 0);
+	const long n_reads = 2 * n_pairs;
+	for (long r = 0; r < n_reads; ++r) {
+		if (req_off[r + 1] < req_off[r]) return dbg_refuse(who, "offsets must not decrease: read", r);
+		int n_main = 0;
+		for (int64_t g = req_off[r]; g < req_off[r + 1]; ++g) {
+			if (req[g].kind != SSG_REQ_MAIN && req[g].kind != SSG_REQ_XA) return dbg_refuse(who, "kind is SSG_REQ_MAIN or SSG_REQ_XA: request", (long)g);
+			if (alns[g].n_cigar < 0 || alns[g].n_cigar > SSG_MAX_CIGAR) return dbg_refuse(who, "need 0 <= n_cigar <= " SSG_STR(SSG_MAX_CIGAR) ": record", (long)g);
+			n_main += req[g].kind == SSG_REQ_MAIN;
+		}
+		if (!n_main) return dbg_refuse(who, "a read without a main request: read", r);
+		if (req[req_off[r]].kind != SSG_REQ_MAIN) return dbg_refuse(who, "the first request of a read is a main one (its mate's lines print against it): read", r);
+	}
+	const size_t nreq = (size_t)req_off[n_reads];
+	dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_alnreq_t> d_req(nreq + 1); dbuf<ssg_aln_t> d_alns(nreq + 1); dbuf<uint64_t> d_sig(3 * (size_t)n_pairs);
+	CHKA(d_off); CHKA(d_req); CHKA(d_alns); CHKA(d_sig);
+	CHK(d_off.up(req_off, (size_t)n_reads + 1)); CHK(d_req.up(req, nreq)); CHK(d_alns.up(alns, nreq));
+	sbl_lines_t L;
+	CHK(records_lines(n_pairs, d_off.p, d_req.p, d_alns.p, &L));
+	CHK(records_dedup(st, n_pairs, L.ends.p, L.dup.p, d_sig.p));
+	CHK(records_classify(n_pairs, &L, o, L.dup.p, counts));
+	const size_t nl = (size_t)L.n_lines;
+	dbuf<uint64_t> d_keys(nl + 1);
+	CHKA(d_keys);
+	CHK(records_export(&L, d_alns.p, d_keys.p, 0, 0));
+	*n_lines = L.n_lines;
+	CHK(L.line_off.down(line_off, (size_t)n_pairs + 1)); CHK(L.lines.down(lines, nl)); CHK(L.line_req.down(line_req, nl)); CHK(L.ends.down(ends, 2 * (size_t)n_pairs));
+	CHK(L.prim.down(prim, 2 * (size_t)n_pairs)); CHK(d_sig.down(sig, 3 * (size_t)n_pairs)); CHK(L.dup.down(dup, (size_t)n_pairs)); CHK(L.bits.down(bits, nl));
+	CHK(L.mate.down(mate_line, nl));
+	return d_keys.down(keys, nl);
 }

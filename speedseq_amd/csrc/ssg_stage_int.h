@@ -12,9 +12,10 @@
 
 #define SSG_STR_(x) #x
 #define SSG_STR(x) SSG_STR_(x)
-/* two constants of kernel headers, under names of their own; ssgpu_core.cpp, which sees both, asserts that they agree */
+/* three constants of kernel headers, under names of their own; ssgpu_core.cpp, which sees both, asserts that they agree */
 #define SSG_STAGE_TWIN_GLB 32768   /* SSG_TWIN_GLB (k_extend.h): the longest reference window of a region */
 #define SSG_STAGE_R2D_CLASSES 3    /* SSG_R2D_CLASSES (k_aln.h): band classes of the CIGAR stage's lane DP */
+#define SSG_STAGE_SBL_MAX_SPLIT 16 /* SSG_SBL_MAX_SPLIT (k_sbl.h): the largest --maxSplitCount of the splitter test */
 
 struct align1_dev_t {	/* device-resident result of stages 1-4 */
 	dbuf<int64_t> seed_off; dbuf<ssg_alnreg_t> regs; dbuf<int32_t> n_reg;
@@ -28,6 +29,12 @@ struct msw_stage_t { unsigned long long cells, windows, from_slots, left_windows
  * d_pw = the pairs heaviest first (key: candidate regions of both ends); d_regs2 = the regions (d_regoff, d_regs, d_nreg) copied into their slices. */
 struct pair_slices_t {
 	dbuf<int32_t> d_cap2, d_capq, d_pkey, d_pw; dbuf<int64_t> d_r2off, d_reqoff; dbuf<ssg_alnreg_t> d_regs2; int64_t t2, tq;
+};
+/* the samblaster view of a call's records in HBM (k_sbl.h): per pair the offset of its SAM lines, per line the line, the request it prints, what classification
+ * leaves (bits, mate line); per pair the two primaries (line index or -1), their ends and the duplicate verdict */
+struct sbl_lines_t {
+	int64_t n_lines = 0;
+	dbuf<int64_t> line_off, line_req, prim, mate; dbuf<ssg_sbl_line_t> lines; dbuf<ssg_sbl_end_t> ends; dbuf<uint8_t> bits, dup;
 };
 struct reg2aln_in_t { const ssg_index_t *idx; const ssg_mem_opt_t *opt; const ssg_alnreg_t *d_regs; const uint8_t *d_seq; const int64_t *d_off; int max_len; unsigned long long *d_cnt; uint64_t *stats; };
 
@@ -56,4 +63,8 @@ int run_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, co
 void msw_counts(const msw_stage_t &m, uint64_t counts[8]);   /* counts[0 .. 6] of ssg_dbg_matesw / ssg_dbg_matesw_last (include/ssgpu.h); counts[7] = 0 */
 int make_pair_slices(int n_reads, const int64_t *d_regoff, const ssg_alnreg_t *d_regs, const int32_t *d_nreg, int max_matesw, pair_slices_t &s);
 int run_req_tail(int n_reads, const int64_t *d_reqoff, const ssg_alnreq_t *d_req, const int32_t *d_nreq, int64_t *h_off, const reg2aln_in_t *a, pe_dev_t &t);
+int records_lines(long n_pairs, const int64_t *d_req_off, const ssg_alnreq_t *d_req, const ssg_aln_t *d_alns, sbl_lines_t *R);
+int records_dedup(ssg_sbl_state_t *st, long n_pairs, const ssg_sbl_end_t *d_ends, uint8_t *d_dup, uint64_t *d_sig_out);
+int records_classify(long n_pairs, sbl_lines_t *R, const ssg_sbl_opt_t *o, const uint8_t *d_dup, uint64_t counts[4]);
+int records_export(const sbl_lines_t *R, const ssg_aln_t *d_alns, uint64_t *d_keys, ssg_aln_t *d_recs, uint8_t *d_bits);
 #endif

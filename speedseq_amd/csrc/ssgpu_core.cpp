@@ -1146,7 +1146,8 @@ static thread_local unsigned int ssg_r2a_last[1 + SSG_R2D_CLASSES];   /* of this
 /* CIGAR / NM / MD of the compacted requests (k_aln.h): gap-free records one lane each; records whose band is narrow one lane each through the DP (three classes of
  * band width, a launch each with the LDS that class needs, side by side); the rest -- wide bands, and records whose first alignment does not end upstream's
  * loop -- one wave each.  SSG_R2A_DPLANE=0: no lane DP (A/B, tests). */
-static_assert(SSG_STAGE_R2D_CLASSES == SSG_R2D_CLASSES && SSG_STAGE_TWIN_GLB == SSG_TWIN_GLB, "ssg_stage_int.h disagrees with k_aln.h or k_extend.h about a constant");
+static_assert(SSG_STAGE_R2D_CLASSES == SSG_R2D_CLASSES && SSG_STAGE_TWIN_GLB == SSG_TWIN_GLB && SSG_STAGE_SBL_MAX_SPLIT == SSG_SBL_MAX_SPLIT,
+              "ssg_stage_int.h disagrees with k_aln.h, k_extend.h or k_sbl.h about a constant");
 /* The lane DP keeps h and e in 16 bits with "minus infinity" at SSG_R2D_NEG.  Its comparisons come out as upstream's while every value of a reachable cell, and every
  * gap-opening candidate made of one, lies above everything derived from minus infinity (at most SSG_R2D_NEG + a); what is stored then stays above -32768 as well.  A
  * reachable in-band H is at least the score of the path "down the main diagonal, then one gap of |i - j| <= 33": -(b' min(i, j) + o + 33 e) with b' = max(b, 1) (an N
@@ -1566,6 +1567,47 @@ static int sbl_process_dev(ssg_sbl_state *st, const ssg_sbl_opt_t *o, long n_blo
 	return rt_sync();
 }
 
+/* SAM lines of a call's records in HBM (k_sbl.h) and the two primary ends per pair; for the pipeline and the test entry ssg_dbg_sbl_records alike */
+int records_lines(long n_pairs, const int64_t *d_req_off, const ssg_alnreq_t *d_req, const ssg_aln_t *d_alns, sbl_lines_t *R)
+{
+	const int block = 256;
+	dbuf<int32_t> d_nl(n_pairs);
+	CHKA(d_nl);
+	if (!R->line_off.alloc(n_pairs + 1)) { ssg_err_msg = "device allocation failed: line offsets"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_sbl_count_lines, (n_pairs + block - 1) / block, block, 0, n_pairs, d_req_off, d_req, d_nl.p);
+	CHK(ssg_dev_exclusive_scan(d_nl.p, R->line_off.p, n_pairs, &R->n_lines));
+	const size_t nl = (size_t)R->n_lines + 1;
+	if (!R->lines.alloc(nl) || !R->line_req.alloc(nl) || !R->prim.alloc(2 * n_pairs) || !R->mate.alloc(nl) || !R->bits.alloc(nl) || !R->ends.alloc(2 * n_pairs) || !R->dup.alloc(n_pairs)) {
+		ssg_err_msg = "device allocation failed: samblaster lines"; return SSG_ENOMEM; }
+	SSG_LAUNCH(ssg_k_sbl_lines_from_alns, (n_pairs + block - 1) / block, block, 0, n_pairs, d_req_off, d_req, d_alns, R->line_off.p, R->lines.p, R->line_req.p);
+	SSG_LAUNCH(ssg_k_sbl_ends, (n_pairs + block - 1) / block, block, 0, n_pairs, R->line_off.p, R->lines.p, R->ends.p, R->prim.p);
+	return 0;
+}
+int records_classify(long n_pairs, sbl_lines_t *R, const ssg_sbl_opt_t *o, const uint8_t *d_dup, uint64_t counts[4])
+{	/* counts: [0] duplicate pairs [1] lines to the discordant stream [2] lines to the splitter stream [3] SAM lines */
+	const int block = 256;
+	if (o->max_split_count > SSG_SBL_MAX_SPLIT) { ssg_err_msg = "samblaster: --maxSplitCount above 16 is not supported"; return SSG_EINVAL; }
+	SSG_LAUNCH(ssg_k_sbl_classify, (n_pairs + block - 1) / block, block, 0, *o, n_pairs, R->line_off.p, R->lines.p, R->prim.p, d_dup, R->bits.p, R->mate.p);
+	dbuf<unsigned int> d_c(4);
+	CHKA(d_c); CHK(d_c.zero());
+	SSG_LAUNCH(ssg_k_sbl_count_bits, (R->n_lines + block - 1) / block, block, 0, R->n_lines, R->bits.p, n_pairs, d_dup, d_c.p);
+	unsigned int c[4];
+	CHK(d_c.down(c, 4));
+	counts[0] = c[0]; counts[1] = c[1]; counts[2] = c[2]; counts[3] = (uint64_t)R->n_lines;
+	return 0;
+}
+/* the duplicate stage of the records' ends, for ssg_dbg_sbl_records: dedup_core with the signatures as plain words (n_pairs x 3, may be 0) */
+int records_dedup(ssg_sbl_state *st, long n_pairs, const ssg_sbl_end_t *d_ends, uint8_t *d_dup, uint64_t *d_sig_out)
+{
+	return dedup_core(st, n_pairs, d_ends, d_dup, (ssg_sig_t*)d_sig_out);
+}
+/* sort keys, records (d_recs may be 0) and bits (d_bits may be 0) of the lines, in line order (ssg_k_sbl_export) */
+int records_export(const sbl_lines_t *R, const ssg_aln_t *d_alns, uint64_t *d_keys, ssg_aln_t *d_recs, uint8_t *d_bits)
+{
+	if (R->n_lines > 0) SSG_LAUNCH(ssg_k_sbl_export, (R->n_lines + 255) / 256, 256, 0, R->n_lines, R->lines.p, R->line_req.p, d_alns, R->bits.p, d_keys, d_recs, d_bits);
+	return rt_sync();
+}
+
 extern "C" {
 
 static int process_pairs_host(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *off,
@@ -1705,27 +1747,10 @@ int ssg_sbl_classify(const ssg_sbl_opt_t *o, long n_blocks, const int64_t *blk_o
 }
 
 /* aligned records of one call kept in HBM with their samblaster view (lines, primaries), for the stages after alignment */
-struct ssg_dev_records {
-	pe_dev_t keep; long n_pairs; int64_t n_lines;
-	dbuf<int64_t> line_off, line_req, prim, mate; dbuf<ssg_sbl_line_t> lines; dbuf<ssg_sbl_end_t> ends; dbuf<uint8_t> bits, dup;
+struct ssg_dev_records : sbl_lines_t {
+	pe_dev_t keep; long n_pairs;
 };
 
-/* SAM lines of the kept records (k_sbl.h) and the two primary ends per pair */
-static int records_lines(struct ssg_dev_records *R)
-{
-	const long n_pairs = R->n_pairs; const int block = 256;
-	dbuf<int32_t> d_nl(n_pairs);
-	CHKA(d_nl);
-	if (!R->line_off.alloc(n_pairs + 1)) { ssg_err_msg = "device allocation failed: line offsets"; return SSG_ENOMEM; }
-	SSG_LAUNCH(ssg_k_sbl_count_lines, (n_pairs + block - 1) / block, block, 0, n_pairs, R->keep.req_off.p, R->keep.req.p, d_nl.p);
-	CHK(ssg_dev_exclusive_scan(d_nl.p, R->line_off.p, n_pairs, &R->n_lines));
-	const size_t nl = (size_t)R->n_lines + 1;
-	if (!R->lines.alloc(nl) || !R->line_req.alloc(nl) || !R->prim.alloc(2 * n_pairs) || !R->mate.alloc(nl) || !R->bits.alloc(nl) || !R->ends.alloc(2 * n_pairs) || !R->dup.alloc(n_pairs)) {
-		ssg_err_msg = "device allocation failed: samblaster lines"; return SSG_ENOMEM; }
-	SSG_LAUNCH(ssg_k_sbl_lines_from_alns, (n_pairs + block - 1) / block, block, 0, n_pairs, R->keep.req_off.p, R->keep.req.p, R->keep.alns.p, R->line_off.p, R->lines.p, R->line_req.p);
-	SSG_LAUNCH(ssg_k_sbl_ends, (n_pairs + block - 1) / block, block, 0, n_pairs, R->line_off.p, R->lines.p, R->ends.p, R->prim.p);
-	return 0;
-}
 static int process_pairs_host(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs, const uint8_t *seq, const int64_t *off,
                               const int32_t *pair_batch, int n_batches, int64_t id0, const ssg_pestat_t *pes0, ssg_pe_result_t **out)
 {
@@ -1747,19 +1772,6 @@ static int process_pairs_host(const ssg_index_t *idx, const ssg_mem_opt_t *opt, 
 	*out = res.release();
 	return 0;
 }
-static int records_classify(ssg_dev_records *R, const ssg_sbl_opt_t *o, const uint8_t *d_dup, uint64_t counts[4])
-{	/* counts: [0] duplicate pairs [1] lines to the discordant stream [2] lines to the splitter stream [3] SAM lines */
-	const long n_pairs = R->n_pairs; const int block = 256;
-	if (o->max_split_count > SSG_SBL_MAX_SPLIT) { ssg_err_msg = "samblaster: --maxSplitCount above 16 is not supported"; return SSG_EINVAL; }
-	SSG_LAUNCH(ssg_k_sbl_classify, (n_pairs + block - 1) / block, block, 0, *o, n_pairs, R->line_off.p, R->lines.p, R->prim.p, d_dup, R->bits.p, R->mate.p);
-	dbuf<unsigned int> d_c(4);
-	CHKA(d_c); CHK(d_c.zero());
-	SSG_LAUNCH(ssg_k_sbl_count_bits, (R->n_lines + block - 1) / block, block, 0, R->n_lines, R->bits.p, n_pairs, d_dup, d_c.p);
-	unsigned int c[4];
-	CHK(d_c.down(c, 4));
-	counts[0] = c[0]; counts[1] = c[1]; counts[2] = c[2]; counts[3] = (uint64_t)R->n_lines;
-	return 0;
-}
 
 /* The measured hot path (bench.py): device-resident reads in; aligned, duplicate-marked and side-stream-classified records
  * left in HBM (rows a1-a12, a14-a17).  d_seq / d_off / d_pair_batch are DEVICE pointers.  summary[0] = records,
@@ -1778,7 +1790,7 @@ int ssg_hotpath_dev_ex(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
 	ssg_pe_result res; std::unique_ptr<ssg_dev_records> R(new ssg_dev_records());
 	R->n_pairs = n_pairs;
 	CHK(ssg_pe_core(idx, opt, n_pairs, d_seq, d_off, max_len, d_pair_batch, n_batches, id0, 0, &res, &R->keep));
-	CHK(records_lines(R.get()));
+	CHK(records_lines(n_pairs, R->keep.req_off.p, R->keep.req.p, R->keep.alns.p, R.get()));
 	memset(summary, 0, 16 * sizeof(uint64_t));
 	if (local_dedup || d_sig_out) {
 		dbuf<ssg_sig_t> d_sigb;
@@ -1786,7 +1798,7 @@ int ssg_hotpath_dev_ex(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
 	}
 	if (local_dedup) {
 		uint64_t c[4];
-		CHK(records_classify(R.get(), &so, R->dup.p, c));
+		CHK(records_classify(n_pairs, R.get(), &so, R->dup.p, c));
 		summary[1] = c[0]; summary[8] = c[1]; summary[9] = c[2]; summary[10] = c[3];
 		if (dup_host) CHK(R->dup.down(dup_host, n_pairs));
 	}
@@ -1800,7 +1812,7 @@ int ssg_hotpath_dev_ex(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_p
 int ssg_dev_records_classify(ssg_dev_records_t *R, const ssg_sbl_opt_t *sbl, const uint8_t *d_dup, uint64_t counts[4])
 {
 	ssg_sbl_opt_t so; if (sbl) so = *sbl; else { ssg_sbl_opt_init(&so); so.exclude_dups = 1; so.add_mate_tags = 1; }
-	return records_classify(R, &so, d_dup, counts);
+	return records_classify(R->n_pairs, R, &so, d_dup, counts);
 }
 void ssg_dev_records_free(ssg_dev_records_t *R) { delete R; }
 int64_t ssg_dev_records_n_lines(const ssg_dev_records_t *R) { return R->n_lines; }
@@ -1808,8 +1820,7 @@ size_t ssg_dev_record_bytes(void) { return sizeof(ssg_aln_t); }
 /* keys (n_lines x u64), records (n_lines x ssg_dev_record_bytes(), may be NULL) and side-stream bits (n_lines, may be NULL) into DEVICE buffers of the caller */
 int ssg_dev_records_export(const ssg_dev_records_t *R, uint64_t *d_keys, void *d_recs, uint8_t *d_bits)
 {
-	if (R->n_lines > 0) SSG_LAUNCH(ssg_k_sbl_export, (R->n_lines + 255) / 256, 256, 0, R->n_lines, R->lines.p, R->line_req.p, R->keep.alns.p, R->bits.p, d_keys, (ssg_aln_t*)d_recs, d_bits);
-	return rt_sync();
+	return records_export(R, R->keep.alns.p, d_keys, (ssg_aln_t*)d_recs, d_bits);
 }
 
 /* the kept records back on the host as an ssg_pe_result_t (ssg_pe_* accessors, ssg_sam_format) together with, per SAM line in line

@@ -1,4 +1,4 @@
-"""What the six stage test entries (ssg_dbg_chain, ssg_dbg_regions, ssg_dbg_reg2aln, ssg_dbg_pestat, ssg_dbg_pair_final, ssg_dbg_matesw) answer to malformed
+"""What the seven stage test entries (ssg_dbg_chain, ssg_dbg_regions, ssg_dbg_reg2aln, ssg_dbg_pestat, ssg_dbg_pair_final, ssg_dbg_matesw, ssg_dbg_sbl_records) answer to malformed
 input: the return code AND the whole message, and which refusal wins where two apply.  The reference tests of the stages mostly ask for "-22" alone; the strings
 below were taken from the library as it stood before the entries moved into a translation unit of their own, so a message or an order of checks that changes with
 such a move fails here.
@@ -15,6 +15,7 @@ Literals of the entries' source, counted by hand (each `bad = "..."` and each di
   ssg_dbg_pestat     2 direct           reached: 2
   ssg_dbg_pair_final 1 direct           reached: 1
   ssg_dbg_matesw     4 direct           reached: 4 (and its unprefixed "reads longer than 310 bases ...")
+  ssg_dbg_sbl_records 6 refusals + 2 direct  reached: 6 + 1 (and the unprefixed "samblaster: --maxSplitCount above 16 ..."; not "n_pairs < 2^31": 2^32 offsets)
 plus the scoring limits the entries call (check_band, check_scores, check_gap_penalties: 4 messages).  Not reachable by any input a test can hold: "more than 2^31
 seeds" of chain and regions (every read has fewer than 2^24 seeds and each is read by the validator: 48 GB of seeds), and the four SSG_EOVERFLOW messages about
 counts "outside its slice", which only a kernel that wrote nonsense could cause.
@@ -346,7 +347,37 @@ def matesw_cases(lib, b):
         (dict(seq=ch(seq, None, 5, 150), regs=ch(rg, "qe", 101)), P + "bases are codes 0 .. 4")]
 
 
-ENTRIES = dict(chain=(lambda lib: base_chain(), call_chain, chain_cases), regions=(lambda lib: base_regions(), call_regions, regions_cases),
+def base_sbl_records(lib):
+    """one pair: read 1 with a main, an XA and a second main request, read 2 with one main request"""
+    req, alns = np.zeros(4, capi.ALNREQ_DT), np.zeros(4, capi.ALN_DT)
+    req["kind"] = [0, 1, 0, 0]
+    alns["rid"], alns["pos"], alns["flag"], alns["n_cigar"] = [0, 1, 1, 0], [100, 5, 700, 400], [0x40, 0, 0x840, 0x80], 1
+    alns["cigar"][:, 0] = 100 << 4
+    return dict(req_off=i64(0, 3, 4), req=req, alns=alns, sbl=capi.sbl_opt_init(lib))
+
+
+def call_sbl_records(lib, a):
+    rc, _ = capi.dbg_sbl_records(lib, a["req_off"], a["req"], a["alns"], a["sbl"])
+    return answer(lib, rc)
+
+
+def sbl_records_cases(lib, b):
+    P = "ssg_dbg_sbl_records: "
+    split = "samblaster: --maxSplitCount above 16 is not supported"
+    rq, al = b["req"], b["alns"]
+    return [(dict(), None), (dict(req_off=i64(0), req=rq[:0], alns=al[:0]), None), (dict(sbl=capi.sbl_opt_init(lib, max_split_count=16)), None),
+            (dict(sbl=capi.sbl_opt_init(lib, max_split_count=17)), split), (dict(sbl=capi.sbl_opt_init(lib, max_split_count=17), req_off=i64(1, 3, 4)), split),
+            (dict(req_off=i64(1, 3, 4)), P + "offsets start at 0: read 0"), (dict(req_off=i64(0, 4, 3)), P + "offsets must not decrease: read 1"),
+            (dict(req_off=i64(0, 4, 4)), P + "a read without a main request: read 1"), (dict(req=ch(rq, "kind", 1, 3)), P + "a read without a main request: read 1"),
+            (dict(req=ch(rq, "kind", 1, 0)), P + "the first request of a read is a main one (its mate's lines print against it): read 0"),
+            (dict(req=ch(rq, "kind", 2, 1)), P + "kind is SSG_REQ_MAIN or SSG_REQ_XA: request 1"), (dict(req=ch(rq, "kind", -1, 2)), P + "kind is SSG_REQ_MAIN or SSG_REQ_XA: request 2"),
+            (dict(alns=ch(al, "n_cigar", 65, 2)), P + "need 0 <= n_cigar <= 64: record 2"), (dict(alns=ch(al, "n_cigar", -1, 1)), P + "need 0 <= n_cigar <= 64: record 1"),
+            (dict(alns=ch(al, "n_cigar", 64, 3)), None), (dict(alns=ch(al, "n_cigar", 0, 0)), None),
+            (dict(alns=ch(al, "n_cigar", 65, 3), req_off=i64(0, 3, 2)), P + "offsets must not decrease: read 1"),
+            (dict(alns=ch(al, "n_cigar", 65, 3), req=ch(rq, "kind", 1, 0)), P + "the first request of a read is a main one (its mate's lines print against it): read 0")]
+
+
+ENTRIES = dict(sbl_records=(base_sbl_records, call_sbl_records, sbl_records_cases), chain=(lambda lib: base_chain(), call_chain, chain_cases), regions=(lambda lib: base_regions(), call_regions, regions_cases),
                reg2aln=(lambda lib: base_reg2aln(), call_reg2aln, reg2aln_cases), pestat=(base_pair, call_pestat, pestat_cases),
                pair_final=(base_pair, call_pair_final, pair_final_cases), matesw=(base_pair, call_matesw, matesw_cases))
 
