@@ -118,6 +118,24 @@ int ssg_extend_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int 
 int ssg_align2_lane_batch(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_jobs, const ssg_sw_job_t *jobs, const int64_t *tpos,
                           const uint8_t *qbuf, size_t qbytes, int lanes, ssg_kswr_t *res, int32_t *from_lane);
 
+/* Test entries of the seeding kernels (csrc/k_smem2.h).
+ *   ssg_dbg_extend_coop  one upstream bwt_extend per item, followed base base[t] (0 .. 3) and direction is_back[t] (0 / 1) on interval in[t] (x0, x1, x2; info is
+ *                        ignored), once by ssg_bwt_extend1_lean, the lane kernel's form (out_lean), and once by s2_extend_coop, the form of the wave-per-read
+ *                        kernel's chains, whose rank work 16 lanes share (out_coop): the two must be equal in x0, x1, x2 and info.  out_lean4 / out_coop4 (4 n
+ *                        entries): entry 4 t + g is the interval of item (t + g) mod n extended by item t's base in item t's direction, by ssg_bwt_extend1_lean and by
+ *                        s2_extend_coop4, the form of the kernel's short backward rows, which does four intervals at once; equal again.  Validated first,
+ *                        SSG_EINVAL otherwise: the rank queries of either direction inside the text (x0 + x2 and x1 + x2 <= text length + 1).
+ *   ssg_dbg_smem_ext     ssg_smem_batch through the seeding stage's two kernels alone, with what the stage reports to the step's summary: *n_extend = the
+ *                        bwt_extend calls of upstream mem_collect_intv on these reads, whichever kernel took a read and however often it started on it.  The
+ *                        lists are unsorted (the stage sorts them afterwards); a list longer than cap is SSG_EOVERFLOW.  SSG_SMEM_MAX_EXT / SSG_SMEM_MAX_ROW /
+ *                        SSG_KTAB_K act as in the pipeline.  paths[4]: the reads the wave-per-read kernel took up and how -- [0] resumed in pass 1 where the lane kernel's
+ *                        unfinished call began, at x > 0; [1] resumed in pass 2; [2] started again because the lane kernel had not finished the third pass; [3] taken up
+ *                        in pass 1 at the read's start. */
+int ssg_dbg_extend_coop(const ssg_index_t *idx, int n, const ssg_intv_t *in, const uint8_t *base, const uint8_t *is_back, ssg_intv_t *out_lean, ssg_intv_t *out_coop,
+                        ssg_intv_t *out_lean4, ssg_intv_t *out_coop4);
+int ssg_dbg_smem_ext(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off, int cap, ssg_intv_t *out_intv, int32_t *out_n,
+                     uint64_t *n_extend, uint32_t paths[4]);
+
 /* Test hook for the chaining kernels' weight sort (csrc/k_chainw.h wv_introsort_whi; upstream ks_introsort over chain weights, bwamem.c mem_chain_flt's
  * ks_introsort(mem_flt, ...) with its unstable tie order): sorts n <= 5120 words (w << 32 | id) by w, descending, once by the whole wave (out_wave) and
  * once by one lane running the textbook loops (out_lane); the two must be equal word for word. */

@@ -152,6 +152,27 @@ class Lib:
         self._chk(self.l.ssg_smem_batch(idx, _ptr(opt), C.c_int(n), _ptr(seq), _ptr(off), C.c_int(cap), _ptr(intv), _ptr(cnt)))
         return intv, cnt
 
+    def dbg_smem_ext(self, idx, opt, seq, off, cap=64):
+        """the seeding stage's two kernels alone (ssg_dbg_smem_ext): (intervals unsorted, counts, upstream's bwt_extend count over the reads, the wave
+        kernel's reads by how it took them up: resumed in pass 1 at x > 0, resumed in pass 2, started again for an unfinished third pass, pass 1 from the start)"""
+        n = len(off) - 1
+        intv = np.zeros((n, cap), dtype=INTV_DT)
+        cnt = np.zeros(n, dtype=np.int32)
+        nx = C.c_uint64(0)
+        paths = np.zeros(4, dtype=np.uint32)
+        self._chk(self.l.ssg_dbg_smem_ext(idx, _ptr(opt), C.c_int(n), _ptr(seq), _ptr(off), C.c_int(cap), _ptr(intv), _ptr(cnt), C.byref(nx), _ptr(paths)))
+        return intv, cnt, nx.value, [int(x) for x in paths]
+
+    def dbg_extend_coop(self, idx, intv, base, is_back):
+        """one bwt_extend per item by ssg_bwt_extend1_lean and by s2_extend_coop, and four at a time by the former and by s2_extend_coop4 (ssg_dbg_extend_coop):
+        (lean, coop [INTV_DT, n], lean4, coop4 [INTV_DT, n x 4]: item t's base and direction on the intervals of items t .. t + 3 mod n)"""
+        intv = np.ascontiguousarray(intv, dtype=INTV_DT)
+        base, is_back = np.ascontiguousarray(base, dtype=np.uint8), np.ascontiguousarray(is_back, dtype=np.uint8)
+        n = len(intv)
+        lean, coop, lean4, coop4 = np.zeros(n, dtype=INTV_DT), np.zeros(n, dtype=INTV_DT), np.zeros((n, 4), dtype=INTV_DT), np.zeros((n, 4), dtype=INTV_DT)
+        self._chk(self.l.ssg_dbg_extend_coop(idx, C.c_int(n), _ptr(intv), _ptr(base), _ptr(is_back), _ptr(lean), _ptr(coop), _ptr(lean4), _ptr(coop4)))
+        return lean, coop, lean4, coop4
+
     def seeds_batch(self, idx, opt, seq, off):
         """seeds of every read before chaining: (seed_off, seeds[rbeg qbeg len score next], rids)"""
         n = len(off) - 1

@@ -1,6 +1,6 @@
 /*
  * ssg_dbg.cpp -- the stage test entries of include/ssgpu.h: ssg_dbg_chain, ssg_dbg_regions, ssg_dbg_reg2aln, ssg_dbg_pestat, ssg_dbg_pair_final,
- * ssg_dbg_matesw and ssg_dbg_sbl_records.  Each checks lists built by the caller until nothing out of range can reach a kernel, lays them out as the stage before leaves them, and
+ * ssg_dbg_matesw, ssg_dbg_sbl_records, ssg_dbg_extend_coop and ssg_dbg_smem_ext.  Each checks lists built by the caller until nothing out of range can reach a kernel, lays them out as the stage before leaves them, and
  * runs the pipeline's own stage function on them (ssgpu_core.cpp, through ssg_stage_int.h).  A translation unit of its own so that the stage code of the core
  * reads without them -- and one that must never include a kernel header (k_*.h) or launch a kernel: the machine code of every kernel depends on what else
  * its unit holds, and that code is pinned (tools/isa_pin.py).  Device work goes through dbuf<> and the core's host functions.
@@ -468,6 +468,65 @@ int ssg_dbg_matesw(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_pairs
 	msw_counts(ms, counts);
 	*regs_out = out;
 	return SSG_OK;
+}
+
+/* test entry: one bwt_extend per item by the seeding kernels' two forms (include/ssgpu.h); the kernel is ssg_seed.cpp's */
+int ssg_dbg_extend_coop(const ssg_index_t *idx, int n, const ssg_intv_t *in, const uint8_t *base, const uint8_t *is_back, ssg_intv_t *out_lean, ssg_intv_t *out_coop,
+                        ssg_intv_t *out_lean4, ssg_intv_t *out_coop4)
+{
+	CHK(ssg_need_device());
+	if (n < 0 || n > 1 << 24) { ssg_err_msg = "ssg_dbg_extend_coop: need 0 <= n <= 2^24"; return SSG_EINVAL; }
+	if (n == 0) return SSG_OK;
+	const uint64_t seq_len = idx->v.seq_len;
+	std::vector<uint8_t> cd((size_t)n);
+	for (int t = 0; t < n; ++t) {
+		if (base[t] > 3) return dbg_refuse("ssg_dbg_extend_coop", "bases are codes 0 .. 3: item", t);
+		if (is_back[t] > 1) return dbg_refuse("ssg_dbg_extend_coop", "is_back is 0 or 1: item", t);
+		/* the rank queries are rows kx - 1 (-1 allowed) and kx - 1 + x2 of the text with its sentinel: rows 0 .. seq_len; an item's interval is also extended
+		 * in its neighbours' direction (the four-interval form), so both sides must do */
+		for (int side = 0; side < 2; ++side) {
+			const uint64_t kx = side ? in[t].x0 : in[t].x1;
+			if (kx > seq_len + 1 || in[t].x2 > seq_len + 1 || kx + in[t].x2 > seq_len + 1) return dbg_refuse("ssg_dbg_extend_coop", "need x0 + x2 <= text length + 1 and x1 + x2 <= text length + 1: item", t);
+		}
+		cd[t] = (uint8_t)(base[t] | is_back[t] << 2);
+	}
+	dbuf<ssg_intv_t> d_in((size_t)n), d_lean((size_t)n), d_coop((size_t)n), d_lean4((size_t)n * 4), d_coop4((size_t)n * 4); dbuf<uint8_t> d_cd((size_t)n);
+	CHKA(d_in); CHKA(d_lean); CHKA(d_coop); CHKA(d_lean4); CHKA(d_coop4); CHKA(d_cd);
+	CHK(d_in.up(in, (size_t)n)); CHK(d_cd.up(cd.data(), (size_t)n)); CHK(d_lean.zero()); CHK(d_coop.zero()); CHK(d_lean4.zero()); CHK(d_coop4.zero());
+	CHK(ssg_seed_dbg_extend_coop(idx, n, d_in.p, d_cd.p, d_lean.p, d_coop.p, d_lean4.p, d_coop4.p));
+	CHK(d_lean.down(out_lean, (size_t)n)); CHK(d_coop.down(out_coop, (size_t)n)); CHK(d_lean4.down(out_lean4, (size_t)n * 4));
+	return d_coop4.down(out_coop4, (size_t)n * 4);
+}
+
+/* test entry: the seeding kernels on the caller's reads with the extension count (include/ssgpu.h), through ssg_seed_smem2 as the pipeline's seeding stage goes through it */
+int ssg_dbg_smem_ext(const ssg_index_t *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *seq, const int64_t *off, int cap, ssg_intv_t *out_intv, int32_t *out_n, uint64_t *n_extend, uint32_t paths[4])
+{
+	CHK(ssg_need_device());
+	*n_extend = 0; memset(paths, 0, 4 * sizeof(uint32_t));
+	if (n_reads < 0 || cap < 1) { ssg_err_msg = "ssg_dbg_smem_ext: need n_reads >= 0, cap >= 1"; return SSG_EINVAL; }
+	if (n_reads == 0) return SSG_OK;
+	if (off[0] != 0) return dbg_refuse("ssg_dbg_smem_ext", "offsets start at 0: read", 0);
+	int max_len = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		const char *bad = 0;
+		const int64_t len = off[r + 1] - off[r];   /* (an empty read is a read: ssg_smem_batch takes it) */
+		if (len < 0) bad = "offsets must not decrease: read";
+		else if (len > SSG_MAX_READ_LEN) bad = "need read length <= " SSG_STR(SSG_MAX_READ_LEN) ": read";
+		if (!bad) dbg_check_codes(seq, off, r, &bad);
+		if (bad) return dbg_refuse("ssg_dbg_smem_ext", bad, r);
+		max_len = std::max(max_len, (int)len);
+	}
+	const char *e = getenv("SSG_SMEM_MAX_EXT");
+	const unsigned int max_ext = e && *e ? (unsigned int)atoi(e) : (unsigned int)(13 * max_len + 50);   /* the seeding stage's own default */
+	dbuf<uint8_t> d_seq((size_t)off[n_reads] + 1); dbuf<int64_t> d_off((size_t)n_reads + 1); dbuf<ssg_intv_t> d_intv((size_t)n_reads * cap); dbuf<int32_t> d_n((size_t)n_reads); dbuf<unsigned long long> d_nx(1); dbuf<unsigned int> d_paths(4);
+	CHKA(d_seq); CHKA(d_off); CHKA(d_intv); CHKA(d_n); CHKA(d_nx); CHKA(d_paths);
+	CHK(d_seq.up(seq, (size_t)off[n_reads])); CHK(d_off.up(off, (size_t)n_reads + 1)); CHK(d_nx.zero()); CHK(d_paths.zero());
+	CHK(ssg_seed_smem2_paths(idx, opt, n_reads, d_seq.p, d_off.p, max_len, cap, d_intv.p, d_n.p, d_nx.p, max_ext, d_paths.p));
+	unsigned long long nx = 0;
+	CHK(d_nx.down(&nx, 1)); CHK(d_intv.down(out_intv, (size_t)n_reads * cap)); CHK(d_n.down(out_n, (size_t)n_reads));
+	for (int r = 0; r < n_reads; ++r) if (out_n[r] < 0) { ssg_err_msg = "ssg_dbg_smem_ext: a read's list exceeds the per-read capacity"; return SSG_EOVERFLOW; }
+	*n_extend = nx;
+	return d_paths.down(paths, 4);
 }
 
 /* test entry: samblaster's stage of the timed step on the caller's records (include/ssgpu.h), through the host functions ssg_hotpath_dev_ex runs after alignment */

@@ -115,6 +115,30 @@ SSG_DEVFN int wv_scan_add(int v)
 	return v;
 }
 #endif
+/* sums within groups of eight lanes: lane 8 g + 7 leaves with v summed over lanes 8 g .. 8 g + 7 (three row_shr steps: a row_shr never leaves its row of 16, and a lane
+ * without a source adds 0); what the other lanes leave with is not defined -- read lanes 7, 15, 23, ... */
+#ifdef SSG_EMU
+SSG_DEVFN int wv_seg8_sum(int v) { for (int d = 1; d < 8; d <<= 1) v += wv_shfl(v, wv_lane() ^ d); return v; }
+#else
+SSG_DEVFN int wv_seg8_sum(int v)
+{
+	v += SSG_DPP(0, v, 0x111, 0xf); v += SSG_DPP(0, v, 0x112, 0xf); v += SSG_DPP(0, v, 0x114, 0xf);
+	return v;
+}
+#endif
+/* the same sums left in EVERY lane of the eight (two quad_perm butterflies, then row_half_mirror brings the other quad's sum), and the value of the lane
+ * eight further on or back in the row of 16 (row_ror:8) */
+#ifdef SSG_EMU
+SSG_DEVFN int wv_seg8_allsum(int v) { return wv_seg8_sum(v); }
+SSG_DEVFN int wv_xor8(int v) { return wv_shfl(v, wv_lane() ^ 8); }
+#else
+SSG_DEVFN int wv_seg8_allsum(int v)
+{
+	v += SSG_DPP(0, v, 0xb1 /* quad_perm:[1,0,3,2] */, 0xf); v += SSG_DPP(0, v, 0x4e /* quad_perm:[2,3,0,1] */, 0xf); v += SSG_DPP(0, v, 0x141 /* row_half_mirror */, 0xf);
+	return v;
+}
+SSG_DEVFN int wv_xor8(int v) { return SSG_DPP(0, v, 0x128 /* row_ror:8 */, 0xf); }
+#endif
 SSG_DEVFN int wv_last(int v) { return wv_get(v, 63); }
 /* dynamic work distribution: lane 0 takes the next index of a global queue, the wave shares it */
 SSG_DEVFN long wv_queue_pop(unsigned int *queue)

@@ -34,6 +34,13 @@ struct ssg_index {
 extern "C" int ssg_index_build_ktab(ssg_index *ix);
 extern "C" int ssg_seed_smem2(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, int cap,
                               ssg_intv_t *d_intv, int32_t *d_n, unsigned long long *n_extend, unsigned int max_ext, uint32_t *d_n_ext_read);
+/* (for the test entry ssg_dbg_smem_ext: d_paths = 4 zeroed device counters -- reads the wave kernel resumed in pass 1 at x > 0, resumed in pass 2, started again because the
+ * third pass was unfinished, took up in pass 1 at the read's start) */
+extern "C" int ssg_seed_smem2_paths(const ssg_index *idx, const ssg_mem_opt_t *opt, int n_reads, const uint8_t *d_seq, const int64_t *d_off, int max_len, int cap,
+                                    ssg_intv_t *d_intv, int32_t *d_n, unsigned long long *n_extend, unsigned int max_ext, unsigned int *d_paths);
+/* (for the test entry ssg_dbg_extend_coop: the forms of one extension per item, cd[t] = base | is_back << 2; device buffers, d_lean4 / d_coop4 of 4 n entries) */
+extern "C" int ssg_seed_dbg_extend_coop(const ssg_index *idx, int n, const ssg_intv_t *d_in, const uint8_t *d_cd, ssg_intv_t *d_lean, ssg_intv_t *d_coop,
+                                        ssg_intv_t *d_lean4, ssg_intv_t *d_coop4);
 extern "C" int ssg_sa_verify(const ssg_index *ix, int new_intv, const uint64_t *d_sa_new, long n_new);
 /* ssg_bgzf_frame.cpp: the launchers of the CRC-32 and framing kernels (k_bgzf_frame.h), queued on the calling thread's stream; device buffers */
 extern "C" int ssg_crc32_ranges_dev(const uint8_t *d_data, const uint64_t *d_cut, long n, uint32_t *d_crc);
