@@ -13,7 +13,7 @@ lib: speedseq_amd/libssgpu.so
 # Every object's prerequisites come from the compiler (-MMD): no hand-kept header lists, so no object can be stale against a shared
 # declaration (round 3 shipped variant libraries linked from objects of different ages).
 # the translation units hipcc compiles (sam_format.cpp is plain C++)
-UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_bam_select ssg_msw_replay ssg_bam ssg_coll
+UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_bam_select ssg_msw_replay ssg_bam ssg_coll ssg_b2f
 HIPOBJS = $(UNITS:%=$(CSRC)/%.o)
 HIPSRCS = $(UNITS:%=$(CSRC)/%.cpp)
 $(HIPOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp
@@ -53,8 +53,8 @@ tools/dbg/gather_probe: tools/dbg/gather_probe.cpp
 # the executables speedseq.config names (reference bin/speedseq.config:13-14)
 tools: bin/bwa bin/samblaster bin/sambamba bin/bamkit
 # the helpers `speedseq realign` runs through $$PYTHON (bin/pyrun), under the names speedseq.config gives them
-bin/bamkit: $(HOST)/bamkit_main.cpp $(HOST)/bamio.h
-	$(CXX) -O2 -std=c++17 $(HOST)/bamkit_main.cpp -o $@ -lz -lpthread
+bin/bamkit: $(HOST)/bamkit_main.cpp $(HOSTHDRS) speedseq_amd/libssgpu.so
+	$(CXX) -O2 -std=c++17 $(HOST)/bamkit_main.cpp -o $@ -Lspeedseq_amd -lssgpu -lz -lpthread -Wl,-rpath,'$$ORIGIN/../speedseq_amd'
 	for t in bamtofastq bamheadrg bamcleanheader bamlibs; do ln -sf bamkit bin/$$t.py; done
 bin/sambamba: $(HOST)/sambamba_main.cpp $(HOSTHDRS) speedseq_amd/libssgpu.so
 	$(CXX) -O2 -std=c++17 $(HOST)/sambamba_main.cpp -o $@ -Lspeedseq_amd -lssgpu -lz -lpthread -Wl,-rpath,'$$ORIGIN/../speedseq_amd'
@@ -67,7 +67,7 @@ oracle:
 	$(MAKE) -C oracle
 
 # host emulation of the HIP execution model: same kernel + host sources, CPU-side tests only
-emu: tests/emu/libssgpu_emu.so tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test
+emu: tests/emu/libssgpu_emu.so tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test
 tests/emu/fi_mt_test: tools/dbg/fi_mt_test.cpp $(HOST)/fast_inflate.h $(HOST)/fast_inflate_mt.h
 	$(CXX) -O2 -std=c++17 tools/dbg/fi_mt_test.cpp -o $@ -lz -lpthread
 tests/emu/scan_test: tools/dbg/scan_test.cpp $(HOST)/ranksplit.h $(HOST)/ranks.h $(HOST)/fastq.h
@@ -86,6 +86,8 @@ tests/emu/samblaster_emu: $(HOST)/samblaster_main.cpp $(HOSTHDRS) tests/emu/libs
 
 tests/emu/sambamba_emu: $(HOST)/sambamba_main.cpp $(HOSTHDRS) tests/emu/libssgpu_emu.so
 	$(CXX) -O2 -std=c++17 $(HOST)/sambamba_main.cpp -o $@ -Ltests/emu -lssgpu_emu -lz -lpthread -Wl,-rpath,'$$ORIGIN'
+tests/emu/bamkit_emu: $(HOST)/bamkit_main.cpp $(HOSTHDRS) tests/emu/libssgpu_emu.so
+	$(CXX) -O2 -std=c++17 $(HOST)/bamkit_main.cpp -o $@ -Ltests/emu -lssgpu_emu -lz -lpthread -Wl,-rpath,'$$ORIGIN'
 
 # memory safety of the inflate kernel's error paths: the emulated kernel under AddressSanitizer and UndefinedBehaviorSanitizer, fed the malformed members of
 # tests/test_bgzf_inflate.py and 2000 seeded mutations (tools/dbg/inflate_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
@@ -121,10 +123,20 @@ tests/emu/deflate_deep_fuzz: tools/dbg/deflate_deep_fuzz.cpp $(DEEPFUZZ_SRCS) te
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
 		tools/dbg/deflate_deep_fuzz.cpp $(DEEPFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
 
+# memory safety and exactness of bamtofastq on the device (k_b2f.h): the emulated kernels under AddressSanitizer and UndefinedBehaviorSanitizer on 3000 seeded
+# record streams -- truncated aux areas, sequences that leave their record, an l_qname of 0 and of 255 -- in one to three pushes each; every outcome is SSG_EIO or
+# the text of a plain C++ restatement (tools/dbg/b2f_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
+B2FFUZZ_SRCS = $(CSRC)/ssg_b2f.cpp $(CSRC)/ssg_bam_scan.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp
+fuzz-b2f: tests/emu/b2f_fuzz
+	tests/emu/b2f_fuzz
+tests/emu/b2f_fuzz: tools/dbg/b2f_fuzz.cpp $(B2FFUZZ_SRCS) tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
+		tools/dbg/b2f_fuzz.cpp $(B2FFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
+
 clean:
-	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz $(CSRC)/*.o
+	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba bin/bamkit tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz tests/emu/b2f_fuzz $(CSRC)/*.o
 	$(MAKE) -C oracle clean
-.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep
+.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep fuzz-b2f
 
 # A/B builds of the device library with other compile-time parameters (bench / tests: SSGPU_LIB=speedseq_amd/libssgpu_$(NAME).so); never the
 # default.  The units named in VUNITS (default: all) are compiled with VFLAGS into build/$(NAME)/; the others are the product build's

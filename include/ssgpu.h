@@ -29,6 +29,7 @@ extern "C" {
 #define SSG_EIO      (-5)
 #define SSG_EOVERFLOW (-75) /* an on-device capacity was exceeded; nothing was silently dropped */
 #define SSG_EALIGN   (-71)  /* ssg_recs_scan: a BGZF block that does not start at a record -- a property of the file, callers fall back on it */
+#define SSG_ERANGE   (-34)   /* ssg_b2f_push: more eligible records share one name hash than the pairing kernel takes -- a property of the input, callers fall back on it */
 #define SSG_EHIP     (-1000)
 
 const char *ssg_version(void);
@@ -529,6 +530,37 @@ int ssg_recs_release(ssg_recs_t *r, uint32_t chunk_id);
 int ssg_device_memory(uint64_t *free_bytes, uint64_t *total_bytes);
 void *ssg_host_alloc(size_t n);
 void ssg_host_free(void *p);
+
+/* ---- bamtofastq on the device (csrc/ssg_b2f.cpp, k_b2f.h): the pairs of a BAM stream as interleaved FASTQ text, byte for byte what `bamkit bamtofastq' writes ----
+ * The stream is fed chunk by chunk (ssg_recs_append_bgzf, then ssg_b2f_push), files in the order given, records in file order.  A record takes part when
+ * flag & 0x900 is clear, flag & 1 is set, no CIGAR operation is a hard clip and -- with a read group list -- its RG:Z is in the list (a record without one is
+ * not).  The aux area is walked with the types A c C s S i I f Z H B; any other type (`d' among them), a Z / H without its NUL or a B without its five bytes
+ * ends the walk, and the last RG:Z met before that counts.  Per name (the l_qname - 1 bytes, compared whole): nothing held -> the record is held; the held one
+ * has the same flag & 0x40 -> the record is dropped; otherwise the pair leaves, the half with 0x40 as /1, and nothing is held.  Pairs leave in the stream order
+ * of the record that completed them.  A half is `@name/1' or `@name/2', ` RG:Z:<rg>' when its own RG is not empty, `\n SEQ \n+\n QUAL \n'; flag & 0x10
+ * reverses both and complements SEQ (A/T C/G M/K R/Y V/B H/D); a first quality byte 0xff gives all `I'.  With `rename' the name is a running pair number from 0.
+ * ssg_b2f_create: rg[0 .. n_rg) is the read group list (n_rg == 0: no test); hash_bits in 0 .. 64 is how much of the 64-bit name hash groups the records
+ *   (callers pass 64; the result does not depend on it: names are compared in full).  The object lives on the store's device and must be freed before the store.
+ *   SSG_EINVAL for a NULL store, a NULL or empty id, n_rg < 0, hash_bits outside 0 .. 64.
+ * ssg_b2f_push: the chunk's records are found as ssg_recs_scan finds them (the same hints, `first', SSG_EIO / SSG_EALIGN / SSG_EINVAL and words, under this
+ *   entry's name) and paired with the halves carried from earlier pushes, which precede them in stream order.  The text of the pairs completed by this chunk's
+ *   records goes to out[0 .. *out_len); *n_rec: the records scanned; *n_pairs: the pairs written.
+ *     SSG_EIO        also a record with 32 + l_qname + 4 n_cigar + (l_seq + 1) / 2 + l_seq > block_size (its offset in ssg_last_error()): nothing is written.
+ *     SSG_EOVERFLOW  *out_len > out_cap; *out_len is set.  out_cap = 2 * (chunk length + carried bytes) + 64 always suffices: a half's text is
+ *                    name + 2 l_seq + 8 (+ 6 + rg) bytes, its record 36 + name + 1 + 4 n_cigar + (l_seq + 1) / 2 + l_seq (+ 4 + rg) bytes or more, and with
+ *                    `rename' the number's at most 20 digits stand in for the name against the 72 bytes that two fixed parts give.
+ *     SSG_ERANGE     more than SSG_B2F_RUN_MAX eligible records (carried ones included) share one hash of hash_bits bits.
+ *     SSG_ENOMEM     device memory.  SSG_EINVAL also while an order is declared (ssg_recs_reopen first).
+ *   On every failure the object, the store and the chunk are as before and the call may be repeated.  On success the chunk is released (ssg_recs_release), the
+ *   carry -- device memory that counts against the store's capacity -- holds exactly the halves still held, and the pair number has advanced by *n_pairs.
+ * ssg_b2f_waiting: the halves held and the bytes of their records (4 + block_size each). */
+#define SSG_B2F_RUN_MAX 256
+typedef struct ssg_b2f ssg_b2f_t;
+int  ssg_b2f_create(ssg_recs_t *r, const char *const *rg, int n_rg, int rename, int hash_bits, ssg_b2f_t **out);
+int  ssg_b2f_push(ssg_b2f_t *b, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first,
+                  uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *n_rec, uint64_t *n_pairs);
+int  ssg_b2f_waiting(ssg_b2f_t *b, uint64_t *n_halves, uint64_t *bytes);
+void ssg_b2f_free(ssg_b2f_t *b);
 
 #ifdef __cplusplus
 }

@@ -806,6 +806,66 @@ def recs_release(lib, recs, chunk_id):
     lib._chk(lib.l.ssg_recs_release(recs.h, C.c_uint32(chunk_id)))
 
 
+SSG_ERANGE = -34
+B2F_RUN_MAX = 256
+
+
+class B2f:
+    """bamtofastq on a record store (ssg_b2f_*): freed with the object or by close(), before its store."""
+
+    def __init__(self, lib, h, recs):
+        self.lib, self.h, self.recs = lib, h, recs   # (the store is kept alive: the carry counts against it)
+
+    def close(self):
+        if self.h is not None:
+            self.lib.l.ssg_b2f_free.argtypes = [C.c_void_p]
+            self.lib.l.ssg_b2f_free.restype = None
+            if self.recs.h is not None:
+                self.lib.l.ssg_b2f_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def b2f_create(lib, recs, rg=(), rename=False, hash_bits=64, raw=False):
+    """ssg_b2f_create: rg is the -r list (bytes or str ids; None stands for a NULL id).  raw=True returns (rc, B2f or None) instead of raising."""
+    ids = [None if x is None else (x if isinstance(x, bytes) else x.encode()) for x in rg]
+    arr = (C.c_char_p * max(len(ids), 1))(*ids)
+    h = C.c_void_p()
+    rc = lib.l.ssg_b2f_create(recs.h if recs is not None else None, arr if ids else None, C.c_int(len(ids)), C.c_int(1 if rename else 0), C.c_int(hash_bits), C.byref(h))
+    if raw:
+        return rc, (B2f(lib, h, recs) if rc == 0 else None)
+    lib._chk(rc)
+    return B2f(lib, h, recs)
+
+
+def b2f_push(lib, b, chunk_id, hint, first=0, out_cap=None):
+    """ssg_b2f_push: returns (rc, text, out_len, n_rec, n_pairs).  out_cap None: the documented bound 2 * (hint[-1] + carried bytes) + 64.  No return code
+    raises; text is the bytes written (b"" unless rc == 0), and the buffer behind them is seen to be untouched."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_hints = len(hint) - 1
+    if out_cap is None:
+        out_cap = 2 * ((int(hint[-1]) if len(hint) else 0) + b2f_waiting(lib, b)[1]) + 64
+    out = np.full(int(out_cap) + 8, 0xAB, dtype=np.uint8)
+    out_len, n_rec, n_pairs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = lib.l.ssg_b2f_push(b.h, C.c_uint32(chunk_id), _ptr(hint) if len(hint) else None, C.c_int64(n_hints), C.c_uint64(first), _ptr(out), C.c_uint64(int(out_cap)),
+                            C.byref(out_len), C.byref(n_rec), C.byref(n_pairs))
+    n = int(out_len.value)
+    if rc == 0:
+        assert n <= out_cap and (out[n:] == 0xAB).all()             # nothing behind the text
+        return rc, out[:n].tobytes(), n, int(n_rec.value), int(n_pairs.value)
+    assert (out == 0xAB).all()                                       # a failure writes nothing
+    return rc, b"", n, int(n_rec.value), int(n_pairs.value)
+
+
+def b2f_waiting(lib, b):
+    """ssg_b2f_waiting: (halves held, bytes of their records)."""
+    n, by = C.c_uint64(0), C.c_uint64(0)
+    lib._chk(lib.l.ssg_b2f_waiting(b.h, C.byref(n), C.byref(by)))
+    return int(n.value), int(by.value)
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

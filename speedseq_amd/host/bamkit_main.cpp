@@ -1,7 +1,9 @@
 /*
  * bamkit -- the four helpers `speedseq realign` drives (reference bin/speedseq:1886-1968), as one native executable that answers
- * to their names: bamtofastq.py, bamheadrg.py, bamcleanheader.py, bamlibs.py.  Host code only (no device
- * work): BAM decoding on the threaded BGZF reader of bamio.h, text out.
+ * to their names: bamtofastq.py, bamheadrg.py, bamcleanheader.py, bamlibs.py.  BAM decoding on the threaded BGZF reader of
+ * bamio.h, text out: host code, and the default.  bamtofastq alone has a device path as well (SSG_B2F_DEVICE=1, off by default): the files' BGZF members
+ * go through the device's record store batch by batch and libssgpu pairs the mates and writes the FASTQ text there (ssg_b2f_push, csrc/k_b2f.h), byte for
+ * byte what the host loop below writes; the other three helpers do no device work.
  *
  * Upstream these are the python scripts of hall-lab/bamkit (an empty submodule in the reference tree: src/bamkit), so this is a
  * restatement of their documented behaviour, anchored on how the reference script uses them:
@@ -34,9 +36,13 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <zlib.h>
+#include <time.h>
 #include "bamio.h"
 
 static void die(const std::string &m) { fprintf(stderr, "[bamkit] %s\n", m.c_str()); exit(1); }
+#include "devread.h"
+static double wall() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
+static bool dbg() { static int d = -1; if (d < 0) d = getenv("SSG_DEBUG") ? 1 : 0; return d != 0; }
 static int open_in(const char *p) { if (!strcmp(p, "/dev/stdin") || !strcmp(p, "-")) return 0; int fd = open(p, O_RDONLY); if (fd < 0) die(std::string("cannot open ") + p); return fd; }
 static std::vector<std::string> split(const std::string &s, char c)
 {
@@ -199,6 +205,69 @@ static void decode_read(const uint8_t *rec, int32_t len, half_t &h, std::string 
 	}
 }
 
+/* The device path (SSG_B2F_DEVICE=1): every file's whole members, from the one that holds the first record, go into the record store in batches of at most
+ * SSG_B2F_BATCH compressed bytes (default 256 MB), 256 MB of records and 4096 members; ssg_b2f_push pairs a batch's records with the halves carried from the
+ * batches -- and files -- before it, writes the text of the pairs they complete and releases the batch.  One ssg_b2f_t across all files: the carry and -n's
+ * counter run on.  false with `why' while nothing is written: the host loop takes over (no device, a pipe, blocks that split records, the store, a name hash
+ * shared by more records than the pairing kernel takes); once output has begun a failure ends the command.  A malformed record ends it on either path. */
+static bool tofastq_device(const std::vector<const char*> &files, const std::set<std::string> &want, bool rename, std::string &why)
+{
+	std::vector<int> fds;
+	struct closer_t { std::vector<int> &v; ~closer_t() { for (int fd : v) if (fd > 0) close(fd); } } closer = { fds };
+	for (const char *path : files) { fds.push_back(open_in(path)); if (!dev_read_ready(fds.back(), why)) return false; }
+	recs_holder_t S;
+	struct b2f_holder_t { ssg_b2f_t *b; ~b2f_holder_t() { if (b) ssg_b2f_free(b); } } B = { 0 };   /* (behind the store: freed before it) */
+	const char *const pool = getenv("SSG_B2F_POOL"), *const batch_env = getenv("SSG_B2F_BATCH");
+	const uint64_t batch = batch_env && *batch_env && strtoull(batch_env, 0, 10) > 0 ? strtoull(batch_env, 0, 10) : (uint64_t)256 << 20;
+	std::vector<const char*> ids; for (const std::string &g : want) ids.push_back(g.c_str());
+	if (ssg_set_device(0) || ssg_recs_create(pool && *pool ? strtoull(pool, 0, 10) : ~(uint64_t)0 >> 1, &S.r) ||
+	    ssg_b2f_create(S.r, ids.empty() ? 0 : ids.data(), (int)ids.size(), rename ? 1 : 0, 64, &B.b)) { why = ssg_last_error(); return false; }
+	struct pinned_t { uint8_t *p; uint64_t cap; ~pinned_t() { if (p) ssg_host_free(p); } } O = { 0, 0 };
+	const int threads = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+	uint64_t n_scanned = 0, n_pairs_all = 0, n_members = 0; int n_batches = 0; bool begun = false;
+	std::vector<uint64_t> out_off; std::vector<int32_t> status;
+	const double t0 = wall();
+	if (getenv("SSG_PROF")) { ssg_prof_reset(); ssg_prof_enable(1); }   /* the device time of every kernel (HIP events around each launch), one line each at the end */
+	auto fail = [&](const std::string &m) -> bool { if (begun) die("bamtofastq: " + m + " after output had begun (SSG_B2F_DEVICE=0 reads the files on the host)"); why = m; return false; };
+	for (size_t f = 0; f < files.size(); ++f) {
+		uint64_t v0;
+		{	bgzf_in_t in(fds[f], threads); bam_hdr_t hd;
+			if (!hdr_read(in, hd)) die(std::string(files[f]) + ": not a BAM file");
+			v0 = in.tell(); }
+		raw_members_t rd; rd.start(fds[f], files[f], v0 >> 16);
+		uint64_t first = v0 & 0xffff;
+		for (;;) {
+			rd.limit = rd.end_addr() + batch;   /* (no member that begins behind this many compressed bytes; the first one always) */
+			if (!rd.next((uint64_t)256 << 20, 4096)) break;
+			const size_t nm = rd.n(); uint32_t cid = 0;
+			out_off.resize(nm + 1); status.assign(nm, 0);
+			int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
+			if (rc == SSG_EIO) die(dev_inflate_failed("bamtofastq", rd, status));
+			if (rc) return fail(ssg_last_error());
+			if (first > out_off[nm]) { if (out_off[nm] == 0) { first = 0; (void)ssg_recs_release(S.r, cid); continue; } die(std::string(files[f]) + ": truncated BAM header"); }
+			uint64_t held = 0, held_bytes = 0, out_len = 0, n_rec = 0, n_pairs = 0;
+			(void)ssg_b2f_waiting(B.b, &held, &held_bytes);
+			const uint64_t cap = 2 * (out_off[nm] + held_bytes) + 64;   /* always enough (include/ssgpu.h) */
+			if (cap > O.cap) { if (O.p) ssg_host_free(O.p); O.cap = cap + cap / 4; O.p = (uint8_t*)ssg_host_alloc((size_t)O.cap); if (!O.p) { O.cap = 0; return fail("no page-locked memory for the text"); } }
+			rc = ssg_b2f_push(B.b, cid, out_off.data(), (int64_t)nm, first, O.p, O.cap, &out_len, &n_rec, &n_pairs);
+			if (rc == SSG_EIO && strstr(ssg_last_error(), "exceeds block_size")) die(std::string(files[f]) + ": " + (ssg_last_error() + strlen("ssg_b2f_push: ")));
+			if (rc) return fail(rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_b2f_push: ")) : std::string(ssg_last_error()));
+			if (out_len) { io_write_all(1, O.p, (size_t)out_len); begun = true; }
+			first = 0; n_scanned += n_rec; n_pairs_all += n_pairs; n_members += nm; ++n_batches;
+		}
+	}
+	uint64_t left = 0; (void)ssg_b2f_waiting(B.b, &left, 0);
+	if (left) fprintf(stderr, "[bamtofastq] %zu reads without their mate in the input were left out\n", (size_t)left);
+	if (getenv("SSG_PROF")) {
+		const char *nm[64]; double ms[64]; long cnt[64];
+		const int n = std::min(ssg_prof_get(64, nm, ms, cnt), 64);
+		for (int i = 0; i < n; ++i) fprintf(stderr, "[bamkit] bamtofastq: kernel %-24s %9.1f ms in %ld launches\n", nm[i], ms[i], cnt[i]);
+	}
+	if (dbg()) fprintf(stderr, "[bamkit] bamtofastq: on the device: %zu file%s, %llu members, %llu records scanned, %llu pairs, %llu halves left, %d batches, %.2f s\n", files.size(), files.size() == 1 ? "" : "s",
+	                   (unsigned long long)n_members, (unsigned long long)n_scanned, (unsigned long long)n_pairs_all, (unsigned long long)left, n_batches, wall() - t0);
+	return true;
+}
+
 static int main_tofastq(int argc, char **argv)
 {
 	std::set<std::string> want; bool rename = false; std::vector<const char*> files;
@@ -209,6 +278,12 @@ static int main_tofastq(int argc, char **argv)
 		else files.push_back(argv[i]);
 	}
 	if (files.empty()) { fprintf(stderr, "usage: bamtofastq.py [-r id[,id...]] [-n] <in.bam> [in2.bam ...] > interleaved.fq\n"); return 1; }
+	const char *const on = getenv("SSG_B2F_DEVICE");
+	if (on && !strcmp(on, "1")) {
+		std::string why;
+		if (tofastq_device(files, want, rename, why)) return 0;
+		if (dbg()) fprintf(stderr, "[bamkit] bamtofastq: on the host: %s\n", why.c_str());
+	}
 	const int threads = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
 	std::unordered_map<std::string, half_t> waiting;
 	std::string out; out.reserve((size_t)1 << 22);
