@@ -562,6 +562,46 @@ int  ssg_b2f_push(ssg_b2f_t *b, uint32_t chunk_id, const uint64_t *hint, int64_t
 int  ssg_b2f_waiting(ssg_b2f_t *b, uint64_t *n_halves, uint64_t *bytes);
 void ssg_b2f_free(ssg_b2f_t *b);
 
+/* ---- coverage on the device (csrc/ssg_depth.cpp, k_depth.h): per-position counters of a BAM stream, their sums over regions and windows, and the lines of
+ * `samtools depth' (samtools 1.3.1 bam2depth.c, bedcov.c: the numbers are theirs, without the 8000 / 64000 pile caps) ----
+ * The stream is fed chunk by chunk (ssg_recs_append_bgzf, then ssg_depth_push).  A record takes part when the filter program leaves 1 on it (the programs and
+ * fields of ssg_recs_select), its tid >= 0 and its n_cigar > 0.  Per reference position two 32-bit counters: every position of an M, =, X, D or N operation
+ * adds 1 to `span'; every position of an M, = or X operation whose base passes the quality test adds 1 to `cov'; S, I, H and P add nothing (S and I advance the
+ * query).  A base passes when its quality byte, taken unsigned, is >= min_baseq (0xff passes; min_baseq == 0 passes everything); a base beyond l_seq has no byte
+ * and passes, so a record with l_seq == 0 passes on every base.  Positions are 0-based reference positions everywhere.
+ * ssg_depth_create: the object lives on the store's device and must be freed before the store.  SSG_EINVAL for what ssg_recs_select refuses of a program, in the
+ *   same words under this entry's name, and for min_baseq outside 0 .. 255.
+ * ssg_depth_begin: opens the span [beg, end) of contig tid, 0 <= beg < end <= 2^31 - 1; its counters are device memory, zeroed there.  SSG_ENOMEM with the
+ *   object unchanged when they do not fit; SSG_EINVAL while a span is open.
+ * ssg_depth_push: the chunk's records are found as ssg_recs_scan finds them (the same hints, `first', SSG_EIO / SSG_EALIGN / SSG_EINVAL and words, under this
+ *   entry's name); every passing record with tid == the span's, pos < end and rec.end > beg (rec.end as in ssg_bam_ent_t) is added, clipped to the span.
+ *   *n_rec: the records scanned; *n_used: the records added; *n_later: the passing records that matter to a later span (a greater tid, or the same tid and
+ *   rec.end > the span's end: the caller keeps the chunk and pushes it again into the next span); *descents: the records whose (tid, pos) lies below their
+ *   predecessor's in the chunk (a file that is not coordinate-sorted); *n_behind (may be NULL): the records, passing or not, that begin behind the span
+ *   (tid < 0, a greater tid, or pos >= end): once there is one, no later chunk of a sorted stream adds to this span.  With min_baseq > 0, SSG_EIO also for a record to be added with 32 + l_qname +
+ *   4 n_cigar + (l_seq + 1) / 2 + l_seq > block_size (its offset in ssg_last_error()).  The chunk is not released and the store is unchanged by every outcome;
+ *   on every failure the counters are as before the call.  SSG_EINVAL also without an open span, after ssg_depth_finish, and while an order is declared.
+ * ssg_depth_finish: the counters become final; ssg_depth_push is refused until the next ssg_depth_begin.  The three calls below need a finished span.
+ * ssg_depth_get: the counters of positions [p0, p1) of the span to host arrays (tests, measuring).
+ * ssg_depth_sums: reg[] holds n_reg pairs (beg, end) inside the span, in any order, overlapping or not; per pair out holds 2 + n_thr values: the sum of span,
+ *   the sum of cov, and per threshold (at most 8) the positions with cov >= thr[k].  n_reg == 0 is allowed; SSG_EINVAL for a pair outside the span or with
+ *   beg >= end.
+ * ssg_depth_text: the lines of positions [p0, p1), ascending, as `name \t position + 1 \t cov \n': with all == 0 those with span > 0, otherwise every one.
+ *   The text is written on the device and copied out once; *len: its bytes.  SSG_EOVERFLOW with *len set and nothing written when cap is too small; cap == 0
+ *   with out == NULL is the sizing form and returns 0.
+ * ssg_depth_end: closes the span and frees its memory.  Results do not depend on SSG_DEPTH_TILE (the positions of the accumulating kernel's LDS tile, 0 .. 8000,
+ *   0: every add goes to global memory). */
+typedef struct ssg_depth ssg_depth_t;
+int  ssg_depth_create(ssg_recs_t *r, const ssg_bam_fop_t *prog, int n_prog, int min_baseq, ssg_depth_t **out);
+int  ssg_depth_begin(ssg_depth_t *d, int32_t tid, int64_t beg, int64_t end);
+int  ssg_depth_push(ssg_depth_t *d, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t *n_rec, uint64_t *n_used, uint64_t *n_later, uint64_t *descents, uint64_t *n_behind);
+int  ssg_depth_finish(ssg_depth_t *d);
+int  ssg_depth_get(ssg_depth_t *d, int64_t p0, int64_t p1, uint32_t *span_out, uint32_t *cov_out);
+int  ssg_depth_sums(ssg_depth_t *d, const int64_t *reg, int64_t n_reg, const uint32_t *thr, int n_thr, uint64_t *out);
+int  ssg_depth_text(ssg_depth_t *d, const char *name, int64_t p0, int64_t p1, int all, uint8_t *out, uint64_t cap, uint64_t *len);
+int  ssg_depth_end(ssg_depth_t *d);
+void ssg_depth_free(ssg_depth_t *d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -866,6 +866,98 @@ def b2f_waiting(lib, b):
     return int(n.value), int(by.value)
 
 
+DEPTH_THR_MAX = 8
+
+
+class Depth:
+    """coverage on a record store (ssg_depth_*): freed with the object or by close(), before its store."""
+
+    def __init__(self, lib, h, recs):
+        self.lib, self.h, self.recs = lib, h, recs
+
+    def close(self):
+        if self.h is not None:
+            self.lib.l.ssg_depth_free.argtypes = [C.c_void_p]
+            self.lib.l.ssg_depth_free.restype = None
+            if self.recs.h is not None:
+                self.lib.l.ssg_depth_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def depth_create(lib, recs, prog=(), min_baseq=0):
+    """ssg_depth_create: prog as recs_select takes it.  Returns (rc, Depth or None); no return code raises."""
+    fop = np.array([(op, arg, 0, value) for op, arg, value in prog], dtype=BAM_FOP_DT)
+    h = C.c_void_p()
+    rc = lib.l.ssg_depth_create(recs.h if recs is not None else None, _ptr(fop) if len(fop) else None, C.c_int(len(fop)), C.c_int(min_baseq), C.byref(h))
+    return rc, (Depth(lib, h, recs) if rc == 0 else None)
+
+
+def depth_begin(lib, d, tid, beg, end):
+    """ssg_depth_begin: opens the span [beg, end) of contig tid; the return code."""
+    return lib.l.ssg_depth_begin(d.h, C.c_int32(tid), C.c_int64(beg), C.c_int64(end))
+
+
+def depth_push(lib, d, chunk_id, hint, first=0):
+    """ssg_depth_push: returns (rc, n_rec, n_used, n_later, descents, n_behind); no return code raises."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_hints = len(hint) - 1
+    v = [C.c_uint64(0) for _ in range(5)]
+    rc = lib.l.ssg_depth_push(d.h, C.c_uint32(chunk_id), _ptr(hint) if len(hint) else None, C.c_int64(n_hints), C.c_uint64(first), *[C.byref(x) for x in v])
+    return (rc,) + tuple(int(x.value) for x in v)
+
+
+def depth_finish(lib, d):
+    return lib.l.ssg_depth_finish(d.h)
+
+
+def depth_end(lib, d):
+    return lib.l.ssg_depth_end(d.h)
+
+
+def depth_get(lib, d, p0, p1):
+    """ssg_depth_get: (rc, span, cov) of the reference positions [p0, p1), uint32 arrays."""
+    n = max(p1 - p0, 0)
+    span = np.full(n + 1, 0xABABABAB, dtype=np.uint32)
+    cov = np.full(n + 1, 0xABABABAB, dtype=np.uint32)
+    rc = lib.l.ssg_depth_get(d.h, C.c_int64(p0), C.c_int64(p1), _ptr(span), _ptr(cov))
+    assert int(span[n]) == 0xABABABAB and int(cov[n]) == 0xABABABAB           # nothing behind the positions
+    return rc, span[:n], cov[:n]
+
+
+def depth_sums(lib, d, pairs, thr=()):
+    """ssg_depth_sums: pairs of (beg, end) reference positions; returns (rc, out) with out[k] = (sum span, sum cov, positions with cov >= thr[0], ...) as uint64."""
+    reg = np.ascontiguousarray(np.array(pairs, dtype=np.int64).reshape(-1, 2))
+    t = np.ascontiguousarray(thr, dtype=np.uint32)
+    out = np.full((len(reg), 2 + len(t)), 0xABABABABABABABAB, dtype=np.uint64)
+    rc = lib.l.ssg_depth_sums(d.h, _ptr(reg) if len(reg) else None, C.c_int64(len(reg)), _ptr(t) if len(t) else None, C.c_int(len(t)), _ptr(out) if out.size else None)
+    return rc, out
+
+
+def depth_text(lib, d, name, p0, p1, all_positions=False, cap=None):
+    """ssg_depth_text: returns (rc, text, len).  cap None: the sizing form first, then a buffer of exactly that size; cap 0 alone is the sizing form (text b"").
+    The buffer behind the text is seen to be untouched, and on a failure the whole of it."""
+    name = name if isinstance(name, bytes) else name.encode()
+    n = C.c_uint64(0)
+    if cap is None:
+        rc = lib.l.ssg_depth_text(d.h, name, C.c_int64(p0), C.c_int64(p1), C.c_int(1 if all_positions else 0), None, C.c_uint64(0), C.byref(n))
+        if rc:
+            return rc, b"", int(n.value)
+        cap = int(n.value)
+    if cap == 0:
+        rc = lib.l.ssg_depth_text(d.h, name, C.c_int64(p0), C.c_int64(p1), C.c_int(1 if all_positions else 0), None, C.c_uint64(0), C.byref(n))
+        return rc, b"", int(n.value)
+    out = np.full(int(cap) + 8, 0xAB, dtype=np.uint8)
+    rc = lib.l.ssg_depth_text(d.h, name, C.c_int64(p0), C.c_int64(p1), C.c_int(1 if all_positions else 0), _ptr(out), C.c_uint64(int(cap)), C.byref(n))
+    if rc == 0:
+        assert int(n.value) <= cap and (out[int(n.value):] == 0xAB).all()
+        return rc, out[:int(n.value)].tobytes(), int(n.value)
+    assert (out == 0xAB).all()
+    return rc, b"", int(n.value)
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

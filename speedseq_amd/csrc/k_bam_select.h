@@ -69,6 +69,7 @@ SSG_DEVFN bool sel_keep(const uint8_t *chunk, uint64_t off, int32_t end, bool ac
 	return act && in && (stk & 1u);
 }
 
+#ifndef SSG_SEL_DECISION_ONLY   /* (k_depth.h takes sel_keep and leaves the kernel to its own translation unit) */
 __global__ void __launch_bounds__(256) ssg_k_bam_select(const uint8_t *chunk, const uint64_t *loc, const uint64_t *key, const ssg_bam_ent_t *ent, int64_t n_rec,
                                                         const ssg_bam_region_t *reg, int32_t n_reg, int32_t n_steps, const ssg_bam_fop_t *prog, int32_t n_prog,
                                                         uint32_t *cnt, const uint64_t *base, uint64_t n_out, uint64_t *out_loc, uint64_t *out_key, ssg_bam_ent_t *out_ent)
@@ -94,4 +95,5 @@ __global__ void __launch_bounds__(256) ssg_k_bam_select(const uint8_t *chunk, co
 		if (w < n_out) { out_loc[w] = l; out_key[w] = key[i]; out_ent[w] = e; }
 	}
 }
+#endif
 #endif

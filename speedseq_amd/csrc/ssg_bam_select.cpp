@@ -26,21 +26,7 @@ static int select_args_ok(const ssg_bam_region_t *reg, int64_t n_reg, const ssg_
 			return SSG_EINVAL;
 		}
 	}
-	if (n_prog < 0 || (n_prog > 0 && !prog)) { ssg_err_msg = who + "n_prog < 0, or no prog[]"; return SSG_EINVAL; }
-	if (n_prog > SSG_FOP_MAX) { ssg_err_msg = who + "a filter program of " + std::to_string(n_prog) + " operations, at most " + std::to_string(SSG_FOP_MAX) + " are taken"; return SSG_EINVAL; }
-	int depth = 0;
-	for (int pc = 0; pc < n_prog; ++pc) {
-		const ssg_bam_fop_t &f = prog[pc];
-		if (f.op == SSG_FOP_AND || f.op == SSG_FOP_OR) { if (depth < 2) { ssg_err_msg = who + "operation " + std::to_string(pc) + " underflows the stack"; return SSG_EINVAL; } --depth; }
-		else if (f.op == SSG_FOP_NOT) { if (depth < 1) { ssg_err_msg = who + "operation " + std::to_string(pc) + " underflows the stack"; return SSG_EINVAL; } }
-		else if (f.op == SSG_FOP_FLAG) ++depth;
-		else if (f.op >= SSG_FOP_EQ && f.op <= SSG_FOP_GE) {
-			if (f.arg > SSG_FLD_FLAG) { ssg_err_msg = who + "operation " + std::to_string(pc) + " compares the unknown field " + std::to_string(f.arg); return SSG_EINVAL; }
-			++depth;
-		} else { ssg_err_msg = who + "operation " + std::to_string(pc) + " is the unknown operation " + std::to_string(f.op); return SSG_EINVAL; }
-	}
-	if (n_prog > 0 && depth != 1) { ssg_err_msg = who + "the filter program leaves " + std::to_string(depth) + " values, not exactly one"; return SSG_EINVAL; }
-	return 0;
+	return recs_prog_ok(who, prog, n_prog);
 }
 
 extern "C" {

@@ -32,6 +32,26 @@ static inline int recs_usable(const ssg_recs *r, const char *who)
 	if (r->dev != ssg_cur_dev) { ssg_err_msg = std::string(who) + ": the record store lives on device " + std::to_string(r->dev) + ", the calling thread drives device " + std::to_string(ssg_cur_dev); return SSG_EINVAL; }
 	return 0;
 }
+/* what the kernels that run a filter program rely on (sel_keep, k_bam_select.h): every operation is known, finds its operands on the stack, and the program never
+ * holds more than 64 values and leaves exactly one.  `who': the entry's name with ": " behind it */
+static inline int recs_prog_ok(const std::string &who, const ssg_bam_fop_t *prog, int n_prog)
+{
+	if (n_prog < 0 || (n_prog > 0 && !prog)) { ssg_err_msg = who + "n_prog < 0, or no prog[]"; return SSG_EINVAL; }
+	if (n_prog > SSG_FOP_MAX) { ssg_err_msg = who + "a filter program of " + std::to_string(n_prog) + " operations, at most " + std::to_string(SSG_FOP_MAX) + " are taken"; return SSG_EINVAL; }
+	int depth = 0;
+	for (int pc = 0; pc < n_prog; ++pc) {
+		const ssg_bam_fop_t &f = prog[pc];
+		if (f.op == SSG_FOP_AND || f.op == SSG_FOP_OR) { if (depth < 2) { ssg_err_msg = who + "operation " + std::to_string(pc) + " underflows the stack"; return SSG_EINVAL; } --depth; }
+		else if (f.op == SSG_FOP_NOT) { if (depth < 1) { ssg_err_msg = who + "operation " + std::to_string(pc) + " underflows the stack"; return SSG_EINVAL; } }
+		else if (f.op == SSG_FOP_FLAG) ++depth;
+		else if (f.op >= SSG_FOP_EQ && f.op <= SSG_FOP_GE) {
+			if (f.arg > SSG_FLD_FLAG) { ssg_err_msg = who + "operation " + std::to_string(pc) + " compares the unknown field " + std::to_string(f.arg); return SSG_EINVAL; }
+			++depth;
+		} else { ssg_err_msg = who + "operation " + std::to_string(pc) + " is the unknown operation " + std::to_string(f.op); return SSG_EINVAL; }
+	}
+	if (n_prog > 0 && depth != 1) { ssg_err_msg = who + "the filter program leaves " + std::to_string(depth) + " values, not exactly one"; return SSG_EINVAL; }
+	return 0;
+}
 /* ssg_recs_scan with loc, key and ent of the chunk's records left in device memory (ssg_bam_scan.cpp): every check, state and message of the scan, the messages
  * under the caller's name `who'.  `arrays': the caller has a place for records (without one, a chunk that holds records is SSG_EINVAL, as the scan says it).
  * o.loc / o.key / o.ent hold *n_rec elements when 0 is returned and *n_rec > 0. */

@@ -7,6 +7,7 @@
  *   sort -t N -m XG --tmpdir=DIR -o out <in>  coordinate sort                         bin/speedseq:427,431,434,1950
  *   index <in.bam>                            <in.bam>.bai                            bin/speedseq:486-494
  *   merge -t N out.bam in1.bam in2.bam ...    merge of coordinate-sorted files        bin/speedseq:2002-2004
+ *   depth base|region|window ... <in.bam>     coverage per base, BED line or window, counted on the device (what `speedseq sv -d' and `var' ask of a BAM)
  * Formats and orders follow the in-tree samtools / htslib 1.3.1 (bamio.h cites the lines).  Text parsing, BGZF (de)compression
  * and the gather of sorted records run on host threads; the coordinate sort itself -- a stable sort of the 64-bit keys
  * tid<<32 | (pos+1)<<1 | reverse -- runs on the MI355X through libssgpu (ssg_sort_u64_perm), chunk by chunk when the input
@@ -2041,9 +2042,188 @@ static int cmd_merge(int argc, char **argv)
 	return 0;
 }
 
+/* ---------------- depth: per-base, region and window coverage, counted on the device (ssg_depth_*, include/ssgpu.h) ----------------
+ * What is read: as `view' -- the whole file, or with regions / -L the chunks the .bai gives for them -- in batches of whole members that go into the record store.
+ * The targets (the merged regions, or every contig in header order) are cut into spans of at most SSG_DEPTH_SPAN positions, neighbouring small targets of a
+ * contig sharing one.  The spans are taken in order: the batches still held are pushed into the span, then batches are loaded and pushed until one holds a record
+ * that begins behind the span (n_behind > 0: the file is sorted, no later batch adds to it); a batch with n_later > 0 is held for the next span, the others are
+ * released.  A window or BED line that several spans share is summed over them on the host.  There is no host path. */
+struct depth_item_t { int32_t tid; int64_t beg, end, pbeg, pend; uint64_t v[2 + 8]; };   /* what is summed (inside its contig) and what is printed */
+struct depth_batch_t { uint32_t cid; std::vector<uint64_t> hint; uint64_t first; };
+static int cmd_depth(int argc, char **argv)
+{
+	const char *const usage = "usage: sambamba depth base|region|window [-t N] [-F FILTER] [-q MINBASEQ] [-a] [-T N ...] [-w SIZE] [-L BED] [-o FILE] <in.bam> [region ...]";
+	if (argc < 1) die(usage);
+	const std::string mode = argv[0];
+	if (mode != "base" && mode != "region" && mode != "window") die(std::string("depth: unknown mode `") + mode + "' (base, region, window)");
+	const char *expr = "not (unmapped or secondary_alignment or failed_quality_control or duplicate)", *out_path = 0, *bed = 0, *in = 0;
+	int min_baseq = 0; bool all = false; int64_t wsize = 0; std::vector<uint32_t> thr; std::vector<std::string> region;
+	for (int i = 1; i < argc; ++i) {
+		const char *a = argv[i];
+		if (!strcmp(a, "-t") && i + 1 < argc) ++i;   /* (the work is the device's) */
+		else if (!strcmp(a, "-F") && i + 1 < argc) expr = argv[++i];
+		else if (!strcmp(a, "-q") && i + 1 < argc) { int64_t q; if (!view_number(argv[++i], q) || q > 255) die("depth: -q takes a number in 0 .. 255"); min_baseq = (int)q; }
+		else if (!strcmp(a, "-a") && mode == "base") all = true;
+		else if (!strcmp(a, "-T") && i + 1 < argc && mode != "base") { int64_t t; if (!view_number(argv[++i], t) || t > 0xffffffffll) die("depth: -T takes a number below 2^32"); if (thr.size() == 8) die("depth: at most 8 -T"); thr.push_back((uint32_t)t); }
+		else if (!strcmp(a, "-w") && i + 1 < argc && mode == "window") { if (!view_number(argv[++i], wsize) || wsize < 1) die("depth: -w takes a window size of at least 1"); }
+		else if (!strcmp(a, "-L") && i + 1 < argc) bed = argv[++i];
+		else if (!strcmp(a, "-o") && i + 1 < argc) out_path = argv[++i];
+		else if (a[0] == '-' && a[1]) die(std::string("depth ") + mode + ": unsupported option " + a);
+		else if (!in) in = a;
+		else region.push_back(a);
+	}
+	if (!in) die(usage);
+	if (mode == "window" && wsize < 1) die("depth window: -w SIZE is required");
+	if (mode == "region" && !bed) die("depth region: -L BED is required");
+	if (mode == "region" && !region.empty()) die("depth region: the regions are the lines of -L");
+	view_filter_t filter; filter.compile(expr);
+	const int fd = open_in(in);
+	std::string why;
+	if (!dev_read_ready(fd, why)) die("depth: " + why + " (the coverage is counted on the device; there is no host path)");
+	bam_hdr_t h;
+	uint64_t v0 = 0;
+	{ bgzf_in_t bi(fd, 1); if (!hdr_read(bi, h)) die("depth: not a BAM file"); v0 = bi.tell(); }
+	/* the targets: merged regions inside their contigs, or every contig */
+	std::vector<ssg_bam_region_t> reg, lines;
+	for (const std::string &r : region) view_region_add(h, r, reg);
+	if (bed) { view_bed_read(h, bed, lines); reg.insert(reg.end(), lines.begin(), lines.end()); }
+	const bool with_regions = bed || !region.empty();
+	view_regions_merge(reg);
+	if (!with_regions) for (size_t t = 0; t < h.names.size(); ++t) { ssg_bam_region_t r; r.tid = (int32_t)t; r.beg = 0; r.end = h.lens[t]; reg.push_back(r); }
+	std::vector<ssg_bam_region_t> targets;
+	for (ssg_bam_region_t r : reg) { r.end = std::min(r.end, h.lens[(size_t)r.tid]); if (r.beg < r.end) targets.push_back(r); }
+	/* what region and window print, in their order */
+	std::vector<depth_item_t> items;
+	auto item_add = [&](int32_t tid, int64_t b, int64_t e) { depth_item_t it; memset(&it, 0, sizeof(it)); it.tid = tid; it.pbeg = b; it.pend = e; it.beg = b; it.end = std::min<int64_t>(e, h.lens[(size_t)tid]); items.push_back(it); };
+	if (mode == "region") for (const ssg_bam_region_t &l : lines) item_add(l.tid, l.beg, l.end);
+	if (mode == "window") for (const ssg_bam_region_t &t : targets) for (int64_t b = t.beg; b < t.end; b += wsize) item_add(t.tid, b, std::min<int64_t>(b + wsize, t.end));
+	std::vector<std::vector<size_t> > items_of(h.names.size());
+	for (size_t k = 0; k < items.size(); ++k) items_of[(size_t)items[k].tid].push_back(k);
+	/* the spans */
+	const char *const se = getenv("SSG_DEPTH_SPAN");
+	const int64_t SPAN = std::max<int64_t>(1, std::min<int64_t>(se && *se ? strtoll(se, 0, 10) : (int64_t)1 << 26, (int64_t)1 << 28));
+	struct span_t { int32_t tid; int64_t beg, end; std::vector<ssg_bam_region_t> parts; };
+	std::vector<span_t> spans;
+	for (const ssg_bam_region_t &t : targets)
+		for (int64_t b = t.beg; b < t.end; b += SPAN) {
+			ssg_bam_region_t p; p.tid = t.tid; p.beg = (int32_t)b; p.end = (int32_t)std::min<int64_t>(b + SPAN, t.end);
+			if (spans.empty() || spans.back().tid != p.tid || p.end - spans.back().beg > SPAN) { span_t s; s.tid = p.tid; s.beg = p.beg; spans.push_back(s); }
+			spans.back().end = p.end; spans.back().parts.push_back(p);
+		}
+	/* what to read */
+	std::vector<view_chunk_t> chunks;
+	if (with_regions) {
+		const std::string bai = std::string(in) + ".bai";
+		struct stat sb, si;
+		if (stat(bai.c_str(), &si) != 0) die("depth: regions need the index " + bai + ", which is not there (sambamba index)");
+		if (fstat(fd, &sb) == 0 && si.st_mtime < sb.st_mtime) die("depth: the index " + bai + " is older than " + in + " (sambamba index)");
+		bai_reader_t idx; std::string err;
+		if (!idx.load(bai.c_str(), err)) die("depth: the index " + bai + ": " + err);
+		if (idx.refs.size() != h.names.size()) die("depth: the index " + bai + " has " + std::to_string(idx.refs.size()) + " references, the header of " + in + " has " + std::to_string(h.names.size()));
+		for (const ssg_bam_region_t &r : targets) idx.query(r.tid, r.beg, r.end, chunks);
+		bai_chunks_merge(chunks);
+	} else { view_chunk_t c; c.u = v0; c.v = ~(uint64_t)0; chunks.push_back(c); }
+	int out_fd = 1;
+	if (out_path) { out_fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666); if (out_fd < 0) die(std::string("cannot write ") + out_path + ": " + strerror(errno)); g_partial_out = out_path; }
+	recs_holder_t S;
+	struct depth_holder_t { ssg_depth_t *d; ~depth_holder_t() { if (d) ssg_depth_free(d); } } D = { 0 };   /* (freed before the store: declared behind it) */
+	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) die(std::string("depth: ") + ssg_last_error());
+	if (ssg_depth_create(S.r, filter.prog.data(), (int)filter.prog.size(), min_baseq, &D.d)) die(std::string("depth: ") + ssg_last_error());
+	dev_prof_begin();
+	/* the reader: the next batch of the chunk list, as view_device cuts them */
+	raw_members_t rd; size_t ci = 0; bool chunk_open = false; uint64_t first = 0; std::vector<int32_t> status; std::vector<uint64_t> out_off;
+	auto load = [&](depth_batch_t &B) -> bool {
+		for (;;) {
+			if (!chunk_open) {
+				if (ci >= chunks.size()) return false;
+				const view_chunk_t &c = chunks[ci];
+				rd.start(fd, in, c.u >> 16); rd.limit = c.v == ~(uint64_t)0 ? c.v : (c.v >> 16) + ((c.v & 0xffff) ? 1 : 0);
+				first = c.u & 0xffff; chunk_open = true;
+			}
+			if (!rd.next((uint64_t)64 << 20, 1024)) { chunk_open = false; ++ci; continue; }
+			const view_chunk_t &c = chunks[ci];
+			const size_t nm = rd.n();
+			out_off.resize(nm + 1); status.assign(nm, 0);
+			const int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &B.cid, out_off.data(), status.data());
+			if (rc == SSG_EIO) die(dev_inflate_failed("depth", rd, status));
+			if (rc) die(std::string("depth: ") + ssg_last_error());
+			B.hint = out_off;
+			if ((c.v & 0xffff) && rd.addr + rd.moff[nm - 1] == c.v >> 16) {   /* the chunk's last member: the stream ends at v */
+				if (out_off[nm - 1] + (c.v & 0xffff) > out_off[nm]) die(std::string("depth: the index of ") + in + " points behind a block's end");
+				B.hint[nm] = out_off[nm - 1] + (c.v & 0xffff);
+			}
+			if (first > B.hint[nm]) die(std::string("depth: the index of ") + in + " points behind a block's end");
+			B.first = first; first = 0;
+			return true;
+		}
+	};
+	std::vector<depth_batch_t> held; bool behind = false; uint64_t used = 0;
+	auto push = [&](depth_batch_t &B) {
+		uint64_t n_rec = 0, n_used = 0, n_later = 0, desc = 0, n_behind = 0;
+		const int rc = ssg_depth_push(D.d, B.cid, B.hint.data(), (int64_t)B.hint.size() - 1, B.first, &n_rec, &n_used, &n_later, &desc, &n_behind);
+		if (rc == SSG_EALIGN || rc == SSG_EIO) die(std::string("depth: ") + in + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_depth_push: ")));
+		if (rc) die(std::string("depth: ") + ssg_last_error());
+		if (desc) die(std::string("depth: ") + in + " is not sorted by coordinate (" + std::to_string(desc) + " records lie before their predecessor): sambamba sort first");
+		used += n_used; behind = behind || n_behind > 0;
+		if (n_later > 0) return true;
+		if (ssg_recs_release(S.r, B.cid)) die(std::string("depth: ") + ssg_last_error());
+		return false;
+	};
+	const size_t TEXT_N = (size_t)1 << 22;   /* positions of one ssg_depth_text */
+	std::vector<uint8_t> text; std::vector<int64_t> pairs; std::vector<size_t> pair_item; std::vector<uint64_t> sums;
+	for (const span_t &s : spans) {
+		if (ssg_depth_begin(D.d, s.tid, s.beg, s.end)) die(std::string("depth: ") + ssg_last_error());
+		behind = false; used = 0;
+		std::vector<depth_batch_t> keep;
+		for (depth_batch_t &B : held) if (push(B)) keep.push_back(std::move(B));
+		held.swap(keep);
+		depth_batch_t B;
+		while (!behind && load(B)) if (push(B)) held.push_back(std::move(B));
+		if (mode == "base" && !all && used == 0) { if (ssg_depth_end(D.d)) die(std::string("depth: ") + ssg_last_error()); continue; }
+		if (ssg_depth_finish(D.d)) die(std::string("depth: ") + ssg_last_error());
+		const std::string &name = h.names[(size_t)s.tid];
+		if (mode == "base") {
+			text.resize(std::min<size_t>(TEXT_N, (size_t)(s.end - s.beg)) * (name.size() + 23));   /* (a line: the name, two tabs, a newline, two numbers of at most ten digits) */
+			for (const ssg_bam_region_t &p : s.parts)
+				for (int64_t b = p.beg; b < p.end; b += (int64_t)TEXT_N) {
+					uint64_t len = 0;
+					if (ssg_depth_text(D.d, name.c_str(), b, std::min<int64_t>(b + (int64_t)TEXT_N, p.end), all ? 1 : 0, text.data(), text.size(), &len)) die(std::string("depth: ") + ssg_last_error());
+					io_write_all(out_fd, text.data(), (size_t)len);
+				}
+		} else {
+			pairs.clear(); pair_item.clear();
+			for (size_t k : items_of[(size_t)s.tid]) {
+				const int64_t b = std::max(items[k].beg, s.beg), e = std::min(items[k].end, s.end);
+				if (b < e) { pairs.push_back(b); pairs.push_back(e); pair_item.push_back(k); }
+			}
+			const size_t row = 2 + thr.size();
+			sums.assign(pair_item.size() * row + 1, 0);
+			if (ssg_depth_sums(D.d, pairs.data(), (int64_t)pair_item.size(), thr.data(), (int)thr.size(), sums.data())) die(std::string("depth: ") + ssg_last_error());
+			for (size_t j = 0; j < pair_item.size(); ++j) for (size_t c = 0; c < row; ++c) items[pair_item[j]].v[c] += sums[j * row + c];
+		}
+		if (ssg_depth_end(D.d)) die(std::string("depth: ") + ssg_last_error());
+	}
+	if (mode != "base") {
+		std::string out;
+		for (const depth_item_t &it : items) {
+			char num[64];
+			out += h.names[(size_t)it.tid]; out += '\t'; out += std::to_string(it.pbeg); out += '\t'; out += std::to_string(it.pend); out += '\t';
+			out += std::to_string(it.v[0]); out += '\t'; out += std::to_string(it.v[1]);
+			snprintf(num, sizeof(num), "\t%.4f", (double)it.v[1] / (double)(it.pend - it.pbeg)); out += num;
+			for (size_t c = 0; c < thr.size(); ++c) { out += '\t'; out += std::to_string(it.v[2 + c]); }
+			out += '\n';
+			if (out.size() > ((size_t)1 << 20)) { io_write_all(out_fd, out.data(), out.size()); out.clear(); }
+		}
+		io_write_all(out_fd, out.data(), out.size());
+	}
+	dev_prof_report("depth");
+	g_partial_out = 0; if (out_path) close(out_fd);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
-	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
+	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge|flagstat|depth> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
 #ifdef F_SETPIPE_SZ
 	(void)fcntl(0, F_SETPIPE_SZ, 1 << 20); (void)fcntl(1, F_SETPIPE_SZ, 1 << 20);   /* the reference's pipelines: fewer wake-ups per megabyte (fails harmlessly on files) */
 #endif
@@ -2054,6 +2234,7 @@ int main(int argc, char **argv)
 	if (!strcmp(argv[1], "index")) { ssg_stamp("sambamba_index", "start"); const int rc = cmd_index(argc - 2, argv + 2); ssg_stamp("sambamba_index", "end"); return rc; }
 	if (!strcmp(argv[1], "flagstat")) return cmd_flagstat(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "merge")) return cmd_merge(argc - 2, argv + 2);
+	if (!strcmp(argv[1], "depth")) return cmd_depth(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "index-parts")) return cmd_index_parts(argc - 2, argv + 2);
 	fprintf(stderr, "[sambamba] unsupported sub-command %s\n", argv[1]);
 	return 2;
