@@ -67,11 +67,13 @@ oracle:
 	$(MAKE) -C oracle
 
 # host emulation of the HIP execution model: same kernel + host sources, CPU-side tests only
-emu: tests/emu/libssgpu_emu.so tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test
+emu: tests/emu/libssgpu_emu.so tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/cut_test
 tests/emu/fi_mt_test: tools/dbg/fi_mt_test.cpp $(HOST)/fast_inflate.h $(HOST)/fast_inflate_mt.h
 	$(CXX) -O2 -std=c++17 tools/dbg/fi_mt_test.cpp -o $@ -lz -lpthread
 tests/emu/scan_test: tools/dbg/scan_test.cpp $(HOST)/ranksplit.h $(HOST)/ranks.h $(HOST)/fastq.h
 	$(CXX) -O2 -std=c++17 -I$(HOST) tools/dbg/scan_test.cpp -o $@ -lz -lpthread
+tests/emu/cut_test: tools/dbg/cut_test.cpp $(HOST)/bamio.h
+	$(CXX) -O2 -std=c++17 -Wall tools/dbg/cut_test.cpp -o $@ -lz -lpthread
 tests/emu/fi_test: tools/dbg/fi_test.cpp $(HOST)/fast_inflate.h
 	$(CXX) -O2 -std=c++17 tools/dbg/fi_test.cpp -o $@ -lz
 tests/emu/fq_dump: tools/dbg/fq_dump.cpp $(HOST)/fastq.h $(HOST)/fast_inflate.h
@@ -144,7 +146,7 @@ tests/emu/depth_fuzz: tools/dbg/depth_fuzz.cpp $(DEPTHFUZZ_SRCS) tests/emu/emu.c
 		tools/dbg/depth_fuzz.cpp $(DEPTHFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
 
 clean:
-	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba bin/bamkit tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz tests/emu/b2f_fuzz tests/emu/depth_fuzz $(CSRC)/*.o
+	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba bin/bamkit tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/cut_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz tests/emu/b2f_fuzz tests/emu/depth_fuzz $(CSRC)/*.o
 	$(MAKE) -C oracle clean
 .PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep fuzz-b2f fuzz-depth
 

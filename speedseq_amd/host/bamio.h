@@ -127,6 +127,26 @@ struct bgzf_out_t {
 	}
 	void finish() { drain(true); io_write_all(fd, BGZF_EOF, 28); }
 };
+/* The blocks of a stream of records whose bytes are elsewhere (the device's writers), cut as bgzf_out_t::record cuts them (tools/dbg/cut_test.cpp holds the two
+ * against each other): record i is bytes cum[i] .. cum[i + 1] of the stream; cut receives 0 and every block's end.  A block closes when the next record would not
+ * fit, a record longer than a block fills whole blocks, the stream ends its last block.  force_at (ascending record indices): a block starts at each of them, as
+ * after close_block(), and force_blk[k] is that block (0 for an index of n or more). */
+static inline void bgzf_cut_blocks(const uint64_t *cum, size_t n, std::vector<uint64_t> &cut, const std::vector<size_t> *force_at = 0, std::vector<size_t> *force_blk = 0)
+{
+	const size_t nf = force_at ? force_at->size() : 0; size_t fk = 0;
+	cut.assign(1, 0); if (force_blk) force_blk->assign(nf, 0);
+	uint64_t open_ = 0;   /* start of the open block */
+	for (size_t i = 0; i < n; ++i) {
+		const uint64_t c0 = cum[i], c1 = cum[i + 1];
+		if (fk < nf && (*force_at)[fk] == i) {
+			if (c0 > open_) { cut.push_back(c0); open_ = c0; }
+			for (; fk < nf && (*force_at)[fk] == i; ++fk) if (force_blk) (*force_blk)[fk] = cut.size() - 1;
+		}
+		if (c0 > open_ && c1 - open_ > BGZF_MAX_PAYLOAD) { cut.push_back(c0); open_ = c0; }
+		while (c1 - open_ >= BGZF_MAX_PAYLOAD) { open_ += BGZF_MAX_PAYLOAD; cut.push_back(open_); }
+	}
+	if (cum[n] > cut.back()) cut.push_back(cum[n]);
+}
 
 /* Optional batch inflate behind the reader (null: zlib on the pool's threads, as ever).  The signature and the return codes are
  * ssg_bgzf_inflate's (include/ssgpu.h): 0, -5 when a member is bad (status[] says which), anything else when the call itself failed.

@@ -222,47 +222,37 @@ static bool tofastq_device(const std::vector<const char*> &files, const std::set
 	std::vector<const char*> ids; for (const std::string &g : want) ids.push_back(g.c_str());
 	if (ssg_set_device(0) || ssg_recs_create(pool && *pool ? strtoull(pool, 0, 10) : ~(uint64_t)0 >> 1, &S.r) ||
 	    ssg_b2f_create(S.r, ids.empty() ? 0 : ids.data(), (int)ids.size(), rename ? 1 : 0, 64, &B.b)) { why = ssg_last_error(); return false; }
-	struct pinned_t { uint8_t *p; uint64_t cap; ~pinned_t() { if (p) ssg_host_free(p); } } O = { 0, 0 };
+	host_pinned_t O;
 	const int threads = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
 	uint64_t n_scanned = 0, n_pairs_all = 0, n_members = 0; int n_batches = 0; bool begun = false;
-	std::vector<uint64_t> out_off; std::vector<int32_t> status;
 	const double t0 = wall();
-	if (getenv("SSG_PROF")) { ssg_prof_reset(); ssg_prof_enable(1); }   /* the device time of every kernel (HIP events around each launch), one line each at the end */
+	dev_prof_begin();
 	auto fail = [&](const std::string &m) -> bool { if (begun) die("bamtofastq: " + m + " after output had begun (SSG_B2F_DEVICE=0 reads the files on the host)"); why = m; return false; };
 	for (size_t f = 0; f < files.size(); ++f) {
 		uint64_t v0;
 		{	bgzf_in_t in(fds[f], threads); bam_hdr_t hd;
 			if (!hdr_read(in, hd)) die(std::string(files[f]) + ": not a BAM file");
 			v0 = in.tell(); }
-		raw_members_t rd; rd.start(fds[f], files[f], v0 >> 16);
-		uint64_t first = v0 & 0xffff;
-		for (;;) {
-			rd.limit = rd.end_addr() + batch;   /* (no member that begins behind this many compressed bytes; the first one always) */
-			if (!rd.next((uint64_t)256 << 20, 4096)) break;
-			const size_t nm = rd.n(); uint32_t cid = 0;
-			out_off.resize(nm + 1); status.assign(nm, 0);
-			int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
-			if (rc == SSG_EIO) die(dev_inflate_failed("bamtofastq", rd, status));
-			if (rc) return fail(ssg_last_error());
-			if (first > out_off[nm]) { if (out_off[nm] == 0) { first = 0; (void)ssg_recs_release(S.r, cid); continue; } die(std::string(files[f]) + ": truncated BAM header"); }
+		dev_batches_t R; R.init("bamtofastq", S.r, fds[f], files[f], (uint64_t)256 << 20, 4096); R.whole_file(v0);
+		R.max_comp = batch; R.check_first = false;   /* (a header that ends behind the batch is judged here) */
+		for (int got; (got = R.next()) != DEV_END; ) {
+			if (got == DEV_FAIL) return fail(R.why);
+			const size_t nm = R.n(); const std::vector<uint64_t> &out_off = R.hint;
+			if (R.first > out_off[nm]) { if (out_off[nm] == 0) { (void)ssg_recs_release(S.r, R.cid); continue; } die(std::string(files[f]) + ": truncated BAM header"); }
 			uint64_t held = 0, held_bytes = 0, out_len = 0, n_rec = 0, n_pairs = 0;
 			(void)ssg_b2f_waiting(B.b, &held, &held_bytes);
 			const uint64_t cap = 2 * (out_off[nm] + held_bytes) + 64;   /* always enough (include/ssgpu.h) */
-			if (cap > O.cap) { if (O.p) ssg_host_free(O.p); O.cap = cap + cap / 4; O.p = (uint8_t*)ssg_host_alloc((size_t)O.cap); if (!O.p) { O.cap = 0; return fail("no page-locked memory for the text"); } }
-			rc = ssg_b2f_push(B.b, cid, out_off.data(), (int64_t)nm, first, O.p, O.cap, &out_len, &n_rec, &n_pairs);
+			if (cap > O.cap && !O.grow(cap + cap / 4)) return fail("no page-locked memory for the text");
+			const int rc = ssg_b2f_push(B.b, R.cid, out_off.data(), (int64_t)nm, R.first, O.p, O.cap, &out_len, &n_rec, &n_pairs);
 			if (rc == SSG_EIO && strstr(ssg_last_error(), "exceeds block_size")) die(std::string(files[f]) + ": " + (ssg_last_error() + strlen("ssg_b2f_push: ")));
-			if (rc) return fail(rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_b2f_push: ")) : std::string(ssg_last_error()));
+			if (rc) return fail(dev_stage_error(rc, files[f], "ssg_b2f_push: "));
 			if (out_len) { io_write_all(1, O.p, (size_t)out_len); begun = true; }
-			first = 0; n_scanned += n_rec; n_pairs_all += n_pairs; n_members += nm; ++n_batches;
+			n_scanned += n_rec; n_pairs_all += n_pairs; n_members += nm; ++n_batches;
 		}
 	}
 	uint64_t left = 0; (void)ssg_b2f_waiting(B.b, &left, 0);
 	if (left) fprintf(stderr, "[bamtofastq] %zu reads without their mate in the input were left out\n", (size_t)left);
-	if (getenv("SSG_PROF")) {
-		const char *nm[64]; double ms[64]; long cnt[64];
-		const int n = std::min(ssg_prof_get(64, nm, ms, cnt), 64);
-		for (int i = 0; i < n; ++i) fprintf(stderr, "[bamkit] bamtofastq: kernel %-24s %9.1f ms in %ld launches\n", nm[i], ms[i], cnt[i]);
-	}
+	dev_prof_report("bamkit", "bamtofastq");
 	if (dbg()) fprintf(stderr, "[bamkit] bamtofastq: on the device: %zu file%s, %llu members, %llu records scanned, %llu pairs, %llu halves left, %d batches, %.2f s\n", files.size(), files.size() == 1 ? "" : "s",
 	                   (unsigned long long)n_members, (unsigned long long)n_scanned, (unsigned long long)n_pairs_all, (unsigned long long)left, n_batches, wall() - t0);
 	return true;

@@ -1,7 +1,8 @@
 /*
- * devread.h -- what the executables that read a BAM file through the device's record store share (sambamba: view, index, merge; bamkit: bamtofastq): the
- * file's whole BGZF members read at offsets of their own, the test of what a device read path needs, the store's holder, and the words for a member the
- * device could not inflate.  The including file defines die(const std::string&) first.
+ * devread.h -- what the executables that read a BAM file through the device's record store share (sambamba: view, index, merge, depth; bamkit: bamtofastq): the
+ * file's whole BGZF members read at offsets of their own, the test of what a device read path needs, the store's holder, the words for a member the device
+ * could not inflate and for a stage's refusal, the kernel times of SSG_PROF, the page-locked output buffer, the chunks of a .bai for a list of regions, and the
+ * reader of a chunk list's batches into the store (dev_batches_t).  The including file defines die(const std::string&) first.
  */
 #ifndef SSG_DEVREAD_H
 #define SSG_DEVREAD_H
@@ -12,6 +13,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include "../../include/ssgpu.h"
+#include "bamio.h"
 
 static void die(const std::string &m);
 
@@ -75,4 +77,80 @@ static std::string dev_inflate_failed(const char *cmd, const raw_members_t &rd, 
 	while (k + 1 < nm && !status[k]) ++k;
 	return std::string(cmd) + ": inflate failed: BGZF member at file offset " + std::to_string(rd.addr + rd.moff[k]) + " of " + rd.name + " (device status " + std::to_string(status[k]) + ")";
 }
+/* a stage entry (ssg_recs_scan, ssg_recs_select, ...) came back with rc: SSG_EALIGN and SSG_EIO speak of the file, in the user's words -- the library's text without
+ * its `entry' prefix ("ssg_recs_scan: "); anything else is the library's own line */
+static std::string dev_stage_error(int rc, const char *file, const char *entry)
+{
+	return rc == SSG_EALIGN || rc == SSG_EIO ? std::string(file) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen(entry)) : std::string(ssg_last_error());
+}
+/* SSG_PROF=1: the device time of every kernel of the command's device path (HIP events around each launch), one line each at the end */
+static void dev_prof_begin() { if (getenv("SSG_PROF")) { ssg_prof_reset(); ssg_prof_enable(1); } }
+static void dev_prof_report(const char *tag, const char *cmd)
+{
+	if (!getenv("SSG_PROF")) return;
+	const char *nm[64]; double ms[64]; long cnt[64];
+	const int n = std::min(ssg_prof_get(64, nm, ms, cnt), 64);
+	for (int i = 0; i < n; ++i) fprintf(stderr, "[%s] %s: kernel %-24s %9.1f ms in %ld launches\n", tag, cmd, nm[i], ms[i], cnt[i]);
+}
+/* page-locked host memory the device writes its output blocks or text into */
+struct host_pinned_t {
+	uint8_t *p; uint64_t cap;
+	host_pinned_t() : p(0), cap(0) {}
+	~host_pinned_t() { if (p) ssg_host_free(p); }
+	bool grow(uint64_t need) { if (need <= cap) return true; if (p) ssg_host_free(p); p = (uint8_t*)ssg_host_alloc((size_t)need); cap = p ? need : 0; return p != 0; }
+};
+/* what the regions of `in' say to read: the chunks its .bai gives for them, sorted and merged.  The index must be there, not older than the file, and of the
+ * header's n_ref references; anything else ends the program in cmd's name. */
+static void bai_chunks_for(const char *cmd, const char *in, int fd, size_t n_ref, const std::vector<ssg_bam_region_t> &regions, std::vector<bai_reader_t::chunk_t> &chunks)
+{
+	const std::string bai = std::string(in) + ".bai", c = std::string(cmd) + ": ";
+	struct stat sb, si;
+	if (stat(bai.c_str(), &si) != 0) die(c + "regions need the index " + bai + ", which is not there (sambamba index)");
+	if (fstat(fd, &sb) == 0 && si.st_mtime < sb.st_mtime) die(c + "the index " + bai + " is older than " + in + " (sambamba index)");
+	bai_reader_t idx; std::string err;
+	if (!idx.load(bai.c_str(), err)) die(c + "the index " + bai + ": " + err);
+	if (idx.refs.size() != n_ref) die(c + "the index " + bai + " has " + std::to_string(idx.refs.size()) + " references, the header of " + in + " has " + std::to_string(n_ref));
+	chunks.clear();
+	for (const ssg_bam_region_t &r : regions) idx.query(r.tid, r.beg, r.end, chunks);
+	bai_chunks_merge(chunks);
+}
+
+/* The batches of a chunk list: every chunk [u, v) of virtual offsets (one chunk (v0, ~0): the whole file from v0) is read as whole members from u >> 16 through the
+ * member that holds v, at most max_members and `window' inflated bytes a batch -- and, with max_comp, max_comp compressed ones -- and each batch is inflated into the
+ * store as a chunk of its own (ssg_recs_append_bgzf).  Of a batch: cid; hint[0 .. n()], the members' offsets in the chunk's stream, the last one shortened to v's
+ * offset in the chunk's last member; first, where its first record begins (u & 0xffff in a chunk's first batch, 0 behind it); rd, the members themselves.
+ * next(): DEV_BATCH, DEV_END, or DEV_FAIL with `why' (no command's name in it: the caller ends, fails or falls back).  A member the device could not inflate ends
+ * the program here, as the host readers do.  check_first = false: a `first' behind the batch's end is the caller's to judge. */
+enum { DEV_END = 0, DEV_BATCH = 1, DEV_FAIL = -1 };
+struct dev_batches_t {
+	const char *cmd; ssg_recs_t *recs; int fd; const char *name; std::vector<bai_reader_t::chunk_t> chunks; uint64_t window, max_comp; size_t max_members; bool check_first;
+	raw_members_t rd; size_t ci; bool chunk_open; uint64_t next_first; std::vector<int32_t> status;
+	uint32_t cid; std::vector<uint64_t> hint; uint64_t first; std::string why;
+	dev_batches_t() : cmd(""), recs(0), fd(-1), name(""), window(0), max_comp(0), max_members(0), check_first(true), ci(0), chunk_open(false), next_first(0), cid(0), first(0) {}
+	void init(const char *cmd_, ssg_recs_t *recs_, int fd_, const char *name_, uint64_t window_, size_t max_members_) { cmd = cmd_; recs = recs_; fd = fd_; name = name_; window = window_; max_members = max_members_; }
+	void whole_file(uint64_t v0) { bai_reader_t::chunk_t c; c.u = v0; c.v = ~(uint64_t)0; chunks.assign(1, c); }
+	size_t n() const { return rd.n(); }
+	int next()
+	{
+		for (;;) {
+			if (ci >= chunks.size()) return DEV_END;
+			const bai_reader_t::chunk_t &c = chunks[ci];
+			if (!chunk_open) { rd.start(fd, name, c.u >> 16); next_first = c.u & 0xffff; chunk_open = true; }
+			rd.limit = c.v == ~(uint64_t)0 ? c.v : (c.v >> 16) + ((c.v & 0xffff) ? 1 : 0);
+			if (max_comp && rd.end_addr() + max_comp < rd.limit) rd.limit = rd.end_addr() + max_comp;   /* (no member that begins behind this many compressed bytes; the first one always) */
+			if (!rd.next(window, max_members)) { chunk_open = false; ++ci; continue; }
+			const size_t nm = rd.n();
+			hint.resize(nm + 1); status.assign(nm, 0);
+			const int rc = ssg_recs_append_bgzf(recs, rd.buf.data(), rd.moff.data(), (long)nm, &cid, hint.data(), status.data());
+			if (rc == SSG_EIO) die(dev_inflate_failed(cmd, rd, status));
+			if (rc) { why = ssg_last_error(); return DEV_FAIL; }
+			const bool last = (c.v & 0xffff) && rd.addr + rd.moff[nm - 1] == c.v >> 16;   /* the chunk's last member: the stream ends at v */
+			const uint64_t end = last ? hint[nm - 1] + (c.v & 0xffff) : hint[nm];
+			first = next_first; next_first = 0;
+			if (end > hint[nm] || (check_first && first > end)) { why = std::string("the index of ") + name + " points behind a block's end"; return DEV_FAIL; }
+			hint[nm] = end;
+			return DEV_BATCH;
+		}
+	}
+};
 #endif

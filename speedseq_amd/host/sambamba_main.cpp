@@ -52,6 +52,7 @@ static void inflate_hook_setup()
  * is tried as a contig name first, then split at its last colon.  -L reads BED: columns 1-3, 0-based half-open; `#', `track' and `browser' lines are skipped.
  * Both become 0-based half-open (tid, beg, end); merged into one sorted list of disjoint, non-adjacent regions they are what ssg_recs_select takes, and the
  * output is their union: every record that overlaps one of them, once, in file order. */
+struct hdr_name_of { const bam_hdr_t &h; hdr_name_of(const bam_hdr_t &h_) : h(h_) {} const char *operator()(int32_t t) const { return t >= 0 && t < (int32_t)h.names.size() ? h.names[(size_t)t].c_str() : "*"; } };   /* the contig names bam_record_to_sam prints */
 static int view_contig(const bam_hdr_t &h, const std::string &name) { for (size_t t = 0; t < h.names.size(); ++t) if (h.names[t] == name) return (int)t; return -1; }
 static bool view_number(std::string v, int64_t &x)
 {
@@ -269,7 +270,7 @@ static int cmd_view(int argc, char **argv)
 			if (bs < 32) die("view: malformed BAM record");
 			rec.resize(4 + (size_t)bs); memcpy(rec.data(), &bs, 4);
 			if (bi.get(rec.data() + 4, bs) != bs) die("view: truncated BAM");
-			if (!bam_record_to_sam(rec.data(), [&](int32_t t) -> const char* { return t < (int32_t)h.names.size() ? h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
+			if (!bam_record_to_sam(rec.data(), hdr_name_of(h), text)) die("view: a record with a tag type this printer does not know");
 			if (text.size() > ((size_t)1 << 20)) { io_write_all(1, text.data(), text.size()); text.clear(); }
 		}
 		io_write_all(1, text.data(), text.size());
@@ -538,21 +539,8 @@ static void write_sorted(const rec_store_t &S, const std::vector<uint32_t> &perm
 	std::vector<uint64_t> cum(n + 1); cum[0] = 0;
 	parallel_for((int)std::min<size_t>((size_t)std::max(1, threads), n / 65536 + 1), n, [&](size_t a, size_t b, int) { for (size_t i = a; i < b; ++i) { uint32_t bs; memcpy(&bs, S.rec(perm[i]), 4); cum[i + 1] = 4 + (uint64_t)bs; } });
 	for (size_t i = 0; i < n; ++i) cum[i + 1] += cum[i];
-	std::vector<uint64_t> cut; cut.push_back(0);
-	std::vector<size_t> force_blk(force_at ? force_at->size() : 0, 0);   /* block that starts at each forced index */
-	{	uint64_t open = 0;   /* start of the open block */
-		size_t fk = 0;
-		for (size_t i = 0; i < n; ++i) {
-			const uint64_t sz = cum[i + 1] - cum[i];
-			if (force_at && fk < force_at->size() && (*force_at)[fk] == i) {
-				if (cum[i] > open) { cut.push_back(cum[i]); open = cum[i]; }
-				while (fk < force_at->size() && (*force_at)[fk] == i) force_blk[fk++] = cut.size() - 1;
-			}
-			if (cum[i] > open && cum[i] - open + sz > BGZF_MAX_PAYLOAD) { cut.push_back(cum[i]); open = cum[i]; }
-			while (cum[i + 1] - open >= BGZF_MAX_PAYLOAD) { open += BGZF_MAX_PAYLOAD; cut.push_back(open); }   /* a record larger than a block fills whole blocks */
-		}
-		if (cum[n] > cut.back()) cut.push_back(cum[n]);
-	}
+	std::vector<uint64_t> cut; std::vector<size_t> force_blk;   /* force_blk: the block that starts at each forced index */
+	bgzf_cut_blocks(cum.data(), n, cut, force_at, &force_blk);
 	const double tw1 = wall();
 	const size_t nb = cut.size() - 1, GRP = 16, ng = (nb + GRP - 1) / GRP;   /* 1 MB of records per work item: a sort of a few hundred blocks still spreads over the pool, and the last items of a large one end together */
 	/* Hand-over between the pool, the writer and the index thread is by atomics and short sleeps, not by one mutex + condition variable: with
@@ -1450,41 +1438,27 @@ static int cmd_flagstat(int argc, char **argv)
 }
 
 /* ---------------- merge and index on device-resident records (SSG_MERGE_DEVICE=1, SSG_INDEX_DEVICE=1) ----------------
- * The input is read as raw BGZF members, inflated into the record store (ssg_recs_append_bgzf) and walked there (ssg_recs_scan): of every record 40 bytes come
+ * The input is read as raw BGZF members, inflated into the record store (dev_batches_t, devread.h) and walked there (ssg_recs_scan): of every record 40 bytes come
  * back -- its location in the store, its sort key, the fields of its index entry -- and the payload stays in HBM.  `index' needs no more; `merge' declares the
  * merged order of what it has loaded (ssg_recs_order) and has the device gather, deflate and frame the output blocks (ssg_bgzf_compress_recs).
  * Both need a file whose blocks start at records (htslib's bgzf_flush_try, sambamba, this repository's writers); for any other they fall back on the host loops. */
 static bool env_is_1(const char *name) { const char *e = getenv(name); return e && !strcmp(e, "1"); }
-/* SSG_PROF=1: the device time of every kernel of the command's device path (HIP events around each launch), one line each at the end */
-static void dev_prof_begin() { if (getenv("SSG_PROF")) { ssg_prof_reset(); ssg_prof_enable(1); } }
-static void dev_prof_report(const char *cmd)
-{
-	if (!getenv("SSG_PROF")) return;
-	const char *nm[64]; double ms[64]; long cnt[64];
-	const int n = std::min(ssg_prof_get(64, nm, ms, cnt), 64);
-	for (int i = 0; i < n; ++i) fprintf(stderr, "[sambamba] %s: kernel %-24s %9.1f ms in %ld launches\n", cmd, nm[i], ms[i], cnt[i]);
-}
-
 static const uint64_t LOC_OFF_MASK = ((uint64_t)1 << 40) - 1;
 
-/* one load: the reader's members into a new chunk, its records appended to loc / key / ent.  0; 1 with `why' (the caller falls back, or ends); bad data ends the program as the host readers do */
-static int dev_load(ssg_recs_t *recs, raw_members_t &rd, uint64_t first, const char *cmd, uint32_t &cid, std::vector<uint64_t> &out_off, uint64_t &n_new,
-                    std::vector<uint64_t> &loc, std::vector<uint64_t> &key, std::vector<ssg_bam_ent_t> &ent, std::string &why)
+/* one load: the reader's next batch into the store, its records appended to loc / key / ent.  DEV_BATCH, DEV_END, or DEV_FAIL with `why' (the caller falls back, or ends); bad data ends the program as the host readers do */
+static int dev_load(dev_batches_t &R, uint64_t &n_new, std::vector<uint64_t> &loc, std::vector<uint64_t> &key, std::vector<ssg_bam_ent_t> &ent, std::string &why)
 {
-	const size_t nm = rd.n();
-	out_off.resize(nm + 1); std::vector<int32_t> status(nm, 0);
-	int rc = ssg_recs_append_bgzf(recs, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
-	if (rc == SSG_EIO) die(dev_inflate_failed(cmd, rd, status));
-	if (rc) { why = ssg_last_error(); return 1; }
-	const size_t have = loc.size(), cap = (size_t)(out_off[nm] / 36) + 1;
-	loc.resize(have + cap); key.resize(have + cap); ent.resize(have + cap);
 	n_new = 0;
-	rc = ssg_recs_scan(recs, cid, out_off.data(), (int64_t)nm, first, cap, &n_new, loc.data() + have, key.data() + have, ent.data() + have);
+	const int got = R.next();
+	if (got != DEV_BATCH) { why = R.why; return got; }
+	const size_t nm = R.n(), have = loc.size(), cap = (size_t)(R.hint[nm] / 36) + 1;
+	loc.resize(have + cap); key.resize(have + cap); ent.resize(have + cap);
+	const int rc = ssg_recs_scan(R.recs, R.cid, R.hint.data(), (int64_t)nm, R.first, cap, &n_new, loc.data() + have, key.data() + have, ent.data() + have);
 	/* (a stream the scan calls malformed goes to the host reader as well: a record that runs past the last of these members may be a truncated file, or one more block
 	 * that does not start at a record -- the host reader tells them apart, and ends the program for the first) */
-	if (rc) { loc.resize(have); key.resize(have); ent.resize(have); why = rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_recs_scan: ")) : std::string(ssg_last_error()); n_new = 0; return 1; }
+	if (rc) { n_new = 0; why = dev_stage_error(rc, R.name, "ssg_recs_scan: "); }
 	loc.resize(have + n_new); key.resize(have + n_new); ent.resize(have + n_new);
-	return 0;
+	return rc ? DEV_FAIL : DEV_BATCH;
 }
 
 /* ---------------- view: selection (-F, -c, -o, -L, regions, -f bam with a BAM input) ----------------
@@ -1512,7 +1486,7 @@ struct view_sink_t {
 		++n_kept;
 		if (J.count) return;
 		if (bo) { bo->record(rec, len); return; }
-		if (!bam_record_to_sam(rec, [&](int32_t t) -> const char* { return t >= 0 && t < (int32_t)J.h.names.size() ? J.h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
+		if (!bam_record_to_sam(rec, hdr_name_of(J.h), text)) die("view: a record with a tag type this printer does not know");
 		if (text.size() > ((size_t)1 << 20)) { io_write_all(J.out_fd, text.data(), text.size()); text.clear(); }
 	}
 	void finish()
@@ -1621,76 +1595,55 @@ static bool view_device(view_job_t &J, std::string &why)
 	if (bam) bgzf_dev_level_set(J.level);
 	const long BATCH = 1024;   /* blocks per device call */
 	const uint64_t out_cap = bam ? ssg_bgzf_bound((uint64_t)BATCH * BGZF_MAX_PAYLOAD, BATCH) : 0;
-	struct pinned_t { uint8_t *p; ~pinned_t() { if (p) ssg_host_free(p); } } O = { bam ? (uint8_t*)ssg_host_alloc((size_t)out_cap) : 0 };
-	if (bam && !O.p) { why = "no page-locked memory for the output blocks"; return false; }
-	raw_members_t rd;
+	host_pinned_t O;
+	if (bam && !O.grow(out_cap)) { why = "no page-locked memory for the output blocks"; return false; }
+	dev_batches_t R; R.init("view", S.r, J.fd, J.in, (uint64_t)256 << 20, 4096); R.chunks = J.chunks;
 	uint64_t n_scanned = 0, n_kept = 0, n_members = 0, n_blocks = 0; int n_batches = 0; bool begun = false;
-	std::vector<uint64_t> out_off, hint, loc, key, cum, cut, boff((size_t)BATCH + 1); std::vector<ssg_bam_ent_t> ent; std::vector<int32_t> status; std::vector<uint8_t> buf;
+	std::vector<uint64_t> loc, key, cum, cut, boff((size_t)BATCH + 1); std::vector<ssg_bam_ent_t> ent; std::vector<uint8_t> buf;
 	std::string text; if (J.with_hdr && !J.count && !bam) text = J.h.text;
 	const double t0 = wall();
 	auto fail = [&](const std::string &m) -> bool { if (begun) die("view: " + m + " after output had begun (SSG_VIEW_DEVICE=0 reads the file on the host)"); why = m; return false; };
 	auto begin_bam = [&]() { if (!begun) { bgzf_out_t o(J.out_fd, J.level, J.threads); hdr_write(o, J.h); o.drain(true); begun = true; } };
-	for (const view_chunk_t &c : J.chunks) {
-		rd.start(J.fd, J.in, c.u >> 16);
-		rd.limit = c.v == ~(uint64_t)0 ? c.v : (c.v >> 16) + ((c.v & 0xffff) ? 1 : 0);
-		uint64_t first = c.u & 0xffff;
-		while (rd.next((uint64_t)256 << 20, 4096)) {
-			const size_t nm = rd.n(); uint32_t cid = 0;
-			out_off.resize(nm + 1); status.assign(nm, 0);
-			int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &cid, out_off.data(), status.data());
-			if (rc == SSG_EIO) die(dev_inflate_failed("view", rd, status));
-			if (rc) return fail(ssg_last_error());
-			hint = out_off;
-			if ((c.v & 0xffff) && rd.addr + rd.moff[nm - 1] == c.v >> 16) {   /* the chunk's last member: the stream ends at v */
-				if (out_off[nm - 1] + (c.v & 0xffff) > out_off[nm]) return fail(std::string("the index of ") + J.in + " points behind a block's end");
-				hint[nm] = out_off[nm - 1] + (c.v & 0xffff);
-			}
-			if (first > hint[nm]) return fail(std::string("the index of ") + J.in + " points behind a block's end");
-			uint64_t n_rec = 0, n_sel = 0;
-			const uint64_t cap = J.count ? 0 : hint[nm] / 36 + 1;
-			if (!J.count) { loc.resize((size_t)cap); key.resize((size_t)cap); ent.resize((size_t)cap); }
-			rc = ssg_recs_select(S.r, cid, hint.data(), (int64_t)nm, first, J.reg.empty() ? 0 : J.reg.data(), (int64_t)J.reg.size(), J.prog.empty() ? 0 : J.prog.data(), (int)J.prog.size(), cap, &n_rec, &n_sel,
-			                     J.count ? 0 : loc.data(), J.count ? 0 : key.data(), J.count ? 0 : ent.data());
-			if (rc) return fail(rc == SSG_EALIGN || rc == SSG_EIO ? std::string(rd.name) + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_recs_select: ")) : std::string(ssg_last_error()));
-			if (!J.count && n_sel) {
-				cum.resize((size_t)n_sel + 1); cum[0] = 0;
-				for (uint64_t i = 0; i < n_sel; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + ent[(size_t)i].len;
-				if (ssg_recs_order(S.r, loc.data(), cum.data(), (int64_t)n_sel)) return fail(ssg_last_error());
-				if (bam) {
-					/* the blocks, cut as bgzf_out_t::record cuts them: a block closes when the next record would not fit, a record longer than a block is split; a batch ends its last block */
-					cut.assign(1, 0); uint64_t open_ = 0;
-					for (uint64_t j = 0; j < n_sel; ++j) {
-						const uint64_t c0 = cum[(size_t)j], c1 = cum[(size_t)j + 1];
-						if (c0 > open_ && c1 - open_ > BGZF_MAX_PAYLOAD) { cut.push_back(c0); open_ = c0; }
-						while (c1 - open_ >= BGZF_MAX_PAYLOAD) { open_ += BGZF_MAX_PAYLOAD; cut.push_back(open_); }
-					}
-					if (cum[(size_t)n_sel] > cut.back()) cut.push_back(cum[(size_t)n_sel]);
-					const size_t nb = cut.size() - 1;
-					for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
-						const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
-						if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, O.p, out_cap, boff.data(), 0)) return fail(ssg_last_error());
-						begin_bam();
-						io_write_all(J.out_fd, O.p, (size_t)boff[(size_t)k]);
-					}
-					n_blocks += nb;
-				} else {
-					buf.resize((size_t)cum[(size_t)n_sel]);
-					if (ssg_recs_gather(S.r, 0, cum[(size_t)n_sel], buf.data())) return fail(ssg_last_error());
-					for (uint64_t i = 0; i < n_sel; ++i) {
-						if (!bam_record_to_sam(buf.data() + cum[(size_t)i], [&](int32_t t) -> const char* { return t >= 0 && t < (int32_t)J.h.names.size() ? J.h.names[(size_t)t].c_str() : "*"; }, text)) die("view: a record with a tag type this printer does not know");
-						if (text.size() > ((size_t)1 << 20)) { io_write_all(J.out_fd, text.data(), text.size()); text.clear(); begun = true; }
-					}
+	for (int got; (got = R.next()) != DEV_END; ) {
+		if (got == DEV_FAIL) return fail(R.why);
+		const size_t nm = R.n();
+		uint64_t n_rec = 0, n_sel = 0;
+		const uint64_t cap = J.count ? 0 : R.hint[nm] / 36 + 1;
+		if (!J.count) { loc.resize((size_t)cap); key.resize((size_t)cap); ent.resize((size_t)cap); }
+		const int rc = ssg_recs_select(S.r, R.cid, R.hint.data(), (int64_t)nm, R.first, J.reg.empty() ? 0 : J.reg.data(), (int64_t)J.reg.size(), J.prog.empty() ? 0 : J.prog.data(), (int)J.prog.size(), cap, &n_rec, &n_sel,
+		                               J.count ? 0 : loc.data(), J.count ? 0 : key.data(), J.count ? 0 : ent.data());
+		if (rc) return fail(dev_stage_error(rc, J.in, "ssg_recs_select: "));
+		if (!J.count && n_sel) {
+			cum.resize((size_t)n_sel + 1); cum[0] = 0;
+			for (uint64_t i = 0; i < n_sel; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + ent[(size_t)i].len;
+			if (ssg_recs_order(S.r, loc.data(), cum.data(), (int64_t)n_sel)) return fail(ssg_last_error());
+			if (bam) {
+				bgzf_cut_blocks(cum.data(), (size_t)n_sel, cut);   /* (a batch ends its last block) */
+				const size_t nb = cut.size() - 1;
+				for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
+					const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
+					if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, O.p, out_cap, boff.data(), 0)) return fail(ssg_last_error());
+					begin_bam();
+					io_write_all(J.out_fd, O.p, (size_t)boff[(size_t)k]);
 				}
-				if (ssg_recs_reopen(S.r)) return fail(ssg_last_error());
+				n_blocks += nb;
+			} else {
+				buf.resize((size_t)cum[(size_t)n_sel]);
+				if (ssg_recs_gather(S.r, 0, cum[(size_t)n_sel], buf.data())) return fail(ssg_last_error());
+				for (uint64_t i = 0; i < n_sel; ++i) {
+					if (!bam_record_to_sam(buf.data() + cum[(size_t)i], hdr_name_of(J.h), text)) die("view: a record with a tag type this printer does not know");
+					if (text.size() > ((size_t)1 << 20)) { io_write_all(J.out_fd, text.data(), text.size()); text.clear(); begun = true; }
+				}
 			}
-			if (ssg_recs_release(S.r, cid)) return fail(ssg_last_error());
-			first = 0; n_scanned += n_rec; n_kept += n_sel; n_members += nm; ++n_batches;
+			if (ssg_recs_reopen(S.r)) return fail(ssg_last_error());
 		}
+		if (ssg_recs_release(S.r, R.cid)) return fail(ssg_last_error());
+		n_scanned += n_rec; n_kept += n_sel; n_members += nm; ++n_batches;
 	}
 	if (J.count) text = std::to_string(n_kept) + "\n";
 	if (bam) { begin_bam(); io_write_all(J.out_fd, BGZF_EOF, 28); }
 	else io_write_all(J.out_fd, text.data(), text.size());
-	dev_prof_report("view");
+	dev_prof_report("sambamba", "view");
 	if (dbg()) fprintf(stderr, "[sambamba] view: on the device: %llu of %llu members read, %llu records scanned, %llu kept, %d batches%s, %.2f s\n", (unsigned long long)n_members, (unsigned long long)view_count_members(J.fd),
 	                   (unsigned long long)n_scanned, (unsigned long long)n_kept, n_batches, bam ? (", " + std::to_string(n_blocks) + " blocks" + bgzf_dev_level_note()).c_str() : "", wall() - t0);
 	return true;
@@ -1705,18 +1658,7 @@ static void view_select_run(const char *in, int fd, bgzf_in_t *bi, bam_hdr_t &h,
 }
 static void view_select(view_job_t &J, bool with_regions)
 {
-	if (with_regions) {   /* the index says what to read */
-		const std::string bai = std::string(J.in) + ".bai";
-		struct stat sb, si;
-		if (stat(bai.c_str(), &si) != 0) die("view: regions need the index " + bai + ", which is not there (sambamba index)");
-		if (fstat(J.fd, &sb) == 0 && si.st_mtime < sb.st_mtime) die("view: the index " + bai + " is older than " + J.in + " (sambamba index)");
-		bai_reader_t idx; std::string err;
-		if (!idx.load(bai.c_str(), err)) die("view: the index " + bai + ": " + err);
-		if (idx.refs.size() != J.h.names.size()) die("view: the index " + bai + " has " + std::to_string(idx.refs.size()) + " references, the header of " + J.in + " has " + std::to_string(J.h.names.size()));
-		J.chunks.clear();
-		for (const ssg_bam_region_t &r : J.reg) idx.query(r.tid, r.beg, r.end, J.chunks);
-		bai_chunks_merge(J.chunks);
-	}
+	if (with_regions) bai_chunks_for("view", J.in, J.fd, J.h.names.size(), J.reg, J.chunks);   /* the index says what to read */
 	if (env_is_1("SSG_VIEW_DEVICE")) {
 		std::string why;
 		if (view_device(J, why)) return;
@@ -1732,18 +1674,19 @@ static bool index_device(const char *in, int fd, int n_ref, uint64_t v0, std::st
 	recs_holder_t S;
 	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) { why = ssg_last_error(); return false; }
 	dev_prof_begin();
-	raw_members_t rd; rd.start(fd, in, v0 >> 16);
+	dev_batches_t R; R.init("index", S.r, fd, in, (uint64_t)256 << 20, 4096); R.whole_file(v0);   /* a batch: the 4096 members of one device call of the inflate, at most 256 MB of records */
+	const raw_members_t &rd = R.rd; const std::vector<uint64_t> &out_off = R.hint;
 	bai_t idx(n_ref, v0);
-	uint64_t first = v0 & 0xffff, n_total = 0; bool have = false; ssg_bam_ent_t p; memset(&p, 0, sizeof(p));
-	std::vector<uint64_t> out_off, loc, key; std::vector<ssg_bam_ent_t> ent;
+	uint64_t n_total = 0; bool have = false; ssg_bam_ent_t p; memset(&p, 0, sizeof(p));
+	std::vector<uint64_t> loc, key; std::vector<ssg_bam_ent_t> ent;
 	const double t0 = wall(); double t_dev = 0;
-	/* a batch: the 4096 members of one device call of the inflate, at most 256 MB of records */
-	while (rd.next((uint64_t)256 << 20, 4096)) {
-		uint32_t cid = 0; uint64_t n = 0; loc.clear(); key.clear(); ent.clear();
+	for (;;) {
+		uint64_t n = 0; loc.clear(); key.clear(); ent.clear();
 		const double t1 = wall();
-		if (dev_load(S.r, rd, first, "index", cid, out_off, n, loc, key, ent, why)) return false;
+		const int got = dev_load(R, n, loc, key, ent, why);
+		if (got == DEV_FAIL) return false;
+		if (got == DEV_END) break;
 		t_dev += wall() - t1;
-		first = 0;
 		size_t m = 0;
 		for (uint64_t i = 0; i < n; ++i) {   /* the record's virtual offset: the member that holds its first byte (one without bytes holds none) */
 			const uint64_t o = loc[i] & LOC_OFF_MASK;
@@ -1753,23 +1696,23 @@ static bool index_device(const char *in, int fd, int n_ref, uint64_t v0, std::st
 			p = ent[i]; have = true;
 		}
 		n_total += n;
-		if (ssg_recs_release(S.r, cid)) { why = ssg_last_error(); return false; }
+		if (ssg_recs_release(S.r, R.cid)) { why = ssg_last_error(); return false; }
 	}
 	const uint64_t eof_v = rd.end_addr() << 16;
 	if (have && idx.push(p.tid, p.pos, p.end, eof_v, !(p.flag & 4)) < 0) die("index: the file is not coordinate-sorted");
 	idx.finish(eof_v);
 	idx.save((std::string(in) + ".bai").c_str());
-	dev_prof_report("index");
+	dev_prof_report("sambamba", "index");
 	if (dbg()) fprintf(stderr, "[sambamba] index: %llu records found on the device in %.2f s (inflate into the store + scan %.2f s)\n", (unsigned long long)n_total, wall() - t0, t_dev);
 	return true;
 }
 
 /* one input of the device merge: its reader, and what is loaded of it and not yet written, in file order */
 struct dm_src_t {
-	raw_members_t rd; bool ended; uint64_t first, n_seen, last_key, pend_bytes;
+	dev_batches_t R; bool ended; uint64_t n_seen, last_key, pend_bytes;
 	std::vector<uint64_t> loc, key; std::vector<ssg_bam_ent_t> ent;
 	std::deque<std::pair<uint32_t, uint64_t> > chunks;   /* chunk id, its records not yet written */
-	dm_src_t() : ended(false), first(0), n_seen(0), last_key(0), pend_bytes(0) {}
+	dm_src_t() : ended(false), n_seen(0), last_key(0), pend_bytes(0) {}
 };
 
 /* `sambamba merge' on the device.  true: the file, its .bai and the note are written.  false with `why': nothing was written, the host merge takes over.
@@ -1791,30 +1734,30 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 	if (ssg_recs_create(pool, &S.r)) { why = ssg_last_error(); return false; }
 	dev_prof_begin();
 	std::vector<dm_src_t> in(F);
-	for (size_t f = 0; f < F; ++f) { const uint64_t v = src[f].in->tell(); in[f].rd.start(src[f].fd, files[f + 1], v >> 16); in[f].first = v & 0xffff; }
+	for (size_t f = 0; f < F; ++f) { in[f].R.init("merge", S.r, src[f].fd, files[f + 1], window, 4096); in[f].R.whole_file(src[f].in->tell()); }
 	int ofd = -1; uint64_t coff = 0;
 	auto fail = [&](const std::string &m) {   /* after output began */
 		if (ofd >= 0) { close(ofd); unlink(files[0]); }
 		die("merge: " + m + "; the partial output was removed -- SSG_MERGE_DEVICE=0 merges on the host");
 	};
-	std::vector<uint64_t> out_off;
 	/* an input that has less than half a window loaded takes its next members (a round loads every input at the start; an input that is ahead of the others waits) */
 	auto load = [&](bool &ok) {
 		ok = true;
 		for (size_t f = 0; f < F && ok; ++f) {
 			dm_src_t &s = in[f];
 			while (!s.ended && (s.key.empty() || s.pend_bytes < window / 2)) {
-				if (!s.rd.next(window, 4096)) { s.ended = true; break; }
-				uint32_t cid = 0; uint64_t n = 0; const size_t have = s.key.size();
-				if (dev_load(S.r, s.rd, s.first, "merge", cid, out_off, n, s.loc, s.key, s.ent, why)) { ok = false; break; }
-				s.first = 0;
+				uint64_t n = 0; const size_t have = s.key.size();
+				const int got = dev_load(s.R, n, s.loc, s.key, s.ent, why);
+				if (got == DEV_END) { s.ended = true; break; }
+				if (got == DEV_FAIL) { ok = false; break; }
+				const uint32_t cid = s.R.cid;
 				for (size_t i = have; i < have + n; ++i) {
 					if (s.n_seen && s.key[i] < s.last_key) { const std::string m = std::string(files[f + 1]) + " is not coordinate-sorted: its record " + std::to_string(s.n_seen) + " (counted from 0) descends"; if (ofd >= 0) fail(m); die("merge: " + m); }
 					s.last_key = s.key[i]; ++s.n_seen; s.pend_bytes += s.ent[i].len;
 				}
 				if (n) s.chunks.push_back(std::make_pair(cid, n));
 				else if (ssg_recs_release(S.r, cid)) { ok = false; why = ssg_last_error(); break; }
-				if (s.rd.at_end) s.ended = true;
+				if (s.R.rd.at_end) s.ended = true;
 				if (s.key.size() > have) break;   /* (one load a round for an input that got records) */
 			}
 		}
@@ -1831,8 +1774,8 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 	bool have_p = false; ssg_bam_ent_t p; memset(&p, 0, sizeof(p));
 	const long BATCH = 1024;   /* blocks per device call: 64 MB of records */
 	const uint64_t out_cap = ssg_bgzf_bound((uint64_t)BATCH * BGZF_MAX_PAYLOAD, BATCH);
-	uint8_t *const obuf = (uint8_t*)ssg_host_alloc((size_t)out_cap);
-	if (!obuf) fail("no page-locked memory for the output blocks");
+	host_pinned_t O;
+	if (!O.grow(out_cap)) fail("no page-locked memory for the output blocks");
 	std::vector<uint64_t> keys, sloc, cum, cut, boff((size_t)BATCH + 1); std::vector<uint32_t> perm, from; std::vector<ssg_bam_ent_t> sent; std::vector<size_t> take(F), base(F + 1);
 	uint64_t n_written = 0, n_rounds = 0, n_blocks = 0; const double t0 = wall(); double t_load = 0, t_sort = 0, t_write = 0;
 	for (;;) {
@@ -1858,22 +1801,15 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 				const size_t g = perm[(size_t)j], f = (size_t)(std::upper_bound(base.begin(), base.end(), g) - base.begin()) - 1, i = g - base[f];
 				sloc[(size_t)j] = in[f].loc[i]; sent[(size_t)j] = in[f].ent[i]; cum[(size_t)j + 1] = cum[(size_t)j] + in[f].ent[i].len;
 			}
-			/* the blocks, cut as bgzf_out_t::record cuts them: a block closes when the next record would not fit, a record longer than a block is split; a round ends its last block */
-			cut.assign(1, 0); uint64_t open_ = 0;
-			for (uint64_t j = 0; j < E; ++j) {
-				const uint64_t c0 = cum[(size_t)j], c1 = cum[(size_t)j + 1];
-				if (c0 > open_ && c1 - open_ > BGZF_MAX_PAYLOAD) { cut.push_back(c0); open_ = c0; }
-				while (c1 - open_ >= BGZF_MAX_PAYLOAD) { open_ += BGZF_MAX_PAYLOAD; cut.push_back(open_); }
-			}
-			if (cum[(size_t)E] > cut.back()) cut.push_back(cum[(size_t)E]);
+			bgzf_cut_blocks(cum.data(), (size_t)E, cut);   /* (a round ends its last block) */
 			t_sort += wall() - t1;
 			const double t2 = wall();
 			if (ssg_recs_order(S.r, sloc.data(), cum.data(), (int64_t)E)) fail(ssg_last_error());
 			const size_t nb = cut.size() - 1; uint64_t j = 0;
 			for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
 				const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
-				if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, obuf, out_cap, boff.data(), 0)) fail(ssg_last_error());
-				io_write_all(ofd, obuf, (size_t)boff[(size_t)k]);
+				if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, O.p, out_cap, boff.data(), 0)) fail(ssg_last_error());
+				io_write_all(ofd, O.p, (size_t)boff[(size_t)k]);
 				/* the index entries of the records that begin in these blocks: an entry closes at the virtual offset of the record behind it */
 				size_t b = b0;
 				for (; j < E && cum[(size_t)j] < cut[b0 + (size_t)k]; ++j) {
@@ -1906,7 +1842,6 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 		if (!ok) fail(why);
 		t_load += wall() - t3;
 	}
-	ssg_host_free(obuf);
 	io_write_all(ofd, BGZF_EOF, 28);
 	const uint64_t eof_v = (coff + 28) << 16;
 	if (have_p && idx.push(p.tid, p.pos, p.end, eof_v, !(p.flag & 4)) < 0) fail("the merged records are not in coordinate order");
@@ -1914,7 +1849,7 @@ static bool merge_device(const std::vector<const char*> &files, std::vector<merg
 	if (close(ofd) != 0) { ofd = -1; fail(std::string("cannot write ") + files[0]); }
 	idx.save((std::string(files[0]) + ".bai").c_str());
 	bai_note_write(files[0]);
-	dev_prof_report("merge");
+	dev_prof_report("sambamba", "merge");
 	if (dbg()) fprintf(stderr, "[sambamba] merge: %llu records of %zu inputs merged on the device in %llu round(s) of at most %llu bytes an input: %llu blocks, %.2f s (after the first load: inflate + scan %.2f s, order %.2f s, gather + deflate + write %.2f s)%s\n",
 	                   (unsigned long long)n_written, F, (unsigned long long)n_rounds, (unsigned long long)window, (unsigned long long)n_blocks, wall() - t0, t_load, t_sort, t_write, bgzf_dev_level_note().c_str());
 	return true;
@@ -2111,18 +2046,9 @@ static int cmd_depth(int argc, char **argv)
 			spans.back().end = p.end; spans.back().parts.push_back(p);
 		}
 	/* what to read */
-	std::vector<view_chunk_t> chunks;
-	if (with_regions) {
-		const std::string bai = std::string(in) + ".bai";
-		struct stat sb, si;
-		if (stat(bai.c_str(), &si) != 0) die("depth: regions need the index " + bai + ", which is not there (sambamba index)");
-		if (fstat(fd, &sb) == 0 && si.st_mtime < sb.st_mtime) die("depth: the index " + bai + " is older than " + in + " (sambamba index)");
-		bai_reader_t idx; std::string err;
-		if (!idx.load(bai.c_str(), err)) die("depth: the index " + bai + ": " + err);
-		if (idx.refs.size() != h.names.size()) die("depth: the index " + bai + " has " + std::to_string(idx.refs.size()) + " references, the header of " + in + " has " + std::to_string(h.names.size()));
-		for (const ssg_bam_region_t &r : targets) idx.query(r.tid, r.beg, r.end, chunks);
-		bai_chunks_merge(chunks);
-	} else { view_chunk_t c; c.u = v0; c.v = ~(uint64_t)0; chunks.push_back(c); }
+	dev_batches_t R;
+	if (with_regions) bai_chunks_for("depth", in, fd, h.names.size(), targets, R.chunks);
+	else R.whole_file(v0);
 	int out_fd = 1;
 	if (out_path) { out_fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666); if (out_fd < 0) die(std::string("cannot write ") + out_path + ": " + strerror(errno)); g_partial_out = out_path; }
 	recs_holder_t S;
@@ -2130,39 +2056,19 @@ static int cmd_depth(int argc, char **argv)
 	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) die(std::string("depth: ") + ssg_last_error());
 	if (ssg_depth_create(S.r, filter.prog.data(), (int)filter.prog.size(), min_baseq, &D.d)) die(std::string("depth: ") + ssg_last_error());
 	dev_prof_begin();
-	/* the reader: the next batch of the chunk list, as view_device cuts them */
-	raw_members_t rd; size_t ci = 0; bool chunk_open = false; uint64_t first = 0; std::vector<int32_t> status; std::vector<uint64_t> out_off;
+	/* the reader: the next batch of the chunk list, kept while a later span needs it */
+	R.init("depth", S.r, fd, in, (uint64_t)64 << 20, 1024);
 	auto load = [&](depth_batch_t &B) -> bool {
-		for (;;) {
-			if (!chunk_open) {
-				if (ci >= chunks.size()) return false;
-				const view_chunk_t &c = chunks[ci];
-				rd.start(fd, in, c.u >> 16); rd.limit = c.v == ~(uint64_t)0 ? c.v : (c.v >> 16) + ((c.v & 0xffff) ? 1 : 0);
-				first = c.u & 0xffff; chunk_open = true;
-			}
-			if (!rd.next((uint64_t)64 << 20, 1024)) { chunk_open = false; ++ci; continue; }
-			const view_chunk_t &c = chunks[ci];
-			const size_t nm = rd.n();
-			out_off.resize(nm + 1); status.assign(nm, 0);
-			const int rc = ssg_recs_append_bgzf(S.r, rd.buf.data(), rd.moff.data(), (long)nm, &B.cid, out_off.data(), status.data());
-			if (rc == SSG_EIO) die(dev_inflate_failed("depth", rd, status));
-			if (rc) die(std::string("depth: ") + ssg_last_error());
-			B.hint = out_off;
-			if ((c.v & 0xffff) && rd.addr + rd.moff[nm - 1] == c.v >> 16) {   /* the chunk's last member: the stream ends at v */
-				if (out_off[nm - 1] + (c.v & 0xffff) > out_off[nm]) die(std::string("depth: the index of ") + in + " points behind a block's end");
-				B.hint[nm] = out_off[nm - 1] + (c.v & 0xffff);
-			}
-			if (first > B.hint[nm]) die(std::string("depth: the index of ") + in + " points behind a block's end");
-			B.first = first; first = 0;
-			return true;
-		}
+		const int got = R.next();
+		if (got == DEV_FAIL) die("depth: " + R.why);
+		if (got == DEV_BATCH) { B.cid = R.cid; B.hint = R.hint; B.first = R.first; }
+		return got == DEV_BATCH;
 	};
 	std::vector<depth_batch_t> held; bool behind = false; uint64_t used = 0;
 	auto push = [&](depth_batch_t &B) {
 		uint64_t n_rec = 0, n_used = 0, n_later = 0, desc = 0, n_behind = 0;
 		const int rc = ssg_depth_push(D.d, B.cid, B.hint.data(), (int64_t)B.hint.size() - 1, B.first, &n_rec, &n_used, &n_later, &desc, &n_behind);
-		if (rc == SSG_EALIGN || rc == SSG_EIO) die(std::string("depth: ") + in + (rc == SSG_EALIGN ? " is " : ": ") + (ssg_last_error() + strlen("ssg_depth_push: ")));
-		if (rc) die(std::string("depth: ") + ssg_last_error());
+		if (rc) die("depth: " + dev_stage_error(rc, in, "ssg_depth_push: "));
 		if (desc) die(std::string("depth: ") + in + " is not sorted by coordinate (" + std::to_string(desc) + " records lie before their predecessor): sambamba sort first");
 		used += n_used; behind = behind || n_behind > 0;
 		if (n_later > 0) return true;
@@ -2216,7 +2122,7 @@ static int cmd_depth(int argc, char **argv)
 		}
 		io_write_all(out_fd, out.data(), out.size());
 	}
-	dev_prof_report("depth");
+	dev_prof_report("sambamba", "depth");
 	g_partial_out = 0; if (out_path) close(out_fd);
 	return 0;
 }
