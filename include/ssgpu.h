@@ -602,6 +602,58 @@ int  ssg_depth_text(ssg_depth_t *d, const char *name, int64_t p0, int64_t p1, in
 int  ssg_depth_end(ssg_depth_t *d);
 void ssg_depth_free(ssg_depth_t *d);
 
+/* ---- the QC tables of `samtools stats' on the device (csrc/ssg_stats.cpp, k_stats.h; samtools 1.3.1 stats.c: the numbers are collect_stats' for a file read
+ * whole, without -r, -t, -S, -I, -l, -q; the GC-depth table is not computed) ----
+ * The stream is fed chunk by chunk (ssg_recs_append_bgzf, then ssg_stats_push).  Everything but the coverage histogram is a sum of per-record integers: any order
+ * of the adds gives the same bits.  What a record adds, in collect_stats' order:
+ *   - the filter program (the programs and fields of ssg_recs_select; what -f / -F / -d are to samtools) leaves 0: SSG_ST_FILTERED + 1, nothing else;
+ *   - update_checksum: three CRC-32s (zlib's, initial value 0) are added into three 32-bit sums that wrap: the name up to its NUL, the (l_seq + 1) / 2 packed
+ *     sequence bytes, and the FIRST (l_seq + 1) / 2 quality bytes (samtools' own count, kept); the last two only when l_seq > 0;
+ *   - flag 0x100: SSG_ST_SECONDARY + 1 and nothing more; l_seq == 0: nothing more; flag 0x400: SSG_ST_DUP + 1, SSG_ST_DUP_LEN + l_seq;
+ *   - unclipped_length: l_seq + the lengths of the H operations; SSG_ST_MAX_LEN is its maximum;
+ *   - collect_orig_read_stats, for records with neither 0x100 nor 0x800: rl[unclipped length], total length, QC-fail, paired, first (0x80 clear) or last (0x80
+ *     set) fragment; per base i the cycle is i, or l_seq - 1 - i with 0x10: bases[cycle][A, C, G, T, N, other] from the 4-bit codes 1, 2, 4, 8, 15 and the rest;
+ *     quals[fragment][cycle][q] from the quality byte at l_seq - 1 - cycle with 0x10, else at cycle, with its sum and maximum; with g the C and G bases, the bins
+ *     g * 199 / l_seq up to but excluding min((g + 1) * 199 / l_seq, 199) of gc[fragment] get + 1; then unmapped, or bases mapped, MQ0, single / paired-and-mapped,
+ *     proper, mates on another contig, as the function has them;
+ *   - flag 0x4 clear: count_indels -- operations of length 0 are skipped, an I at query offset c of a record of fragment f (0x40 set: 0, else 1) adds to
+ *     ic[f][c] (ic[f][l_seq - c - len] with 0x10), a D to ic[2 + f][c - 1] (ic[2 + f][l_seq - c - 1] with 0x10; dropped when that is below 0), both to id[0 / 1][len - 1]
+ *     up to length 300; N, H and P do not advance c;  the insert size: |isize| in 64 bits clamped to n_isize - 1, counted when it is > 0 or tid == mtid for
+ *     records that are paired with both mates mapped, by collect_stats' orientation rule into isize[inward, outward, other]; the first NM tag of the aux area
+ *     (walked with the types A c C s S i I f Z H B; any other type, a Z / H without NUL or a B cut short ends the walk) as bam_aux2i reads it (c C s S i I,
+ *     anything else 0), added in 64-bit two's complement; the M and I lengths;
+ *   - round_buffer_*: every such mapped record covers [pos, pos + l_seq - 1] (the read length, not the CIGAR; past a contig's end as well); cov[] is the
+ *     histogram of the non-zero depths through coverage_idx(cov_min, cov_max, cov_step), n_cov = 3 + (cov_max - cov_min) / cov_step bins after samtools' own
+ *     rounding of the three (ssg_stats_ncov).  This is the one order-dependent part: the records that get this far must not descend in (tid, pos), within a push
+ *     or from one push to the next; from the first descent on SSG_ST_SORTED reads 0, cov[] is all 0 and stays so.  (samtools lets a contig recur; here that is a
+ *     descent.)  The depths are kept as differences over a window of `span' positions plus max_len of slack that the object slides itself.
+ * ssg_stats_create: opt->max_len: the longest unclipped length taken (1 .. 65535; the tables have max_len + 1 rows); n_isize 1 .. 2^24; 0 <= cov_min <= cov_max
+ *   <= 2^24, cov_step >= 1, at most 8192 bins; span 1 .. 2^28, 0: 2^22.  SSG_EINVAL for these and for what ssg_recs_select refuses of a program.  The object
+ *   lives on the store's device and must be freed before the store.
+ * ssg_stats_push: the chunk's records are found as ssg_recs_scan finds them (the same hints, `first', SSG_EIO / SSG_EALIGN / SSG_EINVAL and words, under this
+ *   entry's name).  *n_rec: the records scanned; *descents: the descents this push saw.  SSG_EIO for a record with 32 + l_qname + 4 n_cigar + (l_seq + 1) / 2 +
+ *   l_seq > block_size, for a record that gets as far as count_indels with n_cigar == 0 (samtools aborts on it), and for an insertion or deletion whose cycle lies
+ *   outside 0 .. max_len; SSG_ERANGE for an unclipped length above max_len (the record's offset in ssg_last_error()); SSG_EINVAL after ssg_stats_finish and while
+ *   an order is declared.  On every failure the object's numbers are those from before the call.  The chunk is not released.
+ * ssg_stats_finish: the window's last depths go into cov[]; no push after it.
+ * ssg_stats_get: scalars[SSG_ST_N]; quals[2][max_len + 1][256]; bases[max_len + 1][6]; gc[2][200]; isize[3][n_isize], each pair having been counted twice and
+ *   halved here with truncation, as output_stats does; rl[max_len + 1]; id[2][300]; ic[4][max_len + 1]; cov[n_cov]: 64-bit integers, a NULL pointer skips its
+ *   table.  Allowed at any time; cov[] is complete after ssg_stats_finish.
+ * Results do not depend on SSG_STATS_TILE (the cycles of the per-base kernel's LDS tile, 1 .. 32) or SSG_STATS_SLAB (the records a workgroup of it takes). */
+enum { SSG_ST_FILTERED, SSG_ST_SECONDARY, SSG_ST_DUP, SSG_ST_DUP_LEN, SSG_ST_MAX_LEN, SSG_ST_TOTAL_LEN, SSG_ST_QCFAIL, SSG_ST_PAIRED, SSG_ST_FIRST, SSG_ST_LAST,
+       SSG_ST_UNMAPPED, SSG_ST_BASES_MAPPED, SSG_ST_MQ0, SSG_ST_SINGLE, SSG_ST_PAIRED_MAPPED, SSG_ST_PROPER, SSG_ST_ANOMALOUS, SSG_ST_MISMATCHES, SSG_ST_BASES_CIGAR,
+       SSG_ST_SUM_QUAL, SSG_ST_MAX_QUAL, SSG_ST_CHK_NAMES, SSG_ST_CHK_READS, SSG_ST_CHK_QUALS, SSG_ST_SORTED, SSG_ST_N = 32 };
+#define SSG_STATS_NGC 200
+#define SSG_STATS_NINDEL 300
+typedef struct { int32_t max_len, n_isize, cov_min, cov_max, cov_step, span; } ssg_stats_opt_t;
+typedef struct ssg_stats ssg_stats_t;
+int64_t ssg_stats_ncov(const ssg_stats_opt_t *opt);   /* the bins of cov[] for these options; -1 for options ssg_stats_create refuses */
+int  ssg_stats_create(ssg_recs_t *r, const ssg_bam_fop_t *prog, int n_prog, const ssg_stats_opt_t *opt, ssg_stats_t **out);
+int  ssg_stats_push(ssg_stats_t *s, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t *n_rec, uint64_t *descents);
+int  ssg_stats_finish(ssg_stats_t *s);
+int  ssg_stats_get(ssg_stats_t *s, uint64_t *scalars, uint64_t *quals, uint64_t *bases, uint64_t *gc, uint64_t *isize, uint64_t *rl, uint64_t *id, uint64_t *ic, uint64_t *cov);
+void ssg_stats_free(ssg_stats_t *s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -958,6 +958,75 @@ def depth_text(lib, d, name, p0, p1, all_positions=False, cap=None):
     return rc, b"", int(n.value)
 
 
+STATS_SCALARS = ("filtered", "secondary", "dup", "dup_len", "max_len", "total_len", "qcfail", "paired", "first", "last", "unmapped", "bases_mapped", "mq0", "single",
+                 "paired_mapped", "proper", "anomalous", "mismatches", "bases_cigar", "sum_qual", "max_qual", "chk_names", "chk_reads", "chk_quals", "sorted")
+STATS_N_SCALARS, STATS_NGC, STATS_NINDEL = 32, 200, 300
+
+
+class StatsOpt(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("max_len", "n_isize", "cov_min", "cov_max", "cov_step", "span")]
+
+
+def stats_opt(max_len=1024, n_isize=8000, cov_min=1, cov_max=1000, cov_step=1, span=0):
+    return StatsOpt(max_len, n_isize, cov_min, cov_max, cov_step, span)
+
+
+class Stats:
+    """the QC tables on a record store (ssg_stats_*): freed with the object or by close(), before its store."""
+
+    def __init__(self, lib, h, recs, opt):
+        self.lib, self.h, self.recs, self.opt = lib, h, recs, opt
+        lib.l.ssg_stats_ncov.restype = C.c_int64
+        self.n_cov = int(lib.l.ssg_stats_ncov(C.byref(opt)))
+
+    def close(self):
+        if self.h is not None:
+            self.lib.l.ssg_stats_free.argtypes = [C.c_void_p]
+            self.lib.l.ssg_stats_free.restype = None
+            if self.recs.h is not None:
+                self.lib.l.ssg_stats_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def stats_create(lib, recs, prog=(), opt=None):
+    """ssg_stats_create: prog as recs_select takes it, opt a StatsOpt (stats_opt()).  Returns (rc, Stats or None); no return code raises."""
+    fop = np.array([(op, arg, 0, value) for op, arg, value in prog], dtype=BAM_FOP_DT)
+    opt = opt if opt is not None else stats_opt()
+    h = C.c_void_p()
+    rc = lib.l.ssg_stats_create(recs.h if recs is not None else None, _ptr(fop) if len(fop) else None, C.c_int(len(fop)), C.byref(opt), C.byref(h))
+    return rc, (Stats(lib, h, recs, opt) if rc == 0 else None)
+
+
+def stats_push(lib, s, chunk_id, hint, first=0):
+    """ssg_stats_push: returns (rc, n_rec, descents); no return code raises."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_rec, desc = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.l.ssg_stats_push(s.h, C.c_uint32(chunk_id), _ptr(hint) if len(hint) else None, C.c_int64(len(hint) - 1), C.c_uint64(first), C.byref(n_rec), C.byref(desc))
+    return rc, int(n_rec.value), int(desc.value)
+
+
+def stats_finish(lib, s):
+    return lib.l.ssg_stats_finish(s.h)
+
+
+def stats_get(lib, s):
+    """ssg_stats_get: (rc, dict) -- the scalars by name (STATS_SCALARS) and the tables quals[2][rows][256], bases[rows][6], gc[2][200], isize[3][n_isize], rl[rows],
+    id[2][300], ic[4][rows], cov[n_cov] as uint64 arrays, rows = max_len + 1."""
+    rows, ni = s.opt.max_len + 1, s.opt.n_isize
+    shapes = {"quals": (2, rows, 256), "bases": (rows, 6), "gc": (2, STATS_NGC), "isize": (3, ni), "rl": (rows,), "id": (2, STATS_NINDEL), "ic": (4, rows), "cov": (s.n_cov,)}
+    sc = np.zeros(STATS_N_SCALARS + 1, dtype=np.uint64)
+    sc[STATS_N_SCALARS] = 0xABABABAB
+    t = {k: np.full(int(np.prod(v)) + 1, 0xABABABAB, dtype=np.uint64) for k, v in shapes.items()}
+    rc = lib.l.ssg_stats_get(s.h, _ptr(sc), *[_ptr(t[k]) for k in ("quals", "bases", "gc", "isize", "rl", "id", "ic", "cov")])
+    assert int(sc[STATS_N_SCALARS]) == 0xABABABAB and all(int(a[-1]) == 0xABABABAB for a in t.values())   # nothing behind the tables
+    out = {k: t[k][:-1].reshape(v) for k, v in shapes.items()}
+    out.update({name: int(sc[i]) for i, name in enumerate(STATS_SCALARS)})
+    return rc, out
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

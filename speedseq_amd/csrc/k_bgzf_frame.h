@@ -58,6 +58,7 @@ SSG_DEVFN uint32_t bzf_crc_word(const uint32_t *tab, uint32_t c, uint32_t w)
 	return tab[768 + (c & 0xff)] ^ tab[512 + ((c >> 8) & 0xff)] ^ tab[256 + ((c >> 16) & 0xff)] ^ tab[c >> 24];
 }
 
+#ifndef SSG_BZF_TABLES_ONLY   /* (k_stats.h takes the tables and the two steps and leaves the kernels to their own translation unit) */
 /* crc[i] = CRC-32 of data[cut[i] .. cut[i+1]), i < n_ranges; a wave takes ranges i, i + waves of the grid, ... */
 __global__ void __launch_bounds__(256) ssg_k_crc32_ranges(const uint8_t *data, const uint64_t *cut, long n_ranges, uint32_t *crc)
 {
@@ -105,4 +106,5 @@ __global__ void __launch_bounds__(256) ssg_k_bgzf_frame(const uint8_t *tmp, uint
 	else if (t < 2) d[18 + t] = t ? 0 : 3;
 	if (t >= 64 && t < 72) { const int j = t - 64; d[18 + clen + (uint32_t)j] = (uint8_t)((j < 4 ? crc[b] : isize) >> (8 * (j & 3))); }
 }
+#endif
 #endif

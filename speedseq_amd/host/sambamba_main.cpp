@@ -8,12 +8,15 @@
  *   index <in.bam>                            <in.bam>.bai                            bin/speedseq:486-494
  *   merge -t N out.bam in1.bam in2.bam ...    merge of coordinate-sorted files        bin/speedseq:2002-2004
  *   depth base|region|window ... <in.bam>     coverage per base, BED line or window, counted on the device (what `speedseq sv -d' and `var' ask of a BAM)
+ *   stats [-F filter] [-c ..] [-i n] <in.bam> the QC report of `samtools stats', its tables counted on the device
  * Formats and orders follow the in-tree samtools / htslib 1.3.1 (bamio.h cites the lines).  Text parsing, BGZF (de)compression
  * and the gather of sorted records run on host threads; the coordinate sort itself -- a stable sort of the 64-bit keys
  * tid<<32 | (pos+1)<<1 | reverse -- runs on the MI355X through libssgpu (ssg_sort_u64_perm), chunk by chunk when the input
  * exceeds the -m budget (chunks are spilled to --tmpdir and merged; ties keep input order, as samtools' merge of sorted blocks).
  */
 #include <queue>
+#include <cmath>
+#include <cstdarg>
 #include <memory>
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -2127,9 +2130,181 @@ static int cmd_depth(int argc, char **argv)
 	return 0;
 }
 
+/* ---------------- stats: the QC tables of `samtools stats', counted on the device (ssg_stats_*, include/ssgpu.h) ----------------
+ * The whole file is read in batches of whole members that go into the record store; every batch is pushed and released.  What is printed is output_stats of
+ * samtools 1.3.1 stats.c, line for line and section comment for section comment, behind two comment lines of this program's own: CHK, the 31 SN lines, FFQ, LFQ,
+ * GCF, GCL, GCC, IS, RL, ID, IC and COV.  The five float lines restate the C expressions with their types.  GCD is not computed (a comment line says so), and an
+ * unsorted file gets a comment in place of its COV rows.  There is no host path. */
+static void stats_put(std::string &out, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static void stats_put(std::string &out, const char *fmt, ...)
+{
+	char buf[512]; va_list ap; va_start(ap, fmt); const int n = vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+	if (n > 0) out.append(buf, std::min<size_t>((size_t)n, sizeof(buf) - 1));
+}
+static int cmd_stats(int argc, char **argv)
+{
+	const char *const usage = "usage: sambamba stats [-t N] [-F FILTER] [-c MIN,MAX,STEP] [-i N] [-m FRAC] [-x] [--max-read-length N] <in.bam>";
+	const char *expr = 0, *in = 0; bool sparse = false; float main_bulk = 0.99f;   /* (isize_main_bulk is a float in stats_info_t) */
+	ssg_stats_opt_t o; o.max_len = 1024; o.n_isize = 8000; o.cov_min = 1; o.cov_max = 1000; o.cov_step = 1; o.span = 0;
+	for (int i = 0; i < argc; ++i) {
+		const char *a = argv[i];
+		if (!strcmp(a, "-t") && i + 1 < argc) ++i;   /* (the work is the device's) */
+		else if (!strcmp(a, "-F") && i + 1 < argc) expr = argv[++i];
+		else if (!strcmp(a, "-c") && i + 1 < argc) { if (sscanf(argv[++i], "%d,%d,%d", &o.cov_min, &o.cov_max, &o.cov_step) != 3) die("stats: -c takes MIN,MAX,STEP"); }
+		else if (!strcmp(a, "-i") && i + 1 < argc) { int64_t v; if (!view_number(argv[++i], v) || v < 1 || v > (1 << 24)) die("stats: -i takes a number in 1 .. 2^24"); o.n_isize = (int32_t)v; }
+		else if (!strcmp(a, "-m") && i + 1 < argc) main_bulk = (float)atof(argv[++i]);
+		else if (!strcmp(a, "-x")) sparse = true;
+		else if (!strcmp(a, "--max-read-length") && i + 1 < argc) { int64_t v; if (!view_number(argv[++i], v) || v < 1 || v > 65535) die("stats: --max-read-length takes a number in 1 .. 65535"); o.max_len = (int32_t)v; }
+		else if (a[0] == '-' && a[1]) die(std::string("stats: unsupported option ") + a);
+		else if (!in) in = a;
+		else die("stats: one input file (regions are not supported)");
+	}
+	if (!in) die(usage);
+	view_filter_t filter; if (expr) filter.compile(expr);
+	const char *const sp = getenv("SSG_STATS_SPAN");
+	if (sp && *sp) o.span = (int32_t)std::max<long long>(1, std::min<long long>(strtoll(sp, 0, 10), 1 << 28));
+	const int64_t n_cov = ssg_stats_ncov(&o);
+	if (n_cov < 0) die("stats: -c takes 0 <= MIN <= MAX <= 16777216 and STEP >= 1, with at most 8192 bins");
+	const int fd = open_in(in);
+	std::string why;
+	if (!dev_read_ready(fd, why)) die("stats: " + why + " (the tables are counted on the device; there is no host path)");
+	bam_hdr_t h; uint64_t v0 = 0;
+	{ bgzf_in_t bi(fd, 1); if (!hdr_read(bi, h)) die("stats: not a BAM file"); v0 = bi.tell(); }
+	recs_holder_t S;
+	struct stats_holder_t { ssg_stats_t *s; ~stats_holder_t() { if (s) ssg_stats_free(s); } } T = { 0 };   /* (freed before the store: declared behind it) */
+	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) die(std::string("stats: ") + ssg_last_error());
+	if (ssg_stats_create(S.r, filter.prog.data(), (int)filter.prog.size(), &o, &T.s)) die(std::string("stats: ") + ssg_last_error());
+	dev_prof_begin();
+	dev_batches_t R; R.init("stats", S.r, fd, in, (uint64_t)64 << 20, 1024); R.whole_file(v0);
+	for (;;) {
+		const int got = R.next();
+		if (got == DEV_FAIL) die("stats: " + R.why);
+		if (got != DEV_BATCH) break;
+		uint64_t n_rec = 0, desc = 0;
+		const int rc = ssg_stats_push(T.s, R.cid, R.hint.data(), (int64_t)R.hint.size() - 1, R.first, &n_rec, &desc);
+		if (rc) die("stats: " + dev_stage_error(rc, in, "ssg_stats_push: "));
+		if (ssg_recs_release(S.r, R.cid)) die(std::string("stats: ") + ssg_last_error());
+	}
+	if (ssg_stats_finish(T.s)) die(std::string("stats: ") + ssg_last_error());
+	const size_t rows = (size_t)o.max_len + 1, ni = (size_t)o.n_isize;
+	std::vector<uint64_t> sc(SSG_ST_N), quals(2 * rows * 256), acgt(rows * 6), gc(2 * SSG_STATS_NGC), isz(3 * ni), rl(rows), id(2 * SSG_STATS_NINDEL), ic(4 * rows), cov((size_t)n_cov);
+	if (ssg_stats_get(T.s, sc.data(), quals.data(), acgt.data(), gc.data(), isz.data(), rl.data(), id.data(), ic.data(), cov.data())) die(std::string("stats: ") + ssg_last_error());
+	dev_prof_report("sambamba", "stats");
+	/* output_stats: the insert sizes first (each pair was counted twice; ssg_stats_get has halved them) */
+	const uint64_t *const in_ = isz.data(), *const out_ = in_ + ni, *const oth_ = out_ + ni;
+	int ibulk = 0; uint64_t nisize = 0, n_in = 0, n_out = 0, n_oth = 0;
+	for (size_t k = 0; k < ni; ++k) { n_in += in_[k]; n_out += out_[k]; n_oth += oth_[k]; nisize += in_[k] + out_[k] + oth_[k]; }
+	double bulk = 0, avg_isize = 0, sd_isize = 0;
+	for (int k = 0; k < (int)ni; ++k) {
+		bulk += in_[k] + out_[k] + oth_[k];
+		avg_isize += k * (in_[k] + out_[k] + oth_[k]);
+		if (bulk / nisize > main_bulk) { ibulk = k + 1; nisize = bulk; break; }
+	}
+	avg_isize /= nisize ? nisize : 1;
+	for (int k = 1; k < ibulk; ++k) sd_isize += (in_[k] + out_[k] + oth_[k]) * (k - avg_isize) * (k - avg_isize) / nisize;
+	sd_isize = sqrt(sd_isize);
+	const uint64_t n1 = sc[SSG_ST_FIRST], n2 = sc[SSG_ST_LAST], total_len = sc[SSG_ST_TOTAL_LEN], mism = sc[SSG_ST_MISMATCHES], cig = sc[SSG_ST_BASES_CIGAR];
+	const double sum_qual = (double)sc[SSG_ST_SUM_QUAL];
+	int max_len = std::max<int>(30, (int)sc[SSG_ST_MAX_LEN]), max_qual = std::max<int>(40, (int)sc[SSG_ST_MAX_QUAL]);   /* stats_init's starting values */
+	std::string t;
+	auto flush = [&](bool all) { if (all || t.size() > ((size_t)1 << 20)) { io_write_all(1, t.data(), t.size()); t.clear(); } };
+	stats_put(t, "# This file was produced by sambamba stats (libssgpu %s, %s) in the layout of samtools stats 1.3.1 and can be plotted using plot-bamstats\n", ssg_version(), ssg_backend());
+	stats_put(t, "# This file contains statistics for all reads.\n");
+	t += std::string("# The input was:  ") + in + (expr ? std::string("  filtered by:  ") + expr : std::string()) + "\n";
+	stats_put(t, "# CHK, Checksum\t[2]Read Names\t[3]Sequences\t[4]Qualities\n");
+	stats_put(t, "# CHK, CRC32 of reads which passed filtering followed by addition (32bit overflow)\n");
+	stats_put(t, "CHK\t%08x\t%08x\t%08x\n", (unsigned)sc[SSG_ST_CHK_NAMES], (unsigned)sc[SSG_ST_CHK_READS], (unsigned)sc[SSG_ST_CHK_QUALS]);
+	stats_put(t, "# Summary Numbers. Use `grep ^SN | cut -f 2-` to extract this part.\n");
+	stats_put(t, "SN\traw total sequences:\t%ld\n", (long)(sc[SSG_ST_FILTERED] + n1 + n2));
+	stats_put(t, "SN\tfiltered sequences:\t%ld\n", (long)sc[SSG_ST_FILTERED]);
+	stats_put(t, "SN\tsequences:\t%ld\n", (long)(n1 + n2));
+	stats_put(t, "SN\tis sorted:\t%d\n", sc[SSG_ST_SORTED] ? 1 : 0);
+	stats_put(t, "SN\t1st fragments:\t%ld\n", (long)n1);
+	stats_put(t, "SN\tlast fragments:\t%ld\n", (long)n2);
+	stats_put(t, "SN\treads mapped:\t%ld\n", (long)(sc[SSG_ST_PAIRED_MAPPED] + sc[SSG_ST_SINGLE]));
+	stats_put(t, "SN\treads mapped and paired:\t%ld\t# paired-end technology bit set + both mates mapped\n", (long)sc[SSG_ST_PAIRED_MAPPED]);
+	stats_put(t, "SN\treads unmapped:\t%ld\n", (long)sc[SSG_ST_UNMAPPED]);
+	stats_put(t, "SN\treads properly paired:\t%ld\t# proper-pair bit set\n", (long)sc[SSG_ST_PROPER]);
+	stats_put(t, "SN\treads paired:\t%ld\t# paired-end technology bit set\n", (long)sc[SSG_ST_PAIRED]);
+	stats_put(t, "SN\treads duplicated:\t%ld\t# PCR or optical duplicate bit set\n", (long)sc[SSG_ST_DUP]);
+	stats_put(t, "SN\treads MQ0:\t%ld\t# mapped and MQ=0\n", (long)sc[SSG_ST_MQ0]);
+	stats_put(t, "SN\treads QC failed:\t%ld\n", (long)sc[SSG_ST_QCFAIL]);
+	stats_put(t, "SN\tnon-primary alignments:\t%ld\n", (long)sc[SSG_ST_SECONDARY]);
+	stats_put(t, "SN\ttotal length:\t%ld\t# ignores clipping\n", (long)total_len);
+	stats_put(t, "SN\tbases mapped:\t%ld\t# ignores clipping\n", (long)sc[SSG_ST_BASES_MAPPED]);
+	stats_put(t, "SN\tbases mapped (cigar):\t%ld\t# more accurate\n", (long)cig);
+	stats_put(t, "SN\tbases trimmed:\t%ld\n", 0l);
+	stats_put(t, "SN\tbases duplicated:\t%ld\n", (long)sc[SSG_ST_DUP_LEN]);
+	stats_put(t, "SN\tmismatches:\t%ld\t# from NM fields\n", (long)mism);
+	stats_put(t, "SN\terror rate:\t%e\t# mismatches / bases mapped (cigar)\n", cig ? (float)mism / cig : 0);   /* a float quotient, as the C expression has it */
+	const float avg_read_length = (n1 + n2) ? total_len / (n1 + n2) : 0;   /* an integer quotient */
+	stats_put(t, "SN\taverage length:\t%.0f\n", avg_read_length);
+	stats_put(t, "SN\tmaximum length:\t%d\n", max_len);
+	stats_put(t, "SN\taverage quality:\t%.1f\n", total_len ? sum_qual / total_len : 0);
+	stats_put(t, "SN\tinsert size average:\t%.1f\n", avg_isize);
+	stats_put(t, "SN\tinsert size standard deviation:\t%.1f\n", sd_isize);
+	stats_put(t, "SN\tinward oriented pairs:\t%ld\n", (long)n_in);
+	stats_put(t, "SN\toutward oriented pairs:\t%ld\n", (long)n_out);
+	stats_put(t, "SN\tpairs with other orientation:\t%ld\n", (long)n_oth);
+	stats_put(t, "SN\tpairs on different chromosomes:\t%ld\n", (long)sc[SSG_ST_ANOMALOUS] / 2);
+	if (max_len < (int)rows) max_len++;
+	if (max_qual + 1 < 256) max_qual++;
+	for (int f = 0; f < 2; ++f) {
+		stats_put(t, "# %s Fragment Qualitites. Use `grep ^%s | cut -f 2-` to extract this part.\n", f ? "Last" : "First", f ? "LFQ" : "FFQ");
+		stats_put(t, "# Columns correspond to qualities and rows to cycles. First column is the cycle number.\n");
+		for (int b = 0; b < max_len && b < (int)rows; ++b) {
+			stats_put(t, "%s\t%d", f ? "LFQ" : "FFQ", b + 1);
+			for (int q = 0; q <= max_qual; ++q) stats_put(t, "\t%ld", (long)quals[((size_t)f * rows + (size_t)b) * 256 + (size_t)q]);
+			t += '\n'; flush(false);
+		}
+	}
+	for (int f = 0; f < 2; ++f) {
+		stats_put(t, "# GC Content of %s fragments. Use `grep ^%s | cut -f 2-` to extract this part.\n", f ? "last" : "first", f ? "GCL" : "GCF");
+		const uint64_t *g = gc.data() + (size_t)f * SSG_STATS_NGC; int prev = 0;
+		for (int b = 0; b < SSG_STATS_NGC; ++b) {
+			if (g[b] == g[prev]) continue;
+			stats_put(t, "%s\t%.2f\t%ld\n", f ? "GCL" : "GCF", (b + prev) * 0.5 * 100. / (SSG_STATS_NGC - 1), (long)g[prev]);
+			prev = b;
+		}
+	}
+	stats_put(t, "# ACGT content per cycle. Use `grep ^GCC | cut -f 2-` to extract this part. The columns are: cycle; A,C,G,T base counts as a percentage of all A/C/G/T bases [%%]; and N and O counts as a percentage of all A/C/G/T bases [%%]\n");
+	for (int b = 0; b < max_len && b < (int)rows; ++b) {
+		const uint64_t *c = acgt.data() + (size_t)b * 6; const uint64_t sum = c[0] + c[1] + c[2] + c[3];
+		if (!sum) continue;
+		stats_put(t, "GCC\t%d\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\n", b + 1, 100. * c[0] / sum, 100. * c[1] / sum, 100. * c[2] / sum, 100. * c[3] / sum, 100. * c[4] / sum, 100. * c[5] / sum);
+	}
+	stats_put(t, "# Insert sizes. Use `grep ^IS | cut -f 2-` to extract this part. The columns are: insert size, pairs total, inward oriented pairs, outward oriented pairs, other pairs\n");
+	for (int k = 0; k < ibulk; ++k) {
+		const long a = (long)in_[k], b = (long)out_[k], c = (long)oth_[k];
+		if (!sparse || a + b + c > 0) stats_put(t, "IS\t%d\t%ld\t%ld\t%ld\t%ld\n", k, a + b + c, a, b, c);
+		flush(false);
+	}
+	stats_put(t, "# Read lengths. Use `grep ^RL | cut -f 2-` to extract this part. The columns are: read length, count\n");
+	for (int k = 0; k < max_len && k < (int)rows; ++k) if (rl[(size_t)k] > 0) stats_put(t, "RL\t%d\t%ld\n", k, (long)rl[(size_t)k]);
+	stats_put(t, "# Indel distribution. Use `grep ^ID | cut -f 2-` to extract this part. The columns are: length, number of insertions, number of deletions\n");
+	for (int k = 0; k < SSG_STATS_NINDEL; ++k) if (id[(size_t)k] > 0 || id[SSG_STATS_NINDEL + (size_t)k] > 0) stats_put(t, "ID\t%d\t%ld\t%ld\n", k + 1, (long)id[(size_t)k], (long)id[SSG_STATS_NINDEL + (size_t)k]);
+	stats_put(t, "# Indels per cycle. Use `grep ^IC | cut -f 2-` to extract this part. The columns are: cycle, number of insertions (fwd), .. (rev) , number of deletions (fwd), .. (rev)\n");
+	for (size_t k = 0; k < rows; ++k)
+		if (ic[k] > 0 || ic[rows + k] > 0 || ic[2 * rows + k] > 0 || ic[3 * rows + k] > 0) stats_put(t, "IC\t%d\t%ld\t%ld\t%ld\t%ld\n", (int)k + 1, (long)ic[k], (long)ic[rows + k], (long)ic[2 * rows + k], (long)ic[3 * rows + k]);
+	stats_put(t, "# Coverage distribution. Use `grep ^COV | cut -f 2-` to extract this part.\n");
+	if (!sc[SSG_ST_SORTED]) stats_put(t, "# COV is not computed: the file is not sorted by coordinate\n");
+	else {
+		int step = o.cov_step;   /* as init_stat_structs rounds it */
+		if (step > o.cov_max - o.cov_min + 1) { step = o.cov_max - o.cov_min; if (step <= 0) step = 1; }
+		if (cov[0]) stats_put(t, "COV\t[<%d]\t%d\t%ld\n", o.cov_min, o.cov_min - 1, (long)cov[0]);
+		for (int k = 1; k < (int)n_cov - 1; ++k)
+			if (cov[(size_t)k]) stats_put(t, "COV\t[%d-%d]\t%d\t%ld\n", o.cov_min + (k - 1) * step, o.cov_min + k * step - 1, o.cov_min + k * step - 1, (long)cov[(size_t)k]);
+		if (cov[(size_t)n_cov - 1]) stats_put(t, "COV\t[%d<]\t%d\t%ld\n", o.cov_min + ((int)n_cov - 2) * step - 1, o.cov_min + ((int)n_cov - 2) * step - 1, (long)cov[(size_t)n_cov - 1]);
+	}
+	stats_put(t, "# GC-depth. Use `grep ^GCD | cut -f 2-` to extract this part. The columns are: GC%%, unique sequence percentiles, 10th, 25th, 50th, 75th and 90th depth percentile\n");
+	stats_put(t, "# GCD is not computed\n");
+	flush(true);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
-	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge|flagstat|depth> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
+	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge|flagstat|depth|stats> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
 #ifdef F_SETPIPE_SZ
 	(void)fcntl(0, F_SETPIPE_SZ, 1 << 20); (void)fcntl(1, F_SETPIPE_SZ, 1 << 20);   /* the reference's pipelines: fewer wake-ups per megabyte (fails harmlessly on files) */
 #endif
@@ -2141,6 +2316,7 @@ int main(int argc, char **argv)
 	if (!strcmp(argv[1], "flagstat")) return cmd_flagstat(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "merge")) return cmd_merge(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "depth")) return cmd_depth(argc - 2, argv + 2);
+	if (!strcmp(argv[1], "stats")) return cmd_stats(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "index-parts")) return cmd_index_parts(argc - 2, argv + 2);
 	fprintf(stderr, "[sambamba] unsupported sub-command %s\n", argv[1]);
 	return 2;
