@@ -13,7 +13,7 @@ lib: speedseq_amd/libssgpu.so
 # Every object's prerequisites come from the compiler (-MMD): no hand-kept header lists, so no object can be stale against a shared
 # declaration (round 3 shipped variant libraries linked from objects of different ages).
 # the translation units hipcc compiles (sam_format.cpp is plain C++)
-UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_bam_select ssg_msw_replay ssg_bam ssg_coll ssg_b2f ssg_depth ssg_stats
+UNITS   = ssgpu_core ssg_dbg ssg_index_build ssg_seed ssg_bgzf ssg_bgzf_deep ssg_bgzf_frame ssg_bgzf_inflate ssg_rec_gather ssg_bam_scan ssg_bam_select ssg_msw_replay ssg_bam ssg_coll ssg_b2f ssg_depth ssg_stats ssg_markdup
 HIPOBJS = $(UNITS:%=$(CSRC)/%.o)
 HIPSRCS = $(UNITS:%=$(CSRC)/%.cpp)
 $(HIPOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp
@@ -155,10 +155,20 @@ tests/emu/stats_fuzz: tools/dbg/stats_fuzz.cpp $(STATSFUZZ_SRCS) tests/emu/emu.c
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
 		tools/dbg/stats_fuzz.cpp $(STATSFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
 
+# memory safety and exactness of the duplicate decision (k_markdup.h): the emulated kernels under AddressSanitizer and UndefinedBehaviorSanitizer on 3000 seeded record
+# streams in one to three chunks, every hash width, a broken record in every seventh, the duplicate bits, the counts and the bytes behind the second pass against a
+# plain C++ loop of the rule (tools/dbg/markdup_fuzz.cpp; a stand-alone program for the CPU, not part of `emu')
+MARKDUPFUZZ_SRCS = $(CSRC)/ssg_markdup.cpp $(CSRC)/ssg_bam_scan.cpp $(CSRC)/ssg_rec_gather.cpp $(CSRC)/ssg_bgzf_inflate.cpp $(CSRC)/ssg_bgzf_frame.cpp
+fuzz-markdup: tests/emu/markdup_fuzz
+	tests/emu/markdup_fuzz
+tests/emu/markdup_fuzz: tools/dbg/markdup_fuzz.cpp $(MARKDUPFUZZ_SRCS) tests/emu/emu.cpp tests/emu/emu.h $(KHDRS)
+	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DSSG_EMU -Itests/emu -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-variable \
+		tools/dbg/markdup_fuzz.cpp $(MARKDUPFUZZ_SRCS) tests/emu/emu.cpp -o $@ -lpthread -lz
+
 clean:
 	rm -rf build; rm -f speedseq_amd/libssgpu.so speedseq_amd/libssgpu_*.so $(CSRC)/*.d tests/emu/libssgpu_emu.so bin/bwa bin/samblaster bin/sambamba bin/bamkit tests/emu/bwa_emu tests/emu/samblaster_emu tests/emu/sambamba_emu tests/emu/bamkit_emu tests/emu/fq_dump tests/emu/fi_test tests/emu/fi_mt_test tests/emu/scan_test tests/emu/cut_test tests/emu/inflate_fuzz tests/emu/bam_scan_fuzz tests/emu/bam_select_fuzz tests/emu/deflate_deep_fuzz tests/emu/b2f_fuzz tests/emu/depth_fuzz tests/emu/stats_fuzz $(CSRC)/*.o
 	$(MAKE) -C oracle clean
-.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep fuzz-b2f fuzz-depth fuzz-stats
+.PHONY: all lib tools oracle emu clean variant tune fuzz-inflate fuzz-bam-scan fuzz-bam-select fuzz-deflate-deep fuzz-b2f fuzz-depth fuzz-stats fuzz-markdup
 
 # A/B builds of the device library with other compile-time parameters (bench / tests: SSGPU_LIB=speedseq_amd/libssgpu_$(NAME).so); never the
 # default.  The units named in VUNITS (default: all) are compiled with VFLAGS into build/$(NAME)/; the others are the product build's

@@ -654,6 +654,54 @@ int  ssg_stats_finish(ssg_stats_t *s);
 int  ssg_stats_get(ssg_stats_t *s, uint64_t *scalars, uint64_t *quals, uint64_t *bases, uint64_t *gc, uint64_t *isize, uint64_t *rl, uint64_t *id, uint64_t *ic, uint64_t *cov);
 void ssg_stats_free(ssg_stats_t *s);
 
+/* ---- `sambamba markdup' on the device (csrc/ssg_markdup.cpp, k_markdup.h): Picard MarkDuplicates' rule, as `sambamba markdup' documents it, over a stream that passes twice ----
+ * The stream is the records of the pushes, in order (ssg_recs_append_bgzf, then ssg_markdup_push); a record's ordinal is its running number from 0.  Nothing
+ * requires a coordinate-sorted stream: the decision is a global sort, not a sweep.
+ *   Library: lib_of_rg[] of the record's RG:Z value -- the aux area walked as ssg_b2f_push walks it, the last RG:Z met -- and 0 without one or with a value that
+ *     is not in rg[].  The caller maps @RG ID -> LB: equal LB strings share an id >= 1, an @RG without LB has 0.
+ *   Taking part: flag & 0x904 clear and n_cigar > 0.  Every other record leaves as it came, its 0x400 included.
+ *   End key of a taking-part record: (library, tid, u5, rev), rev = flag >> 4 & 1; u5 = pos - the lengths of the leading run of S and H operations (rev == 0),
+ *     or end - 1 + the lengths of the trailing run of S and H operations (rev == 1, `end' as in ssg_bam_ent_t), in 64 bits.
+ *   Score: the sum of the l_seq quality bytes that are >= 15, bytes taken unsigned, saturating at 2^30 - 1; 0 for l_seq == 0.
+ *   Paired: a taking-part record with flag & 1 set and flag & 8 clear, by its flags alone.  The others are fragments.
+ *   Mates: among the paired records of one name (l_qname - 1 bytes compared whole, library apart), in ordinal order: nothing held -- the record is held; the
+ *     held one has the same flag & 0xc0 -- the record stays unmatched, the held one held; otherwise the two are a pair and nothing is held.
+ *   Pair key: the two end keys ordered by (tid, u5, rev), the forward end first on a tie (Picard's RF -> FR), a lower library first when these are equal; pair
+ *     score: the sum of the two scores; pair ordinal: the smaller of the two.
+ *   Pairs: among pairs of one pair key the highest score is kept, on equal scores the smallest pair ordinal; both records of every other pair are duplicates.
+ *   Fragments: among all taking-part records of one end key, if one of them is paired (matched or not) every fragment is a duplicate; otherwise the fragment
+ *     with the highest score is kept, the smallest ordinal among equals, and the other fragments are duplicates.  A paired record is never marked by this step.
+ *   Result: a taking-part record has 0x400 cleared, then set when it is a duplicate: one byte of the record.  With `remove' the duplicates leave instead.
+ * ssg_markdup_create: rg[0 .. n_rg) are the @RG ids, lib_of_rg[] their libraries; hash_bits in 0 .. 64 is how much of the 64-bit name hash groups the paired
+ *   records for the mate join -- results do not depend on it, callers pass 64.  The object lives on the store's device and must be freed before the store; its
+ *   entries (40 bytes a record), the names of the paired records and the bitmap are device memory that counts against the store's capacity.  SSG_EINVAL for a
+ *   NULL store, a NULL or empty id, n_rg < 0, no lib_of_rg[], hash_bits outside 0 .. 64.
+ * ssg_markdup_push: the chunk's records are found as ssg_recs_scan finds them (the same hints, `first', SSG_EIO / SSG_EALIGN / SSG_EINVAL and words, under this
+ *   entry's name).  SSG_EIO also for a record with 32 + l_qname + 4 n_cigar + (l_seq + 1) / 2 + l_seq > block_size (its offset in ssg_last_error());
+ *   SSG_ENOMEM when the entries and names do not fit the store's capacity or the device; SSG_EINVAL after ssg_markdup_finish, while an order is declared, and
+ *   past 2^32 - 16 records.  On every failure the object, the store and the chunk are as before and the call may be repeated.  On success the chunk is released.
+ * ssg_markdup_finish: decides; counts[SSG_MD_N].  SSG_ERANGE when more than SSG_MARKDUP_RUN_MAX paired records share one name hash of hash_bits bits: the
+ *   object is as before the call.  Zero records succeed.  After it only get, apply and free.
+ * ssg_markdup_get: dup[k] = 1 when ordinal ord0 + k is a duplicate, else 0 (tests).  SSG_EINVAL before finish and past the records.
+ * ssg_markdup_apply: the second pass -- the same stream's chunks, in the same order; the object keeps the running ordinal.  THIS ENTRY CHANGES RECORD BYTES: the
+ *   flag byte that holds 0x400, in the store's chunk, of every taking-part record.  loc / ent of the kept records (all of them with remove == 0; ent.flag as
+ *   patched) come back in stream order for ssg_recs_order; the chunk is not released.
+ *     SSG_EINVAL     before finish; a chunk that runs past the records counted by the pushes; while an order is declared;
+ *     SSG_EIO        a record whose block_size or name hash is not what its ordinal had in the first pass (the stream changed between the passes; the ordinal
+ *                    in ssg_last_error());
+ *     SSG_EOVERFLOW  cap < *n_kept: *n_rec and *n_kept are set, nothing is written.  cap == 0 with loc and ent NULL is the counting form: the two numbers.
+ *   Nothing is patched and the running ordinal stays unless 0 is returned with the arrays written. */
+#define SSG_MARKDUP_RUN_MAX 256
+enum { SSG_MD_RECORDS, SSG_MD_TAKING_PART, SSG_MD_PAIRED, SSG_MD_PAIRS, SSG_MD_UNMATCHED, SSG_MD_FRAGMENTS, SSG_MD_DUP_PAIRED, SSG_MD_DUP_FRAGMENTS, SSG_MD_N = 16 };
+typedef struct ssg_markdup ssg_markdup_t;
+int  ssg_markdup_create(ssg_recs_t *r, const char *const *rg, const uint16_t *lib_of_rg, int n_rg, int hash_bits, ssg_markdup_t **out);
+int  ssg_markdup_push(ssg_markdup_t *m, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, uint64_t *n_rec);
+int  ssg_markdup_finish(ssg_markdup_t *m, uint64_t *counts /* SSG_MD_N */);
+int  ssg_markdup_get(ssg_markdup_t *m, uint64_t ord0, uint64_t n, uint8_t *dup);
+int  ssg_markdup_apply(ssg_markdup_t *m, uint32_t chunk_id, const uint64_t *hint, int64_t n_hints, uint64_t first, int remove, uint64_t cap,
+                       uint64_t *n_rec, uint64_t *n_kept, uint64_t *loc, ssg_bam_ent_t *ent);
+void ssg_markdup_free(ssg_markdup_t *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1027,6 +1027,88 @@ def stats_get(lib, s):
     return rc, out
 
 
+MARKDUP_RUN_MAX = 256
+MARKDUP_COUNTS = ("records", "taking_part", "paired", "pairs", "unmatched", "fragments", "dup_paired", "dup_fragments")
+MARKDUP_N_COUNTS = 16
+
+
+class Markdup:
+    """the duplicate decision on a record store (ssg_markdup_*): freed with the object or by close(), before its store."""
+
+    def __init__(self, lib, h, recs):
+        self.lib, self.h, self.recs = lib, h, recs   # (the store is kept alive: the entries count against it)
+
+    def close(self):
+        if self.h is not None:
+            self.lib.l.ssg_markdup_free.argtypes = [C.c_void_p]
+            self.lib.l.ssg_markdup_free.restype = None
+            if self.recs.h is not None:
+                self.lib.l.ssg_markdup_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def markdup_create(lib, recs, rg=(), lib_of_rg=(), hash_bits=64, n_rg=None):
+    """ssg_markdup_create: rg the @RG ids (bytes or str; None stands for a NULL id), lib_of_rg their libraries; n_rg: another count than len(rg) (tests).
+    Returns (rc, Markdup or None); no return code raises."""
+    ids = [None if x is None else (x if isinstance(x, bytes) else x.encode()) for x in rg]
+    arr = (C.c_char_p * max(len(ids), 1))(*ids)
+    libs = np.ascontiguousarray(lib_of_rg, dtype=np.uint16)
+    h = C.c_void_p()
+    rc = lib.l.ssg_markdup_create(recs.h if recs is not None else None, arr if ids else None, _ptr(libs) if len(libs) else None, C.c_int(len(ids) if n_rg is None else n_rg),
+                                  C.c_int(hash_bits), C.byref(h))
+    return rc, (Markdup(lib, h, recs) if rc == 0 else None)
+
+
+def markdup_push(lib, m, chunk_id, hint, first=0):
+    """ssg_markdup_push: returns (rc, n_rec); no return code raises."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_rec = C.c_uint64(0)
+    rc = lib.l.ssg_markdup_push(m.h, C.c_uint32(chunk_id), _ptr(hint) if len(hint) else None, C.c_int64(len(hint) - 1), C.c_uint64(first), C.byref(n_rec))
+    return rc, int(n_rec.value)
+
+
+def markdup_finish(lib, m):
+    """ssg_markdup_finish: (rc, the counts by name (MARKDUP_COUNTS))."""
+    c = np.zeros(MARKDUP_N_COUNTS + 1, dtype=np.uint64)
+    c[MARKDUP_N_COUNTS] = 0xABABABAB
+    rc = lib.l.ssg_markdup_finish(m.h, _ptr(c))
+    assert int(c[MARKDUP_N_COUNTS]) == 0xABABABAB                       # nothing behind the counts
+    return rc, {name: int(c[i]) for i, name in enumerate(MARKDUP_COUNTS)}
+
+
+def markdup_get(lib, m, ord0, n):
+    """ssg_markdup_get: (rc, the duplicate bits of ordinals ord0 .. ord0 + n as uint8)."""
+    dup = np.full(max(int(n), 0) + 1, 0xAB, dtype=np.uint8)
+    rc = lib.l.ssg_markdup_get(m.h, C.c_uint64(ord0), C.c_uint64(n), _ptr(dup))
+    assert int(dup[-1]) == 0xAB                                          # nothing behind the bits
+    return rc, dup[:-1]
+
+
+def markdup_apply(lib, m, chunk_id, hint, first=0, remove=False, cap=None, counting=False):
+    """ssg_markdup_apply: returns (rc, n_rec, n_kept, loc, ent), the arrays holding the kept records; counting=True is the counting form (cap 0, no arrays:
+    loc and ent are None).  On a failure the arrays are as the call left them (cap elements, prefilled with 0xAB bytes).  No return code raises."""
+    hint = np.ascontiguousarray(hint, dtype=np.uint64)
+    n_hints = len(hint) - 1
+    n_rec, n_kept = C.c_uint64(0), C.c_uint64(0)
+    head = (m.h, C.c_uint32(chunk_id), _ptr(hint) if len(hint) else None, C.c_int64(n_hints), C.c_uint64(first), C.c_int(1 if remove else 0))
+    if counting:
+        rc = lib.l.ssg_markdup_apply(*head, C.c_uint64(0), C.byref(n_rec), C.byref(n_kept), None, None)
+        return rc, int(n_rec.value), int(n_kept.value), None, None
+    if cap is None:
+        cap = int(hint[-1]) // 36 if n_hints >= 0 and len(hint) else 0
+    loc = np.full(cap + 1, 0xABABABABABABABAB, dtype=np.uint64)
+    ent = np.frombuffer(np.full((cap + 1) * BAM_ENT_DT.itemsize, 0xAB, dtype=np.uint8).tobytes(), dtype=BAM_ENT_DT).copy()
+    rc = lib.l.ssg_markdup_apply(*head, C.c_uint64(cap), C.byref(n_rec), C.byref(n_kept), _ptr(loc), _ptr(ent))
+    n = int(n_kept.value)
+    assert int(loc[cap]) == 0xABABABABABABABAB and ent[cap:].tobytes() == b"\xab" * BAM_ENT_DT.itemsize   # nothing behind cap
+    if rc == 0:
+        return rc, int(n_rec.value), n, loc[:n], ent[:n]
+    return rc, int(n_rec.value), n, loc, ent
+
+
 def sam_format(lib, idx, opt, res, names, seq, off, quals=None, rg_id=""):
     n = 2 * res.n_pairs
     NA = (C.c_char_p * n)(*[s.encode() for s in names])

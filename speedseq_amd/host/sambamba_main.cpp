@@ -2302,9 +2302,154 @@ static int cmd_stats(int argc, char **argv)
 	return 0;
 }
 
+/* ---------------- markdup: Picard's duplicate rule, decided on the device (ssg_markdup_*, include/ssgpu.h) ----------------
+ * The file is read twice, each time in batches of whole members that go into the record store.  The first pass pushes every batch (ssg_markdup_push leaves an
+ * entry per record on the device and releases the batch) and decides (ssg_markdup_finish); the second patches the flag bytes of a batch in the store and writes
+ * its kept records as view_device writes BAM: declared as the stream, cut into blocks by bgzf_out_t::record's rule, gathered, deflated and framed on the device.
+ * At -l 0 the batch is gathered to the host and leaves through bgzf_out_t: stored blocks are the host's.  The header is the input's, with no @PG added.
+ * --tmpdir, --hash-table-size, --overflow-list-size, --sort-buffer-size, --io-buffer-size and -p are upstream's host-memory and progress knobs: taken and
+ * ignored.  SSG_MARKDUP_BATCH: the inflated bytes of a batch (default 64 MB; tests: groups and mates in different batches).  There is no host path. */
+static void markdup_libraries(const bam_hdr_t &h, std::vector<std::string> &ids, std::vector<uint16_t> &libs)
+{
+	std::unordered_map<std::string, uint16_t> lib_id;
+	size_t at = 0;
+	while (at < h.text.size()) {
+		size_t e = h.text.find('\n', at); if (e == std::string::npos) e = h.text.size();
+		const std::string line = h.text.substr(at, e - at); at = e + 1;
+		if (line.compare(0, 4, "@RG\t") != 0) continue;
+		std::string id, lb; bool has_lb = false;
+		size_t f = 4;
+		while (f <= line.size()) {
+			size_t fe = line.find('\t', f); if (fe == std::string::npos) fe = line.size();
+			if (line.compare(f, 3, "ID:") == 0) id = line.substr(f + 3, fe - f - 3);
+			else if (line.compare(f, 3, "LB:") == 0) { lb = line.substr(f + 3, fe - f - 3); has_lb = true; }
+			f = fe + 1;
+		}
+		if (id.empty()) continue;
+		uint16_t l = 0;
+		if (has_lb) {
+			auto it = lib_id.find(lb);
+			if (it == lib_id.end()) {
+				if (lib_id.size() >= 65535) die("markdup: more than 65535 libraries in the header");
+				it = lib_id.emplace(lb, (uint16_t)(lib_id.size() + 1)).first;
+			}
+			l = it->second;
+		}
+		ids.push_back(id); libs.push_back(l);
+	}
+}
+static int cmd_markdup(int argc, char **argv)
+{
+	const char *const usage = "usage: sambamba markdup [-r] [-t N] [-l LEVEL] [-p] [--tmpdir=DIR] [--hash-table-size=N] [--overflow-list-size=N] [--sort-buffer-size=N] [--io-buffer-size=N] <in.bam> <out.bam>";
+	int threads = hw_threads(), level = -1; bool remove = false; const char *in = 0, *outp = 0;
+	for (int i = 0; i < argc; ++i) {
+		const char *a = argv[i];
+		if (!strcmp(a, "-r") || !strcmp(a, "--remove-duplicates")) remove = true;
+		else if (!strcmp(a, "-t") && i + 1 < argc) threads = std::max(1, atoi(argv[++i]));
+		else if (!strcmp(a, "-l") && i + 1 < argc) level = atoi(argv[++i]);
+		else if (!strcmp(a, "-p") || !strcmp(a, "--show-progress")) {}
+		else if (!strncmp(a, "--tmpdir=", 9) || !strncmp(a, "--hash-table-size=", 18) || !strncmp(a, "--overflow-list-size=", 21) || !strncmp(a, "--sort-buffer-size=", 19) || !strncmp(a, "--io-buffer-size=", 17)) {}
+		else if (a[0] == '-' && a[1]) die(std::string("markdup: unsupported option ") + a);
+		else if (!in) in = a;
+		else if (!outp) outp = a;
+		else die("markdup: one input file and one output file (sambamba merge joins several inputs first)");
+	}
+	if (!in || !outp) die(usage);
+	{ const char *e = getenv("SSG_BAM_LEVEL"); if (level < 0 && e && *e) level = atoi(e); }   /* as sort: zlib's 6 when -l is not given */
+	const int fd = open_in(in);
+	std::string why;
+	if (!dev_read_ready(fd, why)) die("markdup: " + why + " (the file is read twice and decided on the device; there is no host path)");
+	bam_hdr_t h; uint64_t v0 = 0;
+	{ bgzf_in_t bi(fd, 1); if (!hdr_read(bi, h)) die("markdup: not a BAM file"); v0 = bi.tell(); }
+	std::vector<std::string> ids; std::vector<uint16_t> libs; std::vector<const char*> idp;
+	markdup_libraries(h, ids, libs);
+	for (const std::string &s : ids) idp.push_back(s.c_str());
+	const char *const be = getenv("SSG_MARKDUP_BATCH");
+	const uint64_t window = be && *be ? std::max<uint64_t>(1, strtoull(be, 0, 10)) : (uint64_t)64 << 20;
+	recs_holder_t S;
+	struct md_holder_t { ssg_markdup_t *m; ~md_holder_t() { if (m) ssg_markdup_free(m); } } T = { 0 };   /* (freed before the store: declared behind it) */
+	if (ssg_set_device(0) || ssg_recs_create(~(uint64_t)0 >> 1, &S.r)) die(std::string("markdup: ") + ssg_last_error());
+	if (ssg_markdup_create(S.r, idp.empty() ? 0 : idp.data(), libs.empty() ? 0 : libs.data(), (int)idp.size(), 64, &T.m)) die(std::string("markdup: ") + ssg_last_error());
+	dev_prof_begin();
+	const double t0 = wall();
+	{
+		dev_batches_t R; R.init("markdup", S.r, fd, in, window, 1024); R.whole_file(v0);
+		for (;;) {
+			const int got = R.next();
+			if (got == DEV_FAIL) die("markdup: " + R.why);
+			if (got != DEV_BATCH) break;
+			uint64_t n_rec = 0;
+			const int rc = ssg_markdup_push(T.m, R.cid, R.hint.data(), (int64_t)R.hint.size() - 1, R.first, &n_rec);
+			if (rc) die("markdup: " + dev_stage_error(rc, in, "ssg_markdup_push: "));
+		}
+	}
+	uint64_t counts[SSG_MD_N];
+	if (ssg_markdup_finish(T.m, counts)) die(std::string("markdup: ") + ssg_last_error());
+	/* the second pass */
+	const int out_fd = open(outp, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+	if (out_fd < 0) die(std::string("markdup: cannot write ") + outp);
+	g_partial_out = outp;
+	const bool stored = level == 0;
+	if (!stored) bgzf_dev_level_set(level);
+	const long BATCH = 1024;   /* blocks per device call */
+	const uint64_t out_cap = stored ? 0 : ssg_bgzf_bound((uint64_t)BATCH * BGZF_MAX_PAYLOAD, BATCH);
+	host_pinned_t O;
+	if (!stored && !O.grow(out_cap)) die("markdup: no page-locked memory for the output blocks");
+	bgzf_out_t ho(out_fd, stored ? 0 : level, threads);   /* the header's blocks; at -l 0 the records' too */
+	bool begun = false;
+	auto begin = [&]() { if (!begun) { hdr_write(ho, h); if (stored) ho.close_block(); else ho.drain(true); begun = true; g_partial_out = 0; } };
+	auto fail = [&](const std::string &m) { die("markdup: " + m + (begun ? " after output had begun" : "")); };
+	std::vector<uint64_t> loc, cum, cut, boff((size_t)BATCH + 1); std::vector<ssg_bam_ent_t> ent; std::vector<uint8_t> buf;
+	uint64_t n_out = 0;
+	{
+		dev_batches_t R; R.init("markdup", S.r, fd, in, window, 1024); R.whole_file(v0);
+		for (int got; (got = R.next()) != DEV_END; ) {
+			if (got == DEV_FAIL) fail(R.why);
+			const size_t nm = R.n();
+			uint64_t n_rec = 0, n_kept = 0;
+			const uint64_t cap = R.hint[nm] / 36 + 1;
+			loc.resize((size_t)cap); ent.resize((size_t)cap);
+			const int rc = ssg_markdup_apply(T.m, R.cid, R.hint.data(), (int64_t)nm, R.first, remove ? 1 : 0, cap, &n_rec, &n_kept, loc.data(), ent.data());
+			if (rc) fail(dev_stage_error(rc, in, "ssg_markdup_apply: "));
+			if (n_kept) {
+				cum.resize((size_t)n_kept + 1); cum[0] = 0;
+				for (uint64_t i = 0; i < n_kept; ++i) cum[(size_t)i + 1] = cum[(size_t)i] + ent[(size_t)i].len;
+				if (ssg_recs_order(S.r, loc.data(), cum.data(), (int64_t)n_kept)) fail(ssg_last_error());
+				if (stored) {
+					buf.resize((size_t)cum[(size_t)n_kept]);
+					if (ssg_recs_gather(S.r, 0, cum[(size_t)n_kept], buf.data())) fail(ssg_last_error());
+					begin();
+					for (uint64_t i = 0; i < n_kept; ++i) ho.record(buf.data() + cum[(size_t)i], (size_t)ent[(size_t)i].len);
+				} else {
+					bgzf_cut_blocks(cum.data(), (size_t)n_kept, cut);   /* (a batch ends its last block) */
+					const size_t nb = cut.size() - 1;
+					for (size_t b0 = 0; b0 < nb; b0 += (size_t)BATCH) {
+						const long k = (long)std::min<size_t>((size_t)BATCH, nb - b0);
+						if (dev_bgzf_compress_recs(S.r, cut.data() + b0, k, O.p, out_cap, boff.data(), 0)) fail(ssg_last_error());
+						begin();
+						io_write_all(out_fd, O.p, (size_t)boff[(size_t)k]);
+					}
+				}
+				if (ssg_recs_reopen(S.r)) fail(ssg_last_error());
+			}
+			if (ssg_recs_release(S.r, R.cid)) fail(ssg_last_error());
+			n_out += n_kept;
+		}
+	}
+	begin();
+	if (stored) ho.finish(); else io_write_all(out_fd, BGZF_EOF, 28);
+	close(out_fd);
+	fprintf(stderr, "[sambamba] markdup: %llu records, %llu taking part, %llu pairs, %llu unmatched paired, %llu fragments, %llu duplicates found (%llu in pairs, %llu fragments)%s, %llu records written, %.2f s\n",
+	        (unsigned long long)counts[SSG_MD_RECORDS], (unsigned long long)counts[SSG_MD_TAKING_PART], (unsigned long long)counts[SSG_MD_PAIRS], (unsigned long long)counts[SSG_MD_UNMATCHED],
+	        (unsigned long long)counts[SSG_MD_FRAGMENTS], (unsigned long long)(counts[SSG_MD_DUP_PAIRED] + counts[SSG_MD_DUP_FRAGMENTS]), (unsigned long long)counts[SSG_MD_DUP_PAIRED],
+	        (unsigned long long)counts[SSG_MD_DUP_FRAGMENTS], remove ? " and removed" : "", (unsigned long long)n_out, wall() - t0);
+	dev_prof_report("sambamba", "markdup");
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
-	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge|flagstat|depth|stats> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
+	if (argc < 2) { fprintf(stderr, "usage: sambamba <view|sort|index|merge|flagstat|depth|stats|markdup> ...  (libssgpu %s, %s)\n", ssg_version(), ssg_backend()); return 1; }
 #ifdef F_SETPIPE_SZ
 	(void)fcntl(0, F_SETPIPE_SZ, 1 << 20); (void)fcntl(1, F_SETPIPE_SZ, 1 << 20);   /* the reference's pipelines: fewer wake-ups per megabyte (fails harmlessly on files) */
 #endif
@@ -2317,6 +2462,7 @@ int main(int argc, char **argv)
 	if (!strcmp(argv[1], "merge")) return cmd_merge(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "depth")) return cmd_depth(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "stats")) return cmd_stats(argc - 2, argv + 2);
+	if (!strcmp(argv[1], "markdup")) return cmd_markdup(argc - 2, argv + 2);
 	if (!strcmp(argv[1], "index-parts")) return cmd_index_parts(argc - 2, argv + 2);
 	fprintf(stderr, "[sambamba] unsupported sub-command %s\n", argv[1]);
 	return 2;
